@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- test-points/sec for predict(mean+var+grad), N_train=250, D=11 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, ...,
+and the roofline of the timed launches).  ``--full`` adds what is measured or checked beside the
+headline: the CPU baseline, the host-to-host leg (``end_to_end``) and the parity spot check of the
+timed outputs against the oracle (``parity``) of the predict / Hessian workloads (``--workload
+mv`` and ``train`` check their outputs in every run, as before).  ``--dump-outputs DIR`` writes
+what the last timed step computed as DIR/<name>.npy (all rows, or a fixed seeded sample of them
+that keeps the dump within 64 MB; with several ranks, rank<r>_<name>.npy).
 
 A "step" is one pass of the fused predict kernel over one batch of M = 1e6 synthetic test
 rows (BASELINE config 2, "PROSAIL single-band": N_train=250, D=11, fp64, mean+var+grad)
@@ -11,7 +19,8 @@ that is ALREADY RESIDENT in HBM; outputs stay in HBM.  With N ranks every rank o
 (SURVEY.md section 8e), so scaling is weak.  torch is imported only for the multi-rank
 barrier / max-reduce (gloo); the product path is ctypes -> libgp_predict_hip.so.
 
-Extra objects on the JSON line (flat scalars only inside each: the driver's record keeps those):
+Extra objects on the JSON line (flat scalars only inside each: the driver's record keeps those;
+cpu_baseline and the e2e_* keys with --full only):
   roofline      the fused kernel against the FP64 pipe peak (matrix = vector on MI355X; the
                 binding roofline, arithmetic intensity ~746 flop/B).  ``achieved`` / ``frac`` count
                 the flops the kernel EXECUTES (matrix instructions issued + phase-A arithmetic),
@@ -73,6 +82,46 @@ def maxnorm_err(ref, got):
     return float(np.max(np.abs(ref - got)) / np.max(np.abs(ref)))
 
 
+DUMP_BYTES = 63 * 10 ** 6        # --dump-outputs: array data of every rank together (64 MB with the .npy headers)
+
+
+def dump_rows(n_rows, row_bytes, budget):
+    """Rows of an output to dump: all of them, or a fixed seeded sample (sorted) within ``budget`` bytes."""
+    k = min(n_rows, max(1, budget // row_bytes))
+    if k == n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(20250).choice(n_rows, k, replace=False))
+
+
+def fetch_rows(ctx, dptr, n_rows, row_shape, dtype, idx, chunk_bytes=256 << 20):
+    """Rows ``idx`` (sorted) of a row-major device array of ``n_rows`` rows, copied back a chunk at a time."""
+    row_shape = tuple(row_shape)
+    row_bytes = np.dtype(dtype).itemsize * int(np.prod(row_shape, dtype=np.int64))
+    per = max(1, chunk_bytes // row_bytes)
+    out = np.empty((len(idx),) + row_shape, dtype)
+    for r0 in range(0, n_rows, per):
+        lo, hi = np.searchsorted(idx, [r0, min(n_rows, r0 + per)])
+        if lo == hi:
+            continue
+        first, last = int(idx[lo]), int(idx[hi - 1]) + 1
+        if 4 * (hi - lo) < last - first:           # sparse sample: row by row
+            for j in range(lo, hi):
+                out[j] = ctx.to_host_at(dptr, int(idx[j]) * row_bytes, row_shape, dtype)
+        else:
+            blk = ctx.to_host_at(dptr, first * row_bytes, (last - first,) + row_shape, dtype)
+            out[lo:hi] = blk[idx[lo:hi] - first]
+    return out
+
+
+def write_outputs(dirname, arrays, rank=0, world=1):
+    """DIR/<name>.npy per output (rank<r>_<name>.npy when there are several ranks)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(dirname, ("rank%d_" % rank if world > 1 else "") + name + ".npy"), arr)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -94,6 +143,11 @@ def parse():
                     help="strong (c4 only): fixed --total-rows split over the ranks, host arrays in, "
                          "shared host array out")
     ap.add_argument("--total-rows", type=int, default=100000000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the host-to-host leg and the parity check against the "
+                         "oracle (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--cpu-worker", default="", help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -270,6 +324,10 @@ def bench_reconstruct(a):
     tol = 1e-12 if a.precision == "f64" else 1e-5
     if not err <= tol:
         raise SystemExit("reconstruct parity failed: %g" % err)
+    if a.dump_outputs:
+        rows = dump_rows(M, (1 + D) * B * isz, DUMP_BYTES)
+        write_outputs(a.dump_outputs, {"fwd": fetch_rows(ctx, d_f, M, (B,), dt, rows),
+                                       "jacobian": fetch_rows(ctx, d_j, M, (D, B), dt, rows)})
     bytes_step = (M * B + M * D * B) * isz            # written; coefficients are 0.06 % of it
     gbps = bytes_step / kern_s / 1e9
     out = {"metric": "test rows/sec for MultivariateEmulator reconstruction (fwd + Jacobian), 12 PCs, D=10, 2101 bands",
@@ -312,6 +370,8 @@ def bench_train(a):
     for _ in range(a.steps):
         cost, grad = ctx.likelihood_batch(thetas, inputs, targets)
     dt = (time.perf_counter() - t0) / a.steps
+    if a.dump_outputs:
+        write_outputs(a.dump_outputs, {"cost": cost, "grad": grad})
     mfma_flop = ((N + 7) // 8) * 136 * 2 * 2048     # matrix-core flops of one evaluation (N <= 256)
     n_cpu = min(8, E)
     t1 = time.perf_counter()
@@ -475,15 +535,20 @@ def bench_strong(a, grp):
     def step():
         model.predict(testing, out=out)
     dt = multi_gpu.timed_steps(grp, step, ctx.synchronize, a.steps, a.warmup)
-    # parity of this rank's slice of the gathered array (oracle = checker, after the timed region)
-    from oracle import gp_oracle
-    idx = np.sort(np.random.RandomState(5 + rank).choice(M, 1024, replace=False))
-    ref = gp_oracle.cpu_predict(inputs, theta, invQ, invQt, testing[idx])
-    errs = [maxnorm_err(r, g[idx]) for r, g in zip(ref, out)]
-    tol = 1e-10 if a.precision == "f64" else 1e-4
-    worst = grp.max(max(errs))
-    if not worst <= tol and not a.no_parity:
-        raise SystemExit("bench parity check failed on rank %d: %s" % (rank, errs))
+    if a.dump_outputs and rank == 0:        # the whole gathered array (timed_steps ends in a barrier)
+        rows = dump_rows(total, (2 + D) * 8, DUMP_BYTES)
+        write_outputs(a.dump_outputs, {name: v[rows] for name, v in
+                                       zip(("mu", "var", "deriv"), shared.views(0, total))})
+    if a.full:
+        # parity of this rank's slice of the gathered array (oracle = checker, after the timed region)
+        from oracle import gp_oracle
+        idx = np.sort(np.random.RandomState(5 + rank).choice(M, 1024, replace=False))
+        ref = gp_oracle.cpu_predict(inputs, theta, invQ, invQt, testing[idx])
+        errs = [maxnorm_err(r, g[idx]) for r, g in zip(ref, out)]
+        tol = 1e-10 if a.precision == "f64" else 1e-4
+        worst = grp.max(max(errs))
+        if not worst <= tol and not a.no_parity:
+            raise SystemExit("bench parity check failed on rank %d: %s" % (rank, errs))
     outd = None
     if rank == 0:
         value = a.steps * total / dt
@@ -507,8 +572,9 @@ def bench_strong(a, grp):
                                  "2 x 48 GB/s both ways at once, profiles/r03_pcie_duplex.txt; the staged pipeline reaches "
                                  "~65 GB/s for both directions together) and by host DRAM when several GPUs stream at once, "
                                  "not by HBM or the fp64 pipe"},
-            "parity": {"worst_over_ranks": worst, "tol": tol, "checked_rows_per_rank": 1024},
         }
+        if a.full:
+            outd["parity"] = {"worst_over_ranks": worst, "tol": tol, "checked_rows_per_rank": 1024}
         print(json.dumps(outd), flush=True)
     grp.barrier()
     del out
@@ -620,7 +686,7 @@ def main():
     # the CPU legs run first: they start worker processes, which must not happen once this
     # process has initialised the GPU
     cpu = None
-    if world == 1 and not a.no_cpu_baseline and a.workload == "c2":
+    if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "c2":
         cpu = cpu_baseline(a.cpu_sample, a.cpu_procs)
     ndev, n_gpus_used = devices_for(world)
     # one process per GPU: run on the cpus next to that GPU (numactl --cpunodebind by hand), so the
@@ -667,13 +733,21 @@ def main():
         def step():
             model.predict_device(d_t, d_mu, d_var, d_der, M, _lib.GP_DERIV_ROWMAJOR)
 
-    e2e = None
-    if a.workload == "c2" and not a.no_e2e:
+    e2e, ramp_steps = None, 0
+    if a.workload == "c2" and not a.no_e2e and a.full:
         # host numpy in -> host numpy out through the same library (its own leg, outside the timed
         # region and in front of it: the device is then at working clocks when the resident loop
         # starts, as it is in any run longer than a few tens of milliseconds); on every rank at
         # once when there are several, so the line carries host-to-host scaling too
         e2e = e2e_leg(N, D, M, inputs, testing, theta, invQ, invQt, dtype, grp)
+    elif a.workload == "c2" and not a.no_e2e:
+        # without the host-to-host leg, untimed steps for 0.1 s in its place: the timed region
+        # still starts at working clocks, as it does behind that leg
+        t_ramp = time.perf_counter()
+        while time.perf_counter() - t_ramp < 0.1:
+            step()
+            ctx.synchronize()
+            ramp_steps += 1
 
     for _ in range(a.warmup):
         step()
@@ -696,12 +770,25 @@ def main():
     kern_ms = [ctx.elapsed_ms(evs[k], evs[k + 1]) for k in range(a.steps)]
     kern_avg_s = float(np.mean(kern_ms)) * 1e-3
 
-    # parity spot check of what was timed (after the timed region; the oracle enters only here,
-    # as the checker, and in the cpu_baseline leg)
-    tol = 1e-10 if a.precision == "f64" else 1e-4
-    errs, n_checked = sample_parity(ctx, a, kind, outs, inputs, testing, params, M, D, E, dtype)
-    if not max(errs.values()) <= tol and not a.no_parity:
-        raise SystemExit("bench parity check failed: %s" % errs)
+    if a.dump_outputs:
+        # what the last timed step left in the output buffers; (emulator, row) pairs count as rows
+        if kind == "hessian":
+            rows = dump_rows(M, D * D * isz, DUMP_BYTES // world)
+            dump = {"hessian": fetch_rows(ctx, d_h, M, (D, D), dtype, rows)}
+        else:
+            rows = dump_rows(E * M, (2 + D) * isz, DUMP_BYTES // world)
+            dump = {"mu": fetch_rows(ctx, d_mu, E * M, (), dtype, rows),
+                    "var": fetch_rows(ctx, d_var, E * M, (), dtype, rows),
+                    "deriv": fetch_rows(ctx, d_der, E * M, (D,), dtype, rows)}
+        write_outputs(a.dump_outputs, dump, rank, world)
+
+    if a.full:
+        # parity spot check of what was timed (after the timed region; the oracle enters only here,
+        # as the checker, and in the cpu_baseline leg)
+        tol = 1e-10 if a.precision == "f64" else 1e-4
+        errs, n_checked = sample_parity(ctx, a, kind, outs, inputs, testing, params, M, D, E, dtype)
+        if not max(errs.values()) <= tol and not a.no_parity:
+            raise SystemExit("bench parity check failed: %s" % errs)
 
     out = None
     if rank == 0:
@@ -777,8 +864,12 @@ def main():
                        "device": info["name"], "compute_units": info["compute_units"],
                        "cpus_bound_near_gpu": len(near)},
             "roofline": roof,
-            "parity": dict(errs, tol=tol, checked_rows=int(n_checked)),
         }
+        if a.full:
+            out["parity"] = dict(errs, tol=tol, checked_rows=int(n_checked))
+        if ramp_steps:
+            out["warmup_extra"] = ("%d untimed steps (0.1 s of device work) run in front of the --warmup steps: the "
+                                   "timed region starts at working clocks" % ramp_steps)
     if rank == 0:
         if e2e is not None:
             rate, steady, first, pinned_s = e2e

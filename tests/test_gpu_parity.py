@@ -661,12 +661,12 @@ def test_real_emulator_variance_against_extended_precision(gpu_lib):
 
 
 def test_bench_json_contract(gpu_lib):
-    """bench.py prints ONE JSON line with the driver's keys plus roofline and cpu_baseline."""
+    """bench.py --full prints ONE JSON line with the driver's keys plus roofline and cpu_baseline."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full",
                         "--cpu-sample", "20000"], cwd=ROOT, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-1500:]
@@ -695,6 +695,40 @@ def test_bench_json_contract(gpu_lib):
     assert cb["all_cores_value"] > 0 and cb["all_cores_procs"] >= 1
     assert d["value"] > 1e8          # a silent CPU fallback would be ~1e5
     assert max(d["parity"]["e_mu"], d["parity"]["e_var"], d["parity"]["e_deriv"]) <= 1e-10
+
+
+def test_bench_plain_run_and_dump_outputs(gpu_lib, tmp_path):
+    """A plain bench.py run times the steps and prints the headline line without the --full legs; with
+    --dump-outputs it writes the last timed step's mu / var / deriv on a fixed sample of rows, within
+    64 MB, and those rows are the oracle's."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    import bench
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-1500:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["dtype"] == "f64" and d["ms_per_step"] > 0
+    assert d["value"] > 1e8 and d["unit"] == "test-points/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 1e6 / (d["ms_per_step"] * 1e-3)) < 1e-9 * d["value"]
+    for k in ("cpu_baseline", "end_to_end", "parity"):
+        assert k not in d, k
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["deriv.npy", "mu.npy", "var.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 * 10 ** 6
+    mu, var, der = (np.load(str(tmp_path / f)) for f in ("mu.npy", "var.npy", "deriv.npy"))
+    rows = bench.dump_rows(1000000, 13 * 8, bench.DUMP_BYTES)
+    assert mu.dtype == var.dtype == der.dtype == np.float64
+    assert mu.shape == var.shape == (len(rows),) and der.shape == (len(rows), 11)
+    inputs, testing, theta, invQ, invQt = bench.synthetic_inputs(1000, 250, 11, 1000000)
+    pick = np.arange(0, len(rows), 97)
+    ref = gp_oracle.cpu_predict(inputs, theta, invQ, invQt, testing[rows[pick]])
+    assert max(errs(ref, (mu[pick], var[pick], der[pick]))) <= 1e-10
 
 
 def test_predict_bands_emulator_shards_on_gpu(gpu_lib):

@@ -407,3 +407,34 @@ def test_bench_gpus_mismatch_and_no_gpu_exit_nonzero():
                            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240)
         assert r.returncode != 0
         assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_rows_are_a_fixed_sample_and_fetched_exactly():
+    """bench.py --dump-outputs: the rows written are all of them or a fixed seeded sample within the byte budget,
+    and fetch_rows brings back exactly those rows of a row-major device array, whether they are dense in a copy
+    chunk (one block copy) or sparse (row by row)."""
+    import ctypes
+    import bench
+
+    class FakeCtx:             # to_host_at over a host buffer standing in for device memory
+        def __init__(self, buf):
+            self.buf, self.calls = buf, 0
+
+        def to_host_at(self, dptr, offset_bytes, shape, dtype):
+            self.calls += 1
+            n = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+            assert 0 <= offset_bytes and offset_bytes + n <= self.buf.nbytes      # never past the buffer
+            return self.buf.reshape(-1).view(np.uint8)[offset_bytes:offset_bytes + n].view(dtype).reshape(shape).copy()
+
+    assert np.array_equal(bench.dump_rows(1000, 104, 10 ** 6), np.arange(1000))
+    rows = bench.dump_rows(1000000, 104, bench.DUMP_BYTES)
+    assert len(rows) == bench.DUMP_BYTES // 104 and np.all(np.diff(rows) > 0) and rows[-1] < 1000000
+    assert np.array_equal(rows, bench.dump_rows(1000000, 104, bench.DUMP_BYTES))          # same rows every run
+    a = np.random.RandomState(3).random_sample((5000, 11))
+    for idx, chunk in ((bench.dump_rows(5000, 88, 300000), 8800), (np.array([3, 2000, 4999]), 1 << 20)):
+        ctx = FakeCtx(a)
+        got = bench.fetch_rows(ctx, ctypes.c_void_p(0), 5000, (11,), np.float64, idx, chunk_bytes=chunk)
+        assert np.array_equal(got, a[idx])
+    assert ctx.calls == 3                                    # sparse: one copy per row
+    flat = bench.fetch_rows(FakeCtx(a.ravel()), ctypes.c_void_p(0), 55000, (), np.float64, np.array([0, 7, 54999]))
+    assert np.array_equal(flat, a.ravel()[[0, 7, 54999]])

@@ -7,7 +7,7 @@ tail -2 $OUT/pytest_hess.txt
 for r in 0 1 2; do
   for prec in f64 f32; do
     for v in 0 1; do
-      GP_HESS_STATIC=$v python3 bench.py --workload c5 --precision $prec --steps 20 --warmup 3 --no-cpu-baseline --no-e2e > $OUT/b.json
+      GP_HESS_STATIC=$v python3 bench.py --workload c5 --precision $prec --steps 20 --warmup 3 --full --no-cpu-baseline --no-e2e > $OUT/b.json
       python3 -c "import json;d=json.load(open('$OUT/b.json'));print('round $r $prec static=$v kernel_ms %.4f e_hess %.2e' % (d['roofline']['kernel_ms'], d['parity']['e_hess']))" | tee -a $OUT/ab.txt
     done
   done

@@ -7,7 +7,7 @@ mkdir -p $OUT; rm -f $OUT/ab.txt
 for r in 0 1 2; do
   for prec in $PRECS; do
     for v in $VALS; do
-      env $VAR=$v python3 bench.py --workload c5 --precision $prec --steps 20 --warmup 3 --no-cpu-baseline --no-e2e > $OUT/b.json
+      env $VAR=$v python3 bench.py --workload c5 --precision $prec --steps 20 --warmup 3 --full --no-cpu-baseline --no-e2e > $OUT/b.json
       python3 -c "import json;d=json.load(open('$OUT/b.json'));print('round $r $prec $VAR=$v kernel_ms %.4f e_hess %.2e' % (d['roofline']['kernel_ms'], d['parity']['e_hess']))" | tee -a $OUT/ab.txt
     done
   done
