@@ -25,7 +25,6 @@
 #include "gp_dispatch.hpp"
 #include "gp_generic_kernel.hpp"
 #include "gp_hessian_kernel.hpp"
-#include "gp_hessian_mfma_kernel.hpp"
 #include "gp_hessian_win_kernel.hpp"
 #include "gp_host_pool.hpp"
 #include "gp_predict_kernel.hpp"
@@ -104,7 +103,7 @@ struct gp_model {
   // the scale sqrt(e_d) and centre c_d the kernel applies to test rows, as doubles (emulator 0):
   // the host applies them itself, in double, when it stages float64 rows for a float32 model
   std::vector<double> scale_host, centre_host;
-  // Hessian on the matrix core (gp_hessian_mfma_kernel.hpp): the constant products
+  // Hessian on the matrix core (gp_hessian_win_kernel.hpp): the constant products
   // x''_id x''_id2 in fragment order, built on the first Hessian call from a host copy of the
   // scaled rows (double, [16 * kernel_nb slots][kernel_d])
   std::vector<double> xs_host;
@@ -650,14 +649,6 @@ hipError_t launch_hessm<double>(int knb, int kd, const gpk::HessMfmaArgs<double>
   return hipErrorInvalidValue;
 }
 
-// The matrix-core Hessian runs the windowed kernel (gp_hessian_win_kernel.hpp) or, with GP_HESS_WIN=0,
-// the block-major hessian_mfma_kernel (A/B reference).  Read once: a model's packed products follow
-// the kernel that will read them.
-static bool hess_use_win() {
-  static const bool v = [] { const char* ev = getenv("GP_HESS_WIN"); return !ev || atoi(ev) != 0; }();
-  return v;
-}
-
 static bool hessian_on_matrix_core(const gp_model* m) {
   if (m->kernel_nb <= 0 || m->n_emulators != 1 || m->xs_host.empty()) return false;
   if (const char* ev = getenv("GP_HESS_VALU"))      // A/B switch: force the VALU kernel
@@ -665,36 +656,31 @@ static bool hessian_on_matrix_core(const gp_model* m) {
   return m->kernel_d == 8 || m->kernel_d == 10 || m->kernel_d == 11 || m->kernel_d == 12 || m->kernel_d == 16;
 }
 
-// The constant operand of hessian_mfma_kernel, built once per model: P[i][(d, d2)] =
+// The constant operand of hessian_win_kernel, built once per model: P[i][(d, d2)] =
 // x''_id x''_id2 (double product of the rounded coordinates, rounded once to T) in 4 x 4 blocks
 // of (d, d2); fragment (block c, training block I, k-step s) lane l = the product for training
 // point 16 I + own(s, l >> 4) and the block's element that MFMA output row (l & 15) stands for.
+// Fragments are packed k-step-major (hess_win_frag_index), padded to whole chunks of WGeo::kChunk.
 template <typename T>
 static int ensure_hess_frags(gp_ctx* ctx, gp_model* m) {
   std::lock_guard<std::mutex> lock(m->h_mutex);
   if (m->d_pfrags) return GP_OK;
   const int kd = m->kernel_d, knb = m->kernel_nb, N = m->n_train;
-  // geometry of hessian_mfma_kernel<T, kd, knb> (gpk::HGeo): wide instances take their
-  // fragments in paired order and in chunks of one pair block
-  const bool win = gpk::hess_win<T>(kd, knb) && hess_use_win();   // windowed kernel: k-step-major fragments, 32 per chunk
-  const bool wide = !win && gpk::hess_wide<T>(kd, knb);
-  const int chunk = win ? gpk::WGeo::kChunk : wide ? 4 * knb : gpk::Geo<T>::kChunk;
   const int nblk = gpk::hess_blocks(kd);
-  const size_t n = (size_t)gpk::hess_frag_count_padded(kd, knb, chunk) * 64;
+  const size_t n = (size_t)gpk::hess_frag_count_padded(kd, knb, gpk::WGeo::kChunk) * 64;
   std::vector<T> fr(n, T(0));
   for (int c = 0; c < nblk; ++c)
     for (int I = 0; I < knb; ++I)
       for (int s = 0; s < 4; ++s) {
-        T* f = fr.data() + (size_t)(win ? gpk::hess_win_frag_index(c, I, s, nblk)
-                                        : gpk::hess_frag_index(c, I, s, knb, wide, nblk)) * 64;
+        T* f = fr.data() + (size_t)gpk::hess_win_frag_index(c, I, s, nblk) * 64;
         for (int l = 0; l < 64; ++l) {
           const int i = gpk::own_index<T>(I, s, l >> 4);   // slot; padding slots hold zero rows
           const int q = l & 15;             // MFMA output row = accumulator r of lane group g
           const int d = 4 * gpk::hess_block_bi(c) + gpk::hess_row_r<T>(q);
           const int d2 = 4 * gpk::hess_block_bj(c) + gpk::hess_row_g<T>(q);
           if (gpk::slot_point<T>(i) >= N) continue;
-          if (win && gpk::hess_block_bi(c) == gpk::hess_block_bj(c)) {
-            // the windowed kernel takes G_n = sum w x''_n and s = sum w from the unused mirror slots of the
+          if (gpk::hess_block_bi(c) == gpk::hess_block_bj(c)) {
+            // the kernel takes G_n = sum w x''_n and s = sum w from the unused mirror slots of the
             // diagonal blocks (gp_hessian_win_kernel.hpp, hess_gslot_*)
             const int n = gpk::hess_gslot_of(gpk::hess_block_bi(c), gpk::hess_row_r<T>(q), gpk::hess_row_g<T>(q));
             if (n >= 0) {
@@ -734,23 +720,18 @@ static int hessian_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
     h.hess = (T*)d_hess;
     h.M = M;
     h.d_actual = m->n_inputs;
-    h.use_win = gpk::hess_win<T>(m->kernel_d, m->kernel_nb) && hess_use_win() ? 1 : 0;
-    const bool wide = !h.use_win && gpk::hess_wide<T>(m->kernel_d, m->kernel_nb);
     h.dbg = (unsigned long long*)ctx->dbg;
     h.n_ksteps = (m->n_train + 3) / 4;
-    // items drawn from a counter (see the kernel); GP_HESS_STATIC=1: dealt round-robin as in round 2 (A/B)
-    static const bool static_items = [] { const char* ev = getenv("GP_HESS_STATIC"); return ev && atoi(ev) != 0; }();
+    // items drawn from a counter (see the kernel)
     h.tickets = h.tickets2 = nullptr;
-    if (h.use_win && !static_items && M < ((int64_t)1 << 36)) {      // (two launches per call at most: whole groups, rest)
+    if (M < ((int64_t)1 << 36)) {      // (two launches per call at most: whole groups, rest)
       const unsigned slot = ctx->ticket_next.fetch_add(2);
       h.tickets = ctx->tickets + 4 * (slot % kTicketSlots);            // (4 words per launch: see the kernel)
       h.tickets2 = ctx->tickets + 4 * ((slot + 1) % kTicketSlots);
     }
-    const int kRowsPerWG = (wide || h.use_win) ? 4 * gpk::kTile : gpk::Geo<T>::kRowsPerWG;   // 4-wave workgroups
-    const int64_t groups = (M + kRowsPerWG - 1) / kRowsPerWG;
-    int64_t grid = (int64_t)ctx->compute_units * (h.use_win ? gpk::win_wg_per_cu<T>() : gpk::Geo<T>::kWGPerCU);
-    if (grid > groups && !h.use_win) grid = groups;      // (the windowed kernel's launcher sizes its own launches)
-    hipError_t e = launch_hessm<T>(m->kernel_nb, m->kernel_d, h, (int)grid, stream);
+    // (the launcher sizes each launch: min(grid, its 64-row groups))
+    const int grid = ctx->compute_units * gpk::win_wg_per_cu<T>();
+    hipError_t e = launch_hessm<T>(m->kernel_nb, m->kernel_d, h, grid, stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "hessian kernel launch: %s", hipGetErrorString(e));
     return GP_OK;
   }

@@ -8,7 +8,7 @@
 //
 // i.e. a symmetric rank-N update per test row, done here on the VALU with D(D+1)/2 fmas per
 // (training point, test row).  This is the kernel for n_inputs <= 5; from kernel D = 8 up the
-// same quantity is computed on the matrix core by gp_hessian_mfma_kernel.hpp (the pair products
+// same quantity is computed on the matrix core by gp_hessian_win_kernel.hpp (the pair products
 // x''_id x''_id2 do not depend on the test row, which turns the sum into a matrix product), which
 // is 1.2-1.5x faster at D = 8, 12 and 16 (even at D = 10, 11 in fp64, where 4 x 4 blocks pad 55 / 66
 // products to 96).  GP_HESS_VALU=1 in the environment forces this kernel for every D.

@@ -1,34 +1,37 @@
-// Hessian on the matrix core, WINDOWED form (the default for every matrix-core instance).
+// Hessian of the GP mean on the matrix core: hessian_win_kernel<T, D, NB> (kernel D >= 8; smaller D and
+// batched emulators run the VALU kernel of gp_hessian_kernel.hpp).
 //
-// hessian_mfma_kernel walks the products block by block: one accumulator at a time runs over ALL
-// training points, so the whole weight tile of a wave's 16 rows must sit in registers through the
-// matrix phase -- 8 NB registers in fp64 (152 at N = 300), which with t'', G and a training row does
-// not fit the 256 registers of a wave at two waves per SIMD.  The wide geometry of that kernel buys
-// the registers with occupancy (one wave per SIMD, 512 registers) and pays for it: a lone wave
-// reaches 85 % of the matrix pipe and 76 % of the fp64 vector rate and has nothing to cover its own
-// LDS and barrier waits with.
+// The reference (gp_emulator/GaussianProcess.py:345-366) forms, for every test row t,
+//   hess[d][d2] = sum_i w_i (e_d (x_id - t_d) e_d2 (x_id2 - t_d2) - [d == d2] e_d),   w_i = k_i alpha_i.
+// In the kernel's scaled, centred coordinates x'' = sqrt(e)(x - c) the sum expands to
+//   sum_i w_i (x''_id - t''_d)(x''_id2 - t''_d2) = S2[d][d2] - G_d t''_d2 - t''_d G_d2 + s t''_d t''_d2,
+//   S2[d][d2] = sum_i w_i x''_id x''_id2,   G_d = sum_i w_i x''_id,   s = sum_i w_i,
+// and the products P[i][(d, d2)] = x''_id x''_id2 do NOT depend on the test row: S2 = W P is a
+// matrix product of the (test rows x N) weight tile with a constant N x D(D+1)/2 matrix, packed once
+// per model by the host.  The pairs are taken in 4 x 4 blocks of the matrix (160 products instead of
+// 136 at D = 16, 96 instead of 66 at D = 11).
 //
-// Here the ORDER is turned round instead.  The training points are taken in windows of KW k-steps
-// (4 KW points per lane group); for each window
-//   phase A   the weights of the window only (2 KW registers), two training points in flight;
+// The training points are taken in windows of KW k-steps (4 KW points per lane group); for each window
+//   phase A   the weights w_i of the window only (KW registers);
 //   phase B   for every k-step of the window, one matrix instruction into EACH of the NBLK block
 //             accumulators (fragments packed k-step-major: (k-step, block)) -- NBLK independent
 //             chains, no dependent issue at all.
-// All NBLK accumulators stay live (8 NBLK registers: 80 at D = 16), but the weight tile never
-// exists as a whole: 80 + 2 KW + t'' + two training rows fit 256 registers, so the kernel runs two
-// waves per SIMD without spills.  s and G_d are not accumulated in phase A at all: they come out of
-// spare accumulator slots of the diagonal blocks (hess_gslot_*).  The blocks are finished and stored
-// after the last window.  Workgroups are four waves (one per SIMD), two per CU (WGeo): the two waves
-// of a SIMD belong to different workgroups and drift apart, so one's latency-bound parts (item start,
-// finish, stores) run under the other's pipe work.  Measured (profiles/r02_hessian_wide.txt,
-// r02_hessian_kernels.txt): config 5 (N = 300, D = 16) 2.25-2.31 ms in fp64 against 2.67-2.9 ms for the
-// wide geometry, 1.30 against 1.52-1.76 ms in fp32, and faster or equal at every other compiled shape.
+// All NBLK accumulators stay live (8 NBLK registers: 80 at D = 16), but the weight tile (8 NB registers
+// in fp64: 152 at N = 300) never exists as a whole: 80 + 2 KW + t'' + two training rows fit 256
+// registers, so the kernel runs two waves per SIMD without spills.  s and G_d are not accumulated in
+// phase A at all: they come out of spare accumulator slots of the diagonal blocks (hess_gslot_*).  The
+// blocks are finished and stored after the last window.  Workgroups are four waves (one per SIMD), two
+// per CU (WGeo): the two waves of a SIMD belong to different workgroups and drift apart, so one's
+// latency-bound parts (item start, finish, stores) run under the other's pipe work.  An earlier
+// block-major kernel, which kept the whole weight tile in registers, lost to this form at every
+// compiled shape; DESIGN.md section 4.2 keeps its history and measurements.
+//
+// Accuracy: the expansion cancels like predict_kernel's exp(h_i + g + x''.t'') does -- by about
+// (|x''| + |t''|)^2 / |x'' - t''|^2, small because the coordinates are centred on the training
+// mean; fp64 stays at 1e-15 on the benchmark sets (tests).
 #pragma once
-#include "gp_hessian_mfma_kernel.hpp"
+#include "gp_predict_kernel.hpp"
 
-#ifndef GP_HESS_WINDOWS
-#define GP_HESS_WINDOWS 4
-#endif
 #ifndef GP_HESS_WIN_GROUP
 #define GP_HESS_WIN_GROUP 2
 #endif
@@ -37,32 +40,118 @@
 #ifndef GP_HESS_ABL
 #define GP_HESS_ABL 0
 #endif
-// GP_HESS_PIPE = 1: phase A of window q + 1 is issued UNDER the matrix instructions of window q -- one training
-// point (k-step) of the next window per k-step of the current one, in the same instruction stream: the fp64
-// matrix instructions (ten independent chains, always ready) fill every dependent-issue bubble of the
-// vector chain, so a wave keeps the pipe busy by itself instead of relying on its SIMD partner being in a
-// complementary phase.  Windows are GP_HESS_PIPE_KW k-steps; two window's weights are live (2 x KW registers
-// pairs), one training point in flight.  0: the round-2 order (a window's weights, then its matrix phase).
-#ifndef GP_HESS_PIPE
-#define GP_HESS_PIPE 1
-#endif
+// Phase A of window q + 1 is issued UNDER the matrix instructions of window q -- one training point (k-step)
+// of the next window per k-step of the current one, in the same instruction stream: the fp64 matrix
+// instructions (ten independent chains, always ready) fill every dependent-issue bubble of the vector chain,
+// so a wave keeps the pipe busy by itself instead of relying on its SIMD partner being in a complementary
+// phase.  Windows are GP_HESS_PIPE_KW k-steps; two windows' weights are live, one training point in flight.
 #ifndef GP_HESS_PIPE_KW
 #define GP_HESS_PIPE_KW 10
 #endif
-#ifndef GP_HESS_ROW_EARLY
-#define GP_HESS_ROW_EARLY 0     // 1: next item's row loaded where the last window begins (A/B: 91 registers spilled)
-#endif
-#ifndef GP_HESS_ROW_MID
-#define GP_HESS_ROW_MID 1       // 1: ... in front of row block GP_HESS_ROW_PASS of the finish; 0: behind the finish
-#endif
+// the next item's test row is loaded in front of row block GP_HESS_ROW_PASS of the whole-line finish
 #ifndef GP_HESS_ROW_PASS
 #define GP_HESS_ROW_PASS (NB4 > 1 ? NB4 - 2 : 0)     // (one block earlier: 9 registers spilled at D = 16)
 #endif
-#ifndef GP_HESS_LDS_OUT
-#define GP_HESS_LDS_OUT 1      // 0: the round-2 finish (16-byte stores straight from the accumulators), A/B reference
-#endif
 
 namespace gpk {
+
+// The D x D matrix is cut into 4 x 4 blocks (bi, bj); the blocks with bi <= bj are the 16-wide
+// column blocks of P.  Within a block, accumulator register r of lane group g (MFMA output row
+// own_sub(r, g)) is element (d, d2) = (4 bi + r, 4 bj + g): the first index is known at compile
+// time wherever the accumulator is used, the second is the lane group's own -- so the epilogue
+// needs no lookup tables (t''_d2, G_d2, sqrt(e_d2) are three small per-lane arrays indexed by bj).
+// Diagonal blocks carry both (d, d2) and (d2, d); D is padded to a multiple of 4 (zero products).
+__host__ __device__ constexpr int hess_nb4(int D) { return (D + 3) / 4; }
+__host__ __device__ constexpr int hess_blocks(int D) { return hess_nb4(D) * (hess_nb4(D) + 1) / 2; }
+__host__ __device__ constexpr int hess_block_index(int bi, int bj) { return bj * (bj + 1) / 2 + bi; }
+__host__ __device__ constexpr int hess_block_bj(int c) {
+  int bj = 0;
+  while ((bj + 1) * (bj + 2) / 2 <= c) ++bj;
+  return bj;
+}
+__host__ __device__ constexpr int hess_block_bi(int c) { return c - hess_block_bj(c) * (hess_block_bj(c) + 1) / 2; }
+__host__ __device__ constexpr int hess_frag_count(int D, int NB) { return hess_blocks(D) * NB * 4; }
+__host__ __device__ constexpr int hess_frag_count_padded(int D, int NB, int chunk) {
+  return (hess_frag_count(D, NB) + chunk - 1) / chunk * chunk;
+}
+// (r, g) with own_sub(r, g) == q: which accumulator register / lane group MFMA output row q is
+template <typename T> __host__ __device__ constexpr int hess_row_r(int q) {
+  for (int r = 0; r < 4; ++r)
+    for (int g = 0; g < 4; ++g)
+      if (Real<T>::own_sub(r, g) == q) return r;
+  return 0;
+}
+template <typename T> __host__ __device__ constexpr int hess_row_g(int q) {
+  for (int r = 0; r < 4; ++r)
+    for (int g = 0; g < 4; ++g)
+      if (Real<T>::own_sub(r, g) == q) return g;
+  return 0;
+}
+
+// 4 x 4 transpose between accumulator register r and lane group g: v[r] of group g <-> v[g] of
+// group r.  v_permlane32_swap exchanges the upper half of one register with the lower half of
+// another (a 2 x 2 transpose on (r bit 1, g bit 1)), v_permlane16_swap the odd 16-lane rows of one
+// with the even rows of the other ((r bit 0, g bit 0)).
+__device__ __forceinline__ void swap_halves2(unsigned& a, unsigned& b, bool rows16) {
+  if (rows16) {
+    auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = r[0];
+    b = r[1];
+  } else {
+    auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    a = r[0];
+    b = r[1];
+  }
+}
+__device__ __forceinline__ void swap_pair(float& a, float& b, bool rows16) {
+  unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
+  swap_halves2(ua, ub, rows16);
+  a = __uint_as_float(ua);
+  b = __uint_as_float(ub);
+}
+__device__ __forceinline__ void swap_pair(double& a, double& b, bool rows16) {
+  unsigned long long xa = (unsigned long long)__double_as_longlong(a), xb = (unsigned long long)__double_as_longlong(b);
+  unsigned alo = (unsigned)xa, ahi = (unsigned)(xa >> 32), blo = (unsigned)xb, bhi = (unsigned)(xb >> 32);
+  swap_halves2(alo, blo, rows16);
+  swap_halves2(ahi, bhi, rows16);
+  a = __longlong_as_double((long long)(((unsigned long long)ahi << 32) | alo));
+  b = __longlong_as_double((long long)(((unsigned long long)bhi << 32) | blo));
+}
+template <typename T>
+__device__ __forceinline__ void transpose_groups4(T (&v)[4]) {
+  swap_pair(v[0], v[2], false);
+  swap_pair(v[1], v[3], false);
+  swap_pair(v[0], v[1], true);
+  swap_pair(v[2], v[3], true);
+}
+// four consecutive elements of one output row as 16-byte stores; `left` = elements of the row
+// still inside the matrix from this position on (a multiple of the vector width, possibly <= 0)
+template <typename T>
+__device__ __forceinline__ void store_row4(T* dst, const T (&v)[4], int left) {
+  if constexpr (sizeof(T) == 8) {
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    if (left > 0) *reinterpret_cast<d2_t*>(dst) = d2_t{v[0], v[1]};
+    if (left > 2) *reinterpret_cast<d2_t*>(dst + 2) = d2_t{v[2], v[3]};
+  } else {
+    typedef float f4_t __attribute__((ext_vector_type(4)));
+    if (left > 0) *reinterpret_cast<f4_t*>(dst) = f4_t{v[0], v[1], v[2], v[3]};
+  }
+}
+
+template <typename T>
+struct HessMfmaArgs {
+  const T* xa;        // [16*NB][row_stride(D)] training rows [x'', alpha, h]
+  const T* pfrags;    // [hess_frag_count_padded][64] products x''_id x''_id2, 4 x 4 blocks, hess_win_frag_index order
+  const T* sd;        // [2*D + 1] sqrt(e_d), the centre c_d, b = e[D]
+  const T* testing;   // [M][d_actual]
+  T* hess;            // [M][d_actual][d_actual]
+  long long M;
+  int d_actual;
+  unsigned long long* dbg;   // GP_STAMPS builds only: [8] segment cycle sums; else unused
+  int n_ksteps;              // ceil(n_train / 4): k-steps that hold training points
+  unsigned* tickets2;        // host side only: the counter of the call's second launch (rows beyond the last whole 64-row group)
+  unsigned* tickets;         // the launch's item counter (0 on entry and on exit), or null: items dealt round-robin
+};
 
 // G and s ride on the matrix core.  A diagonal 4 x 4 block computes every off-diagonal pair twice --
 // accumulator register r of lane group g is (4 bi + r, 4 bi + g), and only r <= g is used -- so its six
@@ -101,11 +190,6 @@ struct WGeo {
 #define GP_HESS_WG_F32 2
 #endif
 template <typename T> __host__ __device__ constexpr int win_wg_per_cu() { return sizeof(T) == 4 ? GP_HESS_WG_F32 : 2; }
-// Instances that run the windowed kernel: all of them.  It started as the cure for the large fp64
-// instances (hess_wide), but with s and G on the matrix core and the decoupled workgroups it beats the
-// block-major kernel at every compiled shape in both precisions (profiles/r02_hessian_kernels.txt;
-// N = 120, D = 8: 0.49 vs 0.59 ms fp64).  hessian_mfma_kernel stays as the A/B reference (GP_HESS_WIN=0).
-template <typename T> __host__ __device__ constexpr bool hess_win(int, int) { return true; }
 
 // LDS row stride of a training point [x'', alpha, h]: D + 2 reals rounded up to 16 bytes
 template <typename T> __host__ __device__ constexpr int win_row_stride(int D) {
@@ -116,9 +200,9 @@ template <typename T> __host__ __device__ constexpr int win_row_stride(int D) {
 // instance when the caller's rows are exactly D long (d_actual == D) and 16-byte pieces (win_lds_out) and the
 // matrix is 16-byte aligned, and runs it on the whole 64-row groups of the call (M a multiple of 64: no row
 // guards anywhere in it); the rows beyond the last whole group, and every other call, go to the instance with
-// the direct stores of round 2.
+// direct 16-byte (or element) stores from the accumulators.
 template <typename T> __host__ __device__ constexpr bool win_lds_out(int D) {
-  return GP_HESS_LDS_OUT && D % (16 / (int)sizeof(T)) == 0;
+  return D % (16 / (int)sizeof(T)) == 0;
 }
 // KL: live k-steps of the last 16-block (1..4).  The kernel is compiled per block count NB; a training set that
 // leaves the last k-step(s) of its last block empty (N = 300: 75 of 76, N = 250: 63 of 64) runs the instance that
@@ -139,14 +223,9 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
   constexpr int NB4 = hess_nb4(D);
   constexpr int NBLK = hess_blocks(D);
   constexpr int NKS = 4 * (NB - 1) + KL;                        // k-steps
-  constexpr bool kPipe = GP_HESS_PIPE != 0;
-  constexpr int NW = kPipe ? (NKS + GP_HESS_PIPE_KW - 1) / GP_HESS_PIPE_KW : (GP_HESS_WINDOWS < NKS ? GP_HESS_WINDOWS : NKS);
+  constexpr int NW = (NKS + GP_HESS_PIPE_KW - 1) / GP_HESS_PIPE_KW;
   constexpr int KW = (NKS + NW - 1) / NW;                       // k-steps per window (the last may be short)
   constexpr int NF = NKS * NBLK;
-  // kPipe, LDSOUT: the k-step at which the next item's test row is loaded: the first of the last window, but behind
-  // the chunk barrier that publishes the next item's number (chunk 1)
-  constexpr int kRowLoadKs0 = (NKS - 1) / KW * KW;
-  constexpr int kRowLoadKs = kRowLoadKs0 * NBLK > 2 * WGeo::kChunk ? kRowLoadKs0 : (NKS - 1);
   constexpr int kChunk = WGeo::kChunk;
   constexpr int NCH = (NF + kChunk - 1) / kChunk;
   // The finish assembles the wave's output in LDS and writes it as whole lines (below) when the rows of the
@@ -180,9 +259,8 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
   const unsigned long long wave_t0 = seg_t0;
   const unsigned long long real_t0 = __builtin_amdgcn_s_memrealtime();      // 100 MHz, one counter for the chip
 #endif
-  // the lane's raw test row, loaded one item ahead: at the end of the last window's phase A, when the
-  // registers of the training row are free again, so that the HBM latency of these loads is not the
-  // first thing an item waits for
+  // the lane's raw test row, loaded one item ahead (LDSOUT: in the finish, in front of row block
+  // GP_HESS_ROW_PASS), so that the HBM latency of these loads is not the first thing an item waits for
   T rraw[D];
   auto load_row = [&](long long grp_) __attribute__((always_inline)) {
     const long long m_ = grp_ * kRowsPerWG + wave * kTile + ml;
@@ -257,15 +335,14 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
       gm = fma(t[d], t[d], gm);
     }
     gm *= T(-0.5);
-    T kvw[kPipe ? 2 : 1][KW];   // the weights of the current window (kPipe: and of the next one)
+    T kvw[2][KW];               // the weights of the current window and of the next one
     acc_t accs[NBLK];
 #pragma unroll
     for (int c = 0; c < NBLK; ++c) accs[c] = acc_t{T(0), T(0), T(0), T(0)};
 
-    // phase A of window q: its KW k-steps, one training point at a time (two waves per SIMD cover
-    // the latencies; there is no register for a second point in flight)
-    auto window_weights = [&](auto qc) __attribute__((always_inline)) {
-      constexpr int q = decltype(qc)::value;
+    // phase A of the first window: its KW k-steps, GP training points at a time (the later windows' weights
+    // are formed a point at a time under the matrix instructions: point_weight)
+    auto first_window_weights = [&]() __attribute__((always_inline)) {
       constexpr int GP = GP_HESS_WIN_GROUP;        // training points in flight (their serial chains interleave)
       static_for<(KW + GP - 1) / GP>([&](auto jc) __attribute__((always_inline)) {
         constexpr int j0 = decltype(jc)::value * GP;
@@ -273,7 +350,7 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
         T al[GP], k[GP];
 #pragma unroll
         for (int u = 0; u < GP; ++u) {
-          const int ks = q * KW + j0 + u < NKS ? q * KW + j0 + u : NKS - 1;     // (a short tail repeats the last k-step)
+          const int ks = j0 + u < NKS ? j0 + u : NKS - 1;     // (a short tail repeats the last k-step)
           const int i = own_index<T>(ks >> 2, ks & 3, g);
           const T* row = &s_xa[i * DS];
 #pragma unroll
@@ -307,12 +384,12 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
         for (int u = 0; u < GP; ++u) {
           if constexpr (!R::kExpand) k[u] *= b;
           // (s and G come out of the matrix phase: hess_gslot_*)
-          if (j0 + u < KW && q * KW + j0 + u < NKS) kvw[kPipe ? q & 1 : 0][j0 + u] = k[u] * al[u];
+          if (j0 + u < KW) kvw[0][j0 + u] = k[u] * al[u];
         }
       });
     };
 
-    // kPipe: the weight of ONE k-step (the lane's training point of it), into the buffer of its window
+    // the weight of ONE k-step (the lane's training point of it), into the buffer of its window
     auto point_weight = [&](auto ksc) __attribute__((always_inline)) {
       constexpr int ks = decltype(ksc)::value;
       const int i = own_index<T>(ks >> 2, ks & 3, g);
@@ -343,36 +420,15 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
     constexpr int kAhead = GP_AHEAD;
     T afr[kAhead];
     GP_STAMP(0);
-    window_weights(std::integral_constant<int, 0>{});
+    first_window_weights();
     GP_STAMP(1);
     static_for<NF>([&](auto fc) {
       constexpr int f = decltype(fc)::value;
       constexpr int ch = f / kChunk, fl = f % kChunk;
       constexpr int ks = f / NBLK, c = f % NBLK;
       constexpr int q = ks / KW;
-      if constexpr (kPipe) {
-        // the next window's k-step in the same position, under this k-step's matrix instructions
-        if constexpr (c == 0 && ks + KW < NKS) point_weight(std::integral_constant<int, ks + KW>{});
-        // the next item's test row: loaded where the last window begins -- no weights are formed any more, so
-        // the registers are there, and the window's matrix instructions cover most of the HBM latency
-        if constexpr (GP_HESS_ROW_EARLY && kLdsOut && c == 0 && ks == kRowLoadKs) {
-          __builtin_amdgcn_sched_barrier(0);
-          const long long nx = next_grp();
-          load_row(nx < n_groups ? nx : grp);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      if constexpr (!kPipe && c == 0 && ks % KW == 0 && q > 0) {
-        GP_STAMP(2);
-        window_weights(std::integral_constant<int, q>{});
-        // (kLdsOut: the row is loaded in the finish, once t and G are dead -- carried through the finish it
-        // went to scratch behind a full wait)
-        if constexpr (q == (NKS - 1) / KW && !kLdsOut) {
-          const long long nx = next_grp();
-          load_row(nx < n_groups ? nx : grp);
-        }
-        GP_STAMP(1);
-      }
+      // the next window's k-step in the same position, under this k-step's matrix instructions
+      if constexpr (c == 0 && ks + KW < NKS) point_weight(std::integral_constant<int, ks + KW>{});
       if constexpr (fl == 0) {
         GP_STAMP(2);
         dma_wait();       // this wave's pieces of chunk ch have landed
@@ -392,7 +448,7 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
       }
       if constexpr (fl + kAhead - 1 < kChunk && f + kAhead - 1 < NF)
         afr[(fl + kAhead - 1) % kAhead] = s_fr[ch & 1][(fl + kAhead - 1) * 64 + lane];
-      accs[c] = R::mfma(afr[fl % kAhead], kvw[kPipe ? q & 1 : 0][ks - q * KW], accs[c]);
+      accs[c] = R::mfma(afr[fl % kAhead], kvw[q & 1][ks - q * KW], accs[c]);
     });
 #if GP_HESS_ABL & 4
     {
@@ -497,7 +553,7 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
       T* out0 = p.hess + m0 * (long long)(D * D);
       static_for<NB4>([&](auto ppc) __attribute__((always_inline)) {
         constexpr int pp = decltype(ppc)::value;
-        if constexpr (GP_HESS_ROW_MID && pp == GP_HESS_ROW_PASS) {
+        if constexpr (pp == GP_HESS_ROW_PASS) {
           // the next item's test row: most accumulators are dead by now, and the remaining row blocks' LDS round
           // trips and stores cover a part of the HBM latency (loaded earlier it lived in scratch: 91 registers)
           __builtin_amdgcn_sched_barrier(0);
@@ -562,11 +618,6 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
       });
-      if constexpr ((!kPipe || !GP_HESS_ROW_EARLY) && !GP_HESS_ROW_MID) {
-        __builtin_amdgcn_sched_barrier(0);
-        const long long nx = next_grp();
-        load_row(nx < n_groups ? nx : grp);     // next item's test row
-      }
     } else {
     const long long m = grp * kRowsPerWG + wave * kTile + ml;
     const bool row_ok = m < p.M;
@@ -585,8 +636,11 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
       if (vec_ok)
 #endif
       {
-        // 16-byte stores: the mirror image as it is, the block's own rows after a 4 x 4 transpose
-        // across the lane groups (see hessian_mfma_kernel)
+        // 16-byte stores.  The lane's four values are H[4 bi + r][d2], r = 0..3: as the MIRROR image they
+        // are four consecutive elements of row d2.  Transposed across the four lane groups (two permlane
+        // swaps per register pair) they become four consecutive elements of row 4 bi + g of the block
+        // itself.  On a diagonal block only the transposed copy is needed, and each lane keeps the
+        // upper-triangle version of every element, so the stored matrix is exactly symmetric.
         T vt[4] = {v[0], v[1], v[2], v[3]};
         transpose_groups4(vt);
         if constexpr (bi != bj) {
