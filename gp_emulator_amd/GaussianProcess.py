@@ -228,7 +228,7 @@ class GaussianProcess:
         assert np.all(ind_end - ind_start <= block_size)
         return ind_start, ind_end
 
-    def gpu_predict(self, testing, precision, threshold, out=None):
+    def gpu_predict(self, testing, precision, threshold, out=None, do_unc=True):
         """Predict on the GPU in row blocks of at most ``threshold`` rows (reference
         :273-323): constants flattened and cast to ``precision`` once (:289-292), each
         block's rows flattened and cast (:300-311), ``predict_wrap`` called with the twelve
@@ -238,12 +238,27 @@ class GaussianProcess:
 
         ``threshold`` only bounds the block size; the kernel itself has no 2e5-row limit
         (the reference's came from kernel_matrixExp.cu:29).
+
+        ``do_unc=False`` (not in the reference's GPU path, which always computes the variance):
+        float64 ``(mu, deriv)``, the shape of ``cpu_predict(do_unc=False)`` (reference :211-251),
+        from the mean+gradient kernels -- bit for bit the ``mu`` and ``deriv`` of ``do_unc=True``.
+        It always runs on the resident model (the twelve-argument boundary has no variance-free
+        form), works without ``invQ``, and ``out`` is then ``(mu, deriv)``.
         """
         precision = np.dtype(precision)
         if precision not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise TypeError("precision must be float32 or float64, got %r" % (precision,))
         n_predict, n_inputs = testing.shape
         assert n_inputs == self.D
+        if not do_unc:
+            testing = np.asarray(testing)
+            if testing.dtype != np.float64:
+                testing = testing.astype(precision)
+            result, deriv = self.gpu_model(precision).predict_mean_grad(
+                testing, max_block_rows=int(threshold), out=out)
+            if result.dtype != np.float64:
+                result, deriv = result.astype(np.float64), deriv.astype(np.float64)
+            return result, deriv
         if self.row_major_boundary:
             # One library call: the constants are packed and uploaded once per emulator
             # (gpu_model), the rows flow through the library's slab pipeline with at most
@@ -293,8 +308,10 @@ class GaussianProcess:
 
     def predict(self, testing, do_unc=True, is_gpu=False, precision=np.float64, threshold=2e5, out=None):
         """Mean, variance and gradient at ``testing`` (n_predict, n_inputs) (reference
-        :327-341).  ``do_unc`` only affects the numpy branch, as in the reference.  ``out`` (GPU branch only, not in
-        the reference): three arrays to fill instead of pooled ones, e.g. page-locked ones (``pinned_empty``)."""
+        :327-341).  ``do_unc`` only affects the numpy branch, as in the reference: with ``is_gpu=True`` this
+        always returns three arrays; ``gpu_predict(testing, precision, threshold, do_unc=False)`` is the GPU
+        form that skips the variance.  ``out`` (GPU branch only, not in the reference): three arrays to fill
+        instead of pooled ones, e.g. page-locked ones (``pinned_empty``)."""
         if is_gpu == True:  # noqa: E712  (reference spelling, :338)
             return self.gpu_predict(testing, precision, threshold=threshold, out=out)
         return self.cpu_predict(testing, do_unc)

@@ -53,6 +53,9 @@ SIGNATURES = {
                                   c_i64, c_int]),
     "gp_predict_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_i64, c_int, c_i64]),
+    "gp_predict_mean_grad_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int]),
+    "gp_predict_mean_grad_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_i64, c_int, c_i64]),
     "gp_ctx_host_threads": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "gp_device_numa_node": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "gp_kernel_ksteps": (c_int, [c_int, c_int, ctypes.POINTER(c_int)]),
@@ -450,6 +453,40 @@ class Model:
         ``testing``); without it the arrays come from the context's ``OutputPool`` (memory of
         results the caller has dropped is reused).  ``max_block_rows`` > 0 bounds the rows per
         launch."""
+        testing, outs = self._host_call(testing, deriv_layout, out, with_var=True)
+        mu, var, deriv = outs
+        M = testing.shape[0]
+        if M:
+            check(self.ctx.lib.gp_predict_host(
+                self.ctx.h, self.h, GP_F64 if testing.dtype == np.float64 else GP_F32, _ptr(testing), _ptr(mu),
+                _ptr(var), _ptr(deriv), M, int(deriv_layout), int(max_block_rows)), "gp_predict_host")
+        return mu, var, deriv
+
+    def predict_mean_grad_device(self, d_testing, d_mu, d_deriv, n_predict, deriv_layout=GP_DERIV_ROWMAJOR):
+        """Mean and gradient only (``gp_predict_mean_grad_device``): the no-variance kernels,
+        asynchronous on the context's stream; device pointers, mu [E][M], deriv [E][M*D].  Works
+        on a model built without invQ."""
+        check(self.ctx.lib.gp_predict_mean_grad_device(self.ctx.h, self.h, d_testing, d_mu, d_deriv,
+                                                       int(n_predict), int(deriv_layout)),
+              "gp_predict_mean_grad_device")
+
+    def predict_mean_grad(self, testing, deriv_layout=GP_DERIV_ROWMAJOR, out=None, max_block_rows=0):
+        """``predict`` without the variance (``gp_predict_mean_grad_host``): returns (mu, deriv),
+        bit for bit those of ``predict``, with the same dtype rules, routes, ``out=(mu, deriv)`` /
+        ``OutputPool`` handling and ``max_block_rows``.  Works on a model built without invQ --
+        the GPU form of the reference's ``cpu_predict(do_unc=False)``."""
+        testing, outs = self._host_call(testing, deriv_layout, out, with_var=False)
+        mu, deriv = outs
+        M = testing.shape[0]
+        if M:
+            check(self.ctx.lib.gp_predict_mean_grad_host(
+                self.ctx.h, self.h, GP_F64 if testing.dtype == np.float64 else GP_F32, _ptr(testing),
+                _ptr(mu), _ptr(deriv), M, int(deriv_layout), int(max_block_rows)), "gp_predict_mean_grad_host")
+        return mu, deriv
+
+    def _host_call(self, testing, deriv_layout, out, with_var):
+        """The rows as the library takes them and the output arrays ((mu, var, deriv), or (mu, deriv)
+        without the variance) of ``predict`` / ``predict_mean_grad``."""
         testing = np.asarray(testing)
         if testing.dtype != np.float64 or self.dtype == np.float64:
             testing = np.ascontiguousarray(testing, dtype=self.dtype)
@@ -464,25 +501,25 @@ class Model:
         E = getattr(self, "n_emulators", None)
         lead = () if E is None else (E,)
         dshape = lead + ((M, D) if deriv_layout == GP_DERIV_ROWMAJOR else (D, M))
+        nv = 2 if with_var else 1
+        shapes = (lead + (M,),) * nv + (dshape,)
         if out is None:
-            # one buffer, three views: the library brings a small call's results back in one copy
-            # when result | error | deriv lie back to back
+            # one buffer, two or three views: the library brings a small call's results back in
+            # one copy when result | error | deriv (or result | deriv) lie back to back
             n_e = (E or 1) * M
-            flat = self.ctx.out_pool.take((n_e * (2 + D),), hdt)
-            mu, var = flat[:n_e].reshape(lead + (M,)), flat[n_e:2 * n_e].reshape(lead + (M,))
-            deriv = flat[2 * n_e:].reshape(dshape)
+            flat = self.ctx.out_pool.take((n_e * (nv + D),), hdt)
+            outs = tuple(flat[k * n_e:(k + 1) * n_e].reshape(lead + (M,)) for k in range(nv))
+            outs += (flat[nv * n_e:].reshape(dshape),)
         else:
-            mu, var, deriv = out
-            for a, shape in ((mu, lead + (M,)), (var, lead + (M,)), (deriv, dshape)):
+            outs = tuple(out)
+            if len(outs) != nv + 1:
+                raise ValueError("out must hold %d arrays" % (nv + 1))
+            for a, shape in zip(outs, shapes):
                 if (not isinstance(a, np.ndarray) or a.dtype != hdt or a.shape != shape
                         or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]):
                     raise ValueError("out arrays must be writeable C-contiguous %s arrays of shapes "
-                                     "%s, %s, %s" % (hdt, lead + (M,), lead + (M,), dshape))
-        if M:
-            check(self.ctx.lib.gp_predict_host(
-                self.ctx.h, self.h, GP_F64 if hdt == np.float64 else GP_F32, _ptr(testing), _ptr(mu),
-                _ptr(var), _ptr(deriv), M, int(deriv_layout), int(max_block_rows)), "gp_predict_host")
-        return mu, var, deriv
+                                     "%s" % (hdt, ", ".join(str(x) for x in shapes)))
+        return testing, outs
 
     def hessian_device(self, d_testing, d_hess, n_predict):
         """Asynchronous Hessian launch; device pointers, hess is (n_predict, D, D)."""
@@ -520,8 +557,10 @@ class BatchModel(Model):
     """E emulators on the SAME training inputs (per-band pattern,
     tests/test_perband_emulator.py:22-37), predicted over shared test rows in ONE launch.
 
-    expX (E, D+2), inputs (N, D), invQt (E, N), invQ (E, N, N).
-    ``predict`` (inherited: the slab pipeline) returns mu (E, M), var (E, M), deriv (E, M, D).
+    expX (E, D+2), inputs (N, D), invQt (E, N), invQ (E, N, N) or None (a batch for
+    ``predict_mean_grad`` only: no inverse is packed or uploaded).
+    ``predict`` (inherited: the slab pipeline) returns mu (E, M), var (E, M), deriv (E, M, D);
+    ``predict_mean_grad`` mu (E, M), deriv (E, M, D).
     """
 
     def __init__(self, ctx, expX, inputs, invQt, invQ, precision=np.float64):
@@ -536,12 +575,13 @@ class BatchModel(Model):
             raise ValueError("expX must be (n_emulators, theta_size)")
         self.n_emulators = E = expX.shape[0]
         invQt = np.ascontiguousarray(invQt, dtype=np.float64)
-        invQ = np.ascontiguousarray(invQ, dtype=np.float64)
-        if invQt.shape != (E, self.n_train) or invQ.shape != (E, self.n_train, self.n_train):
+        if invQ is not None:
+            invQ = np.ascontiguousarray(invQ, dtype=np.float64)
+        if invQt.shape != (E, self.n_train) or (invQ is not None and invQ.shape != (E, self.n_train, self.n_train)):
             raise ValueError("invQt must be (E, N) and invQ (E, N, N)")
         fn = ctx.lib.gp_batch_create_f64 if self.dtype == np.float64 else ctx.lib.gp_batch_create_f32_h64
         h = c_void_p()
-        check(fn(ctx.h, E, _ptr(expX), _ptr(inputs), _ptr(invQt), _ptr(invQ),
+        check(fn(ctx.h, E, _ptr(expX), _ptr(inputs), _ptr(invQt), _ptr(invQ) if invQ is not None else None,
                  self.n_train, self.n_inputs, expX.shape[1], ctypes.byref(h)), "gp_batch_create")
         self.h = h
 

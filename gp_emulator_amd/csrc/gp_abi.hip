@@ -35,8 +35,8 @@ namespace gpk {
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);
 hipError_t launch_reconstruct_f32(const ReconArgs<float>&, int wide, int cus, hipStream_t);
 hipError_t launch_reconstruct_f64(const ReconArgs<double>&, int wide, int cus, hipStream_t);
-hipError_t launch_few_f32(int, const PredictArgs<float>&, int, int, hipStream_t);
-hipError_t launch_few_f64(int, const PredictArgs<double>&, int, int, hipStream_t);
+hipError_t launch_few_f32(int, const PredictArgs<float>&, int, int, bool, hipStream_t);
+hipError_t launch_few_f64(int, const PredictArgs<double>&, int, int, bool, hipStream_t);
 hipError_t launch_generic_f32(const GenericArgs<float>&, int, hipStream_t);
 hipError_t launch_generic_f64(const GenericArgs<double>&, int, hipStream_t);
 #define GP_DECL(nb)                                                                          \
@@ -48,7 +48,9 @@ hipError_t launch_hessian_f32(int, const HessianArgs<float>&, int, hipStream_t);
 hipError_t launch_hessian_f64(int, const HessianArgs<double>&, int, hipStream_t);
 #define GP_DECL(nk)                                                                         \
   hipError_t launch_predict_f32_##nk(int, const PredictArgs<float>&, int, hipStream_t);     \
-  hipError_t launch_predict_f64_##nk(int, const PredictArgs<double>&, int, hipStream_t);
+  hipError_t launch_predict_f64_##nk(int, const PredictArgs<double>&, int, hipStream_t);    \
+  hipError_t launch_mean_grad_f32_##nk(int, const PredictArgs<float>&, int, hipStream_t);   \
+  hipError_t launch_mean_grad_f64_##nk(int, const PredictArgs<double>&, int, hipStream_t);
 GP_FOR_EACH_KERNEL_NK(GP_DECL)
 #undef GP_DECL
 }  // namespace gpk
@@ -299,21 +301,24 @@ static int pack_model(const TH* expX, const TH* inputs, const TH* invQt, const T
   return GP_OK;
 }
 
+// var = false: the mean+gradient instance predict_kernel<T, D, NK, false>
 template <typename T>
-static hipError_t launch(int knk, int kd, const gpk::PredictArgs<T>& a, int grid, hipStream_t s);
+static hipError_t launch(int knk, int kd, const gpk::PredictArgs<T>& a, int grid, bool var, hipStream_t s);
 template <>
-hipError_t launch<float>(int knk, int kd, const gpk::PredictArgs<float>& a, int grid, hipStream_t s) {
+hipError_t launch<float>(int knk, int kd, const gpk::PredictArgs<float>& a, int grid, bool var, hipStream_t s) {
   switch (knk) {
-#define GP_CASE(nk) case nk: return gpk::launch_predict_f32_##nk(kd, a, grid, s);
+#define GP_CASE(nk) \
+  case nk: return var ? gpk::launch_predict_f32_##nk(kd, a, grid, s) : gpk::launch_mean_grad_f32_##nk(kd, a, grid, s);
     GP_FOR_EACH_KERNEL_NK(GP_CASE)
 #undef GP_CASE
   }
   return hipErrorInvalidValue;
 }
 template <>
-hipError_t launch<double>(int knk, int kd, const gpk::PredictArgs<double>& a, int grid, hipStream_t s) {
+hipError_t launch<double>(int knk, int kd, const gpk::PredictArgs<double>& a, int grid, bool var, hipStream_t s) {
   switch (knk) {
-#define GP_CASE(nk) case nk: return gpk::launch_predict_f64_##nk(kd, a, grid, s);
+#define GP_CASE(nk) \
+  case nk: return var ? gpk::launch_predict_f64_##nk(kd, a, grid, s) : gpk::launch_mean_grad_f64_##nk(kd, a, grid, s);
     GP_FOR_EACH_KERNEL_NK(GP_CASE)
 #undef GP_CASE
   }
@@ -544,11 +549,14 @@ hipError_t launch_generic<double>(const gpk::GenericArgs<double>& a, int grid, h
   return gpk::launch_generic_f64(a, grid, s);
 }
 
+// d_var == nullptr: mean and gradient only (the *_mean_grad entry points), on the no-variance
+// instance of whichever kernel the rule below picks for a full predict of the same call.
 template <typename T>
 static int predict_device(gp_ctx* ctx, const gp_model* m, const void* d_testing, void* d_mu,
                           void* d_var, void* d_deriv, int64_t M, int layout,
                           hipStream_t stream = nullptr, bool rows_prescaled = false) {
   if (!stream) stream = ctx->stream;
+  const bool want_var = d_var != nullptr;
   if (m->kernel_nb == 0) {   // general-shape kernel
     if (m->n_emulators != 1)
       return fail(GP_ERR_UNSUPPORTED, "batched emulators need n_train <= %d and n_inputs <= %d",
@@ -568,6 +576,7 @@ static int predict_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
     g.acol = m->kernel_d;
     g.dk = m->kernel_d;
     g.deriv_row_major = layout == GP_DERIV_ROWMAJOR;
+    g.want_var = want_var ? 1 : 0;
     int64_t tiles = (M + 15) / 16;
     int64_t grid = (int64_t)ctx->compute_units * 4;
     if (grid > tiles) grid = tiles;
@@ -600,19 +609,19 @@ static int predict_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
   const int64_t tiles = (M + gpk::kTile - 1) / gpk::kTile * m->n_emulators;
   if (!no_few && tiles <= 2 * (int64_t)ctx->compute_units) {
     hipError_t e;
-    if constexpr (sizeof(T) == 8) e = gpk::launch_few_f64(m->kernel_d, a, m->kernel_nb, (int)tiles, stream);
-    else e = gpk::launch_few_f32(m->kernel_d, a, m->kernel_nb, (int)tiles, stream);
+    if constexpr (sizeof(T) == 8) e = gpk::launch_few_f64(m->kernel_d, a, m->kernel_nb, (int)tiles, want_var, stream);
+    else e = gpk::launch_few_f32(m->kernel_d, a, m->kernel_nb, (int)tiles, want_var, stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "kernel launch (few rows): %s", hipGetErrorString(e));
     return GP_OK;
   }
-  constexpr int kRowsPerWG = gpk::Geo<T>::kRowsPerWG;
+  const int kRowsPerWG = want_var ? gpk::Geo<T>::kRowsPerWG : gpk::Geo<T, false>::kRowsPerWG;
   const int64_t groups = (M + kRowsPerWG - 1) / kRowsPerWG * m->n_emulators;
   if ((M + kRowsPerWG - 1) / kRowsPerWG > 0x7fffffffLL)
     return fail(GP_ERR_INVALID, "n_predict too large for one launch");
-  // persistent grid: the kernel's occupancy (2 waves per SIMD), grid-stride over work items
-  int64_t grid = (int64_t)ctx->compute_units * gpk::Geo<T>::kWGPerCU;
+  // persistent grid: the kernel's occupancy (full: 2 waves per SIMD), grid-stride over work items
+  int64_t grid = (int64_t)ctx->compute_units * (want_var ? gpk::Geo<T>::kWGPerCU : gpk::Geo<T, false>::kWGPerCU);
   if (grid > groups) grid = groups;
-  hipError_t e = launch<T>(m->kernel_nk, m->kernel_d, a, (int)grid, stream);
+  hipError_t e = launch<T>(m->kernel_nk, m->kernel_d, a, (int)grid, want_var, stream);
   if (e != hipSuccess) return fail(GP_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return GP_OK;
 }
@@ -1083,7 +1092,8 @@ static int predict_host_pinned(gp_ctx* ctx, const gp_model* m, const T* testing,
   const int64_t round = (int64_t)ctx->compute_units * gpk::Geo<T>::kWGPerCU * kRowsPerWG;
   int64_t cap = 4 * round;
   if (max_rows > 0 && cap > max_rows) cap = max_rows < kRowsPerWG ? kRowsPerWG : max_rows / kRowsPerWG * kRowsPerWG;
-  const size_t in_elems = (size_t)cap * D, out_elems = (size_t)cap * (2 + D);
+  const bool want_var = error != nullptr;      // (null: mean and gradient only)
+  const size_t in_elems = (size_t)cap * D, out_elems = (size_t)cap * ((want_var ? 2 : 1) + D);
   int rc = ensure_pipe(ctx, 0, 0, (in_elems + out_elems) * sizeof(T));
   if (rc) return rc;
   gp_pipe& pp = ctx->pipe;
@@ -1096,8 +1106,8 @@ static int predict_host_pinned(gp_ctx* ctx, const gp_model* m, const T* testing,
     if (e != hipSuccess) break;
     T* d_in = (T*)pp.dev[k];
     T* d_mu = d_in + in_elems;
-    T* d_var = d_mu + n;
-    T* d_der = d_var + n;
+    T* d_var = want_var ? d_mu + n : nullptr;
+    T* d_der = d_mu + (want_var ? 2 : 1) * n;
     e = hipMemcpyAsync(d_in, testing + (size_t)s0 * D, sizeof(T) * (size_t)n * D, hipMemcpyHostToDevice, pp.up);
     if (e == hipSuccess) e = hipEventRecord(pp.in_there[k], pp.up);
     if (e == hipSuccess) e = hipStreamWaitEvent(pp.stream[k], pp.in_there[k], 0);
@@ -1108,7 +1118,7 @@ static int predict_host_pinned(gp_ctx* ctx, const gp_model* m, const T* testing,
     if (e == hipSuccess) e = hipStreamWaitEvent(pp.down, pp.computed[k], 0);
     if (e == hipSuccess) e = hipMemcpyAsync(deriv + (size_t)s0 * D, d_der, sizeof(T) * (size_t)n * D, hipMemcpyDeviceToHost, pp.down);
     if (e == hipSuccess) e = hipMemcpyAsync(result + s0, d_mu, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, pp.down);
-    if (e == hipSuccess) e = hipMemcpyAsync(error + s0, d_var, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, pp.down);
+    if (e == hipSuccess && want_var) e = hipMemcpyAsync(error + s0, d_var, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, pp.down);
     if (e == hipSuccess) e = hipEventRecord(pp.done[k], pp.down);
     s0 += n;
     if (2 * cur <= cap) cur *= 2;
@@ -1123,13 +1133,16 @@ static int predict_host_pinned(gp_ctx* ctx, const gp_model* m, const T* testing,
 
 // predict for host arrays.  T = compute type (the model's), TH = the caller's host type (T, or
 // double with T = float).  Outputs: result/error [E][M], deriv [E][M*D] (row-major) or [E][D][M].
+// error == nullptr: mean and gradient only, on the no-variance kernels, by the same three routes.
 template <typename T, typename TH>
 static int predict_host(gp_ctx* ctx, const gp_model* m, const TH* testing, TH* result, TH* error,
                         TH* deriv, int64_t M, int layout, int64_t max_rows) {
   const int D = m->n_inputs, E = m->n_emulators;
   if (M == 0) return GP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  const size_t out_row = (size_t)E * (2 + D);
+  const bool want_var = error != nullptr;
+  const int nv = want_var ? 2 : 1;             // per-row outputs in front of the gradient
+  const size_t out_row = (size_t)E * (nv + D);
   // Small calls (one slab, no type conversion): no staging, no helper threads -- the rows go
   // straight from the caller's array to the device and the results straight back (the runtime
   // pins the pages for the DMA: 61 us for 2.6 MB on the box, where a staged copy needs a thread
@@ -1139,21 +1152,22 @@ static int predict_host(gp_ctx* ctx, const gp_model* m, const TH* testing, TH* r
   if (sizeof(T) == sizeof(TH) && M <= direct_rows && (max_rows <= 0 || M <= max_rows) &&
       (size_t)M * out_row * sizeof(T) <= ((size_t)32 << 20)) {
     const size_t n_in = (size_t)M * D, n_e = (size_t)E * M;
-    int rc = ensure_scratch(ctx, (n_in + n_e * (2 + D)) * sizeof(T));
+    int rc = ensure_scratch(ctx, (n_in + n_e * (nv + D)) * sizeof(T));
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     T* d_in = (T*)ctx->scratch;
     T* d_mu = d_in + n_in;
-    T* d_var = d_mu + n_e;
-    T* d_der = d_var + n_e;
+    T* d_var = want_var ? d_mu + n_e : nullptr;
+    T* d_der = d_mu + nv * n_e;
     HIP_TRY(hipMemcpyAsync(d_in, testing, n_in * sizeof(T), hipMemcpyHostToDevice, st));
     rc = predict_device<T>(ctx, m, d_in, d_mu, d_var, d_der, M, layout, st);
     hipError_t e = hipSuccess;
     if (!rc) {
-      // one copy when the caller laid result | error | deriv out back to back
-      const bool one = (const void*)error == (const void*)(result + n_e) && (const void*)deriv == (const void*)(error + n_e);
-      e = hipMemcpyAsync(result, d_mu, (one ? n_e * (2 + D) : n_e) * sizeof(T), hipMemcpyDeviceToHost, st);
-      if (!one && e == hipSuccess) e = hipMemcpyAsync(error, d_var, n_e * sizeof(T), hipMemcpyDeviceToHost, st);
+      // one copy when the caller laid result | error | deriv (or result | deriv) out back to back
+      const bool one = want_var ? (const void*)error == (const void*)(result + n_e) && (const void*)deriv == (const void*)(error + n_e)
+                                : (const void*)deriv == (const void*)(result + n_e);
+      e = hipMemcpyAsync(result, d_mu, (one ? n_e * (nv + D) : n_e) * sizeof(T), hipMemcpyDeviceToHost, st);
+      if (!one && want_var && e == hipSuccess) e = hipMemcpyAsync(error, d_var, n_e * sizeof(T), hipMemcpyDeviceToHost, st);
       if (!one && e == hipSuccess) e = hipMemcpyAsync(deriv, d_der, n_e * D * sizeof(T), hipMemcpyDeviceToHost, st);
     }
     const hipError_t es = hipStreamSynchronize(st);      // whatever happened, leave the stream idle
@@ -1166,7 +1180,7 @@ static int predict_host(gp_ctx* ctx, const gp_model* m, const TH* testing, TH* r
     static const bool no_pinned = [] { const char* ev = getenv("GP_NO_PINNED_PATH"); return ev && atoi(ev) != 0; }();
     if (!no_pinned && E == 1 && layout == GP_DERIV_ROWMAJOR &&
         is_pinned_host(testing, (size_t)M * D * sizeof(T)) && is_pinned_host(result, (size_t)M * sizeof(T)) &&
-        is_pinned_host(error, (size_t)M * sizeof(T)) && is_pinned_host(deriv, (size_t)M * D * sizeof(T)))
+        (!want_var || is_pinned_host(error, (size_t)M * sizeof(T))) && is_pinned_host(deriv, (size_t)M * D * sizeof(T)))
       return predict_host_pinned<T>(ctx, m, (const T*)testing, (T*)result, (T*)error, (T*)deriv, M, max_rows);
   }
   const int64_t slab = slab_rows<T>(ctx, m, M, (int64_t)out_row, max_rows);
@@ -1198,10 +1212,10 @@ static int predict_host(gp_ctx* ctx, const gp_model* m, const TH* testing, TH* r
     }
   };
   auto launch = [=](T* d_in, T* d_out, int64_t n, hipStream_t st) {
-    return predict_device<T>(ctx, m, d_in, d_out, d_out + (size_t)E * n, d_out + (size_t)2 * E * n, n,
+    return predict_device<T>(ctx, m, d_in, d_out, want_var ? d_out + (size_t)E * n : nullptr, d_out + (size_t)nv * E * n, n,
                              layout, st, prescale);
   };
-  // staged slab: mu [E][n], var [E][n], deriv [E][n*D] or [E][D][n]
+  // staged slab: mu [E][n], var [E][n] (want_var only), deriv [E][n*D] or [E][D][n]
   auto copy_out = [=](const T* o, int64_t s0, int64_t n, int64_t lo, int64_t hi) {
     // a task is a share [lo, hi) of the slab's rows -- or, for batched emulators, the same share of
     // the EMULATORS with all the slab's rows: every emulator's results are a separate run of the
@@ -1215,8 +1229,8 @@ static int predict_host(gp_ctx* ctx, const gp_model* m, const TH* testing, TH* r
     }
     for (int e = e_lo; e < e_hi; ++e) {
       convert_range(result + (size_t)e * M + s0, o + (size_t)e * n, (size_t)lo, (size_t)hi);
-      convert_range(error + (size_t)e * M + s0, o + (size_t)(E + e) * n, (size_t)lo, (size_t)hi);
-      const T* od = o + (size_t)2 * E * n + (size_t)e * n * D;
+      if (want_var) convert_range(error + (size_t)e * M + s0, o + (size_t)(E + e) * n, (size_t)lo, (size_t)hi);
+      const T* od = o + (size_t)nv * E * n + (size_t)e * n * D;
       TH* hd = deriv + (size_t)e * M * D;
       if (layout == GP_DERIV_ROWMAJOR) {
         convert_range(hd + (size_t)s0 * D, od, (size_t)lo * D, (size_t)hi * D);
@@ -1414,7 +1428,7 @@ template <typename T>
 static int mv_predict_host(gp_ctx* ctx, const gp_model* m, const T* d_basis, const T* y, int64_t M,
                            int n_bands, T* fwd, T* jac, const host_check* chk = nullptr) {
   const int D = m->n_inputs, P = m->n_emulators;
-  const size_t n_y = (size_t)M * D, n_gp = (size_t)P * M * (2 + D);
+  const size_t n_y = (size_t)M * D, n_gp = (size_t)P * M * (1 + D);   // mu, deriv: the variance is not needed
   const size_t n_fwd = (size_t)M * n_bands, n_jac = jac ? (size_t)M * D * n_bands : 0;
   if ((n_fwd + n_jac) * sizeof(T) > kMvResultMax)
     return fail(GP_ERR_UNSUPPORTED, "gp_mv_predict_host returns at most %zu MiB per call: split the rows", kMvResultMax >> 20);
@@ -1424,12 +1438,11 @@ static int mv_predict_host(gp_ctx* ctx, const gp_model* m, const T* d_basis, con
   hipStream_t st = ctx->stream;
   T* d_y = (T*)ctx->scratch;
   T* d_mu = d_y + n_y;
-  T* d_var = d_mu + (size_t)P * M;
-  T* d_der = d_var + (size_t)P * M;
+  T* d_der = d_mu + (size_t)P * M;
   T* d_fwd = d_y + n_y + n_gp;
   T* d_jac = d_fwd + n_fwd;
   HIP_TRY(hipMemcpyAsync(d_y, y, n_y * sizeof(T), hipMemcpyHostToDevice, st));
-  rc = predict_device<T>(ctx, m, d_y, d_mu, d_var, d_der, M, GP_DERIV_ROWMAJOR, st);
+  rc = predict_device<T>(ctx, m, d_y, d_mu, nullptr, d_der, M, GP_DERIV_ROWMAJOR, st);   // mean+gradient kernels
   const int dtype = sizeof(T) == 8 ? GP_F64 : GP_F32;
   if (!rc) rc = reconstruct_on(ctx, dtype, d_basis, d_mu, d_fwd, M, P, n_bands, st);
   if (!rc && jac) rc = reconstruct_on(ctx, dtype, d_basis, d_der, d_jac, M * D, P, n_bands, st);
@@ -1534,6 +1547,43 @@ int gp_predict_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
   if (model->dtype == GP_F64)
     return predict_device<double>(ctx, model, d_testing, d_mu, d_var, d_deriv, n_predict, deriv_layout);
   return predict_device<float>(ctx, model, d_testing, d_mu, d_var, d_deriv, n_predict, deriv_layout);
+}
+
+int gp_predict_mean_grad_device(gp_ctx* ctx, const gp_model* model, const void* d_testing, void* d_mu,
+                                void* d_deriv, int64_t n_predict, int deriv_layout) {
+  if (!ctx || !model) return fail(GP_ERR_INVALID, "null context or model");
+  if (n_predict < 0) return fail(GP_ERR_INVALID, "n_predict < 0");
+  if (n_predict == 0) return GP_OK;
+  if (!d_testing || !d_mu || !d_deriv) return fail(GP_ERR_INVALID, "null device pointer");
+  if (deriv_layout != GP_DERIV_DMAJOR && deriv_layout != GP_DERIV_ROWMAJOR)
+    return fail(GP_ERR_INVALID, "bad deriv_layout %d", deriv_layout);
+  if (model->device != ctx->device) return fail(GP_ERR_INVALID, "model lives on device %d, context on %d", model->device, ctx->device);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (model->dtype == GP_F64)
+    return predict_device<double>(ctx, model, d_testing, d_mu, nullptr, d_deriv, n_predict, deriv_layout);
+  return predict_device<float>(ctx, model, d_testing, d_mu, nullptr, d_deriv, n_predict, deriv_layout);
+}
+
+int gp_predict_mean_grad_host(gp_ctx* ctx, const gp_model* model, int host_dtype, const void* testing,
+                              void* result, void* deriv, int64_t n_predict, int deriv_layout,
+                              int64_t max_block_rows) {
+  if (!ctx || !model) return fail(GP_ERR_INVALID, "null context or model");
+  if (n_predict < 0) return fail(GP_ERR_INVALID, "n_predict < 0");
+  if (n_predict == 0) return GP_OK;
+  if (!testing || !result || !deriv) return fail(GP_ERR_INVALID, "null pointer");
+  if (deriv_layout != GP_DERIV_DMAJOR && deriv_layout != GP_DERIV_ROWMAJOR)
+    return fail(GP_ERR_INVALID, "bad deriv_layout %d", deriv_layout);
+  if (model->device != ctx->device) return fail(GP_ERR_INVALID, "model lives on device %d, context on %d", model->device, ctx->device);
+  if (model->dtype == GP_F64 && host_dtype == GP_F64)
+    return guarded([&] { return predict_host<double, double>(ctx, model, (const double*)testing, (double*)result, nullptr,
+                                        (double*)deriv, n_predict, deriv_layout, max_block_rows); });
+  if (model->dtype == GP_F32 && host_dtype == GP_F32)
+    return guarded([&] { return predict_host<float, float>(ctx, model, (const float*)testing, (float*)result, nullptr,
+                                      (float*)deriv, n_predict, deriv_layout, max_block_rows); });
+  if (model->dtype == GP_F32 && host_dtype == GP_F64)
+    return guarded([&] { return predict_host<float, double>(ctx, model, (const double*)testing, (double*)result, nullptr,
+                                       (double*)deriv, n_predict, deriv_layout, max_block_rows); });
+  return fail(GP_ERR_INVALID, "host arrays must have the model's dtype, or be float64 for a float32 model");
 }
 
 int gp_predict_host(gp_ctx* ctx, const gp_model* model, int host_dtype, const void* testing,

@@ -1,4 +1,4 @@
-// predict_few_kernel<T, D> launchers (every compiled D; NB is a run-time argument); build.py
+// predict_few_kernel<T, D, kVar> launchers (every compiled D; NB is a run-time argument); build.py
 // compiles this with -DGP_T / -DGP_TNAME.
 #include "gp_dispatch.hpp"
 #include "gp_predict_few_kernel.hpp"
@@ -8,11 +8,14 @@
 
 namespace gpk {
 
-hipError_t GP_CAT(launch_few_, GP_TNAME)(int kd, const PredictArgs<GP_T>& a, int nb, int grid, hipStream_t stream) {
+// var = false: the mean+gradient instances (no phase B)
+hipError_t GP_CAT(launch_few_, GP_TNAME)(int kd, const PredictArgs<GP_T>& a, int nb, int grid, bool var,
+                                        hipStream_t stream) {
   switch (kd) {
 #define GP_CASE(d)                                                                                         \
   case d:                                                                                                  \
-    hipLaunchKernelGGL((predict_few_kernel<GP_T, d>), dim3(grid), dim3(fkThreads), 0, stream, a, nb);      \
+    if (var) hipLaunchKernelGGL((predict_few_kernel<GP_T, d, true>), dim3(grid), dim3(fkThreads), 0, stream, a, nb); \
+    else hipLaunchKernelGGL((predict_few_kernel<GP_T, d, false>), dim3(grid), dim3(fkThreads), 0, stream, a, nb); \
     break;
     GP_FOR_EACH_KERNEL_D(GP_CASE)
 #undef GP_CASE

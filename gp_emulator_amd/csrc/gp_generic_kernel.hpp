@@ -32,6 +32,7 @@ struct GenericArgs {
   int N, D;
   int ds, acol, dk;   // row stride, alpha column, length of the sd / centre blocks
   int deriv_row_major;
+  int want_var;       // 0: mean and gradient only (invQ and var are not touched; invQ may be null)
 };
 
 template <typename T>
@@ -95,6 +96,7 @@ __global__ __launch_bounds__(gkThreads) void predict_generic_kernel(GenericArgs<
         else p.deriv[(long long)d * p.M + m] = gsum;
       }
     }
+    if (!p.want_var) continue;   // (uniform; the next tile's first barrier orders s_k's reuse)
     __syncthreads();   // the whole kernel-row tile is in LDS
 
     // variance: k^T invQ k with invQ as given (16 consecutive columns per lane group)

@@ -29,7 +29,9 @@ constexpr int fkWaves = 8;
 constexpr int fkThreads = fkWaves * 64;
 constexpr int fkMaxKSteps = 4 * 20;      // 4 GP_MAX_KERNEL_NB
 
-template <typename T, int D>
+// kVar = false: the mean+gradient instance.  Phase B and the weight tile's LDS copy are compiled out;
+// phase A and the finish are the same source, so mu and deriv are bit for bit those of kVar = true.
+template <typename T, int D, bool kVar = true>
 __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T> p, int NB) {
   typedef Real<T> R;
   typedef typename R::acc_t acc_t;
@@ -37,7 +39,7 @@ __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T
   constexpr int kVals = D + 2;                       // mu, G_0..G_{D-1}, variance sum
 
   __shared__ __attribute__((aligned(16))) T s_xa[4 * fkMaxKSteps * row_stride(D)];   // training rows [x'', alpha, h]
-  __shared__ T s_k[fkMaxKSteps][64];                 // the weight tile, B-operand layout
+  __shared__ T s_k[kVar ? fkMaxKSteps : 1][64];      // the weight tile, B-operand layout
   __shared__ T s_part[fkWaves][kTile][kVals];        // per-wave partial sums by test row
 
   const int tid = threadIdx.x;
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T
 
   const T* xa = p.xa + e * p.xa_stride;
   const T* frags = p.frags + e * p.frags_stride;
+  (void)frags;
   const T* sdp = p.sd + e * p.sd_stride;
   const long long m = (long long)tile * kTile + ml;
   const long long mc = m < p.M ? m : p.M - 1;
@@ -106,7 +109,7 @@ __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T
       }
       k = b * R::exp_(T(-0.5) * r2);
     }
-    s_k[ks][lane] = k;
+    if constexpr (kVar) s_k[ks][lane] = k;
     const T wgt = k * al;
     mu += wgt;
 #pragma unroll
@@ -122,6 +125,7 @@ __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T
   __syncthreads();                                   // the whole weight tile is in LDS
 
   // ---- phase B: this wave's column blocks --------------------------------------------------------
+  if constexpr (kVar) {
   T vacc = T(0);
   auto column_block = [&](const int J) __attribute__((always_inline)) {
     // fragments (I, J, s), I = J .. NB - 1, s = 0 .. 3, lie one after the other in the packed buffer
@@ -151,6 +155,7 @@ __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T
   vacc = xor_reduce_groups(vacc);
   if (g == 0) s_part[w][ml][1 + D] = vacc;
   __syncthreads();
+  }   // (kVar)
 
   // ---- finish: wave 0 adds the partial results in wave order and stores ---------------------------
   if (w == 0 && m < p.M) {
@@ -163,10 +168,11 @@ __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T
     };
     const T mean = total(0) + poison;
     T* o_mu = p.mu + e * p.M;
-    T* o_var = p.var + e * p.M;
     T* o_der = p.deriv + e * p.M * p.d_actual;
     if (g == 0) o_mu[m] = mean;
-    if (g == 1) o_var[m] = b - total(1 + D) + poison;
+    if constexpr (kVar) {
+      if (g == 1) p.var[e * p.M + m] = b - total(1 + D) + poison;
+    }
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       if ((d & 3) == g && d < p.d_actual) {

@@ -90,7 +90,9 @@ namespace gpk {
 // workgroup beside an MFMA-phase one, and partners in the same phase keep the workgroup's
 // waves in step (short barrier waits) while each fragment staged in LDS feeds every wave.
 constexpr int kTile = 16;            // test rows per wave tile (MFMA N dimension)
-template <typename T> struct Geo {
+// kVar = false: the mean+gradient instance (no variance, no matrix core, no K_* tile kept), whose
+// geometry is its own -- see the specialisation below.
+template <typename T, bool kVar = true> struct Geo {
   static constexpr int kWaves = sizeof(T) == 8 ? GP_WAVES : GP_WAVES_F32;  // per workgroup
   static constexpr int kThreads = kWaves * 64;
 #ifndef GP_WG_PER_CU_SMALL
@@ -101,6 +103,28 @@ template <typename T> struct Geo {
   static constexpr int kRowsPerWG = kWaves * kTile;
   // A-operand fragments per LDS chunk (double-buffered: 2 x kChunk x 64 reals of LDS)
   static constexpr int kChunk = sizeof(T) == 8 ? GP_CHUNK : GP_CHUNK_F32;
+};
+// Mean+gradient instance: what set two waves per SIMD above (the K_* tile in registers, the fragment
+// buffers in LDS) is gone, so phase A alone picks the occupancy.  One workgroup per CU of GP_MG_WAVES
+// waves (candidates and times: profiles/r05_mean_grad.txt), so LDS holds one copy of the training rows
+// per CU.  fp64: 12 waves = three per SIMD (168 VGPRs: <double,11,63> 142 and no scratch, <double,16,75>
+// one spilled register; at 16 waves the 128-register budget spills from D = 10 on); fp32: 16 waves = four.
+#ifndef GP_MG_WAVES
+#define GP_MG_WAVES 12
+#endif
+#ifndef GP_MG_WAVES_F32
+#define GP_MG_WAVES_F32 16
+#endif
+#ifndef GP_MG_WG_PER_CU
+#define GP_MG_WG_PER_CU 1
+#endif
+template <typename T> struct Geo<T, false> {
+  static constexpr int kWaves = sizeof(T) == 8 ? GP_MG_WAVES : GP_MG_WAVES_F32;
+  static constexpr int kThreads = kWaves * 64;
+  static constexpr int kWGPerCU = GP_MG_WG_PER_CU;
+  static constexpr int kWavesPerSimd = kWGPerCU * kWaves / 4;
+  static constexpr int kRowsPerWG = kWaves * kTile;
+  static constexpr int kChunk = 1;     // (no fragment buffers)
 };
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -447,11 +471,15 @@ __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" :
 #endif
 
 // NK = k-steps (groups of 4 training points) the kernel is compiled for: n_train <= 4 NK.
-template <typename T, int D, int NK>
-__global__ __launch_bounds__(Geo<T>::kThreads, Geo<T>::kWavesPerSimd) void predict_kernel(PredictArgs<T> p) {
+// kVar = false: the mean+gradient instance (gp_predict_mean_grad_*).  Phase A is the same source, so
+// mu and deriv are bit for bit those of the full instance; phase B, the S' staging and its barriers,
+// the K_* register tile, the fragment buffers and the variance store are compiled out.
+template <typename T, int D, int NK, bool kVar = true>
+__global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerSimd)) void predict_kernel(PredictArgs<T> p) {
   typedef Real<T> R;
-  constexpr int kThreads = Geo<T>::kThreads;
-  constexpr int kRowsPerWG = Geo<T>::kRowsPerWG;
+  typedef Geo<T, kVar> G;
+  constexpr int kThreads = G::kThreads;
+  constexpr int kRowsPerWG = G::kRowsPerWG;
   typedef typename R::acc_t acc_t;
   constexpr int NB = (NK + 3) / 4;          // 16-blocks of training points
   constexpr int KL = NK - 4 * (NB - 1);     // live k-steps of the last block, 1..4
@@ -459,18 +487,18 @@ __global__ __launch_bounds__(Geo<T>::kThreads, Geo<T>::kWavesPerSimd) void predi
   constexpr int DSG = row_stride(D);        // the packed image in global memory
   constexpr int DS = xa_lds_stride<T>(D);   // its copy in LDS
   constexpr int NF = frag_count(NB);
-  constexpr int kChunk = Geo<T>::kChunk;
+  constexpr int kChunk = G::kChunk;
   constexpr int NCH = (NF + kChunk - 1) / kChunk;
 
   __shared__ __attribute__((aligned(16))) T s_xa[NP * DS];
-  __shared__ __attribute__((aligned(16))) T s_fr[2][kChunk * 64];
+  __shared__ __attribute__((aligned(16))) T s_fr[kVar ? 2 : 1][kVar ? kChunk * 64 : 1];
   __shared__ T s_sd[2 * D + 1];   // sqrt(e_d), centre c_d, b: broadcast reads, no registers
   __shared__ T s_ts[2 * D];       // scale and centre applied to the test rows: s_sd's, or (1, 0)
   // raw test rows of the wave's tile, double-buffered and private to the wave: the NEXT item's
   // rows are fetched (coalesced, 8 or 4 B per lane) while the matrix-core phase runs and are
   // picked up from here at the top of that item -- all waves of a workgroup are in step, so
   // nothing else would hide the HBM latency of those loads
-  __shared__ T s_rows[2][Geo<T>::kWaves][kTile * D];
+  __shared__ T s_rows[2][G::kWaves][kTile * D];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -528,17 +556,25 @@ __global__ __launch_bounds__(Geo<T>::kThreads, Geo<T>::kWavesPerSimd) void predi
         if (tid < 2 * D)
           s_ts[tid] = !live ? T(0) : !p.rows_prescaled ? sdp[tid] : tid < D ? T(1) : T(0);
       }
+      if constexpr (!kVar) __syncthreads();   // new rows visible (the full instance's item barrier does it there)
     }
     const T* frags = p.frags + e * p.frags_stride;
     T* o_mu = p.mu + e * p.M;
-    T* o_var = p.var + e * p.M;
     T* o_der = p.deriv + e * p.M * p.d_actual;
     const long long m = (long long)grp * kRowsPerWG + wave * kTile + ml;
     const long long mc = m < p.M ? m : p.M - 1;
 
-    // chunk 0 of S' goes L2 -> LDS by LDS-DMA now and lands under phase A
-    __syncthreads();  // previous item's readers of s_fr[0] are done; new rows visible
-    stage_chunk<T>(frags, &s_fr[0][0], wave, lane);
+    if constexpr (kVar) {
+      // chunk 0 of S' goes L2 -> LDS by LDS-DMA now and lands under phase A
+      __syncthreads();  // previous item's readers of s_fr[0] are done; new rows visible
+      stage_chunk<T, G::kWaves, kChunk>(frags, &s_fr[0][0], wave, lane);
+    } else {
+      // no barrier per item: the only LDS written per item are the wave's own test-row buffers
+      // (stash_rows below), written and read by this wave alone, in program order
+      (void)frags;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
     const T b = s_sd[2 * D];
     GP_STAMP(0);   // emulator switch, barrier, DMA issue
 
@@ -651,7 +687,7 @@ __global__ __launch_bounds__(Geo<T>::kThreads, Geo<T>::kWavesPerSimd) void predi
 #else
         k[u] = R::kExpand ? R::exp_(k[u]) : b * R::exp_(k[u]);
 #endif
-        kv[q0 + u] = k[u];
+        if constexpr (kVar) kv[q0 + u] = k[u];
       }
       // stage 3: mean and gradient sums
 #pragma unroll
@@ -696,8 +732,15 @@ __global__ __launch_bounds__(Geo<T>::kThreads, Geo<T>::kWavesPerSimd) void predi
 
     GP_STAMP(3);   // lane-group reductions, mean / gradient stores
     stash_rows(rbuf ^ 1, rregs);   // next item's rows (fetched during phase A) -> LDS
+    if constexpr (!kVar) {
+      rbuf ^= 1;
+      e = e_next;
+      grp = grp_next;
+      continue;
+    } else {
 
     // ---------------- phase B: variance on the matrix core -----------------
+    T* o_var = p.var + e * p.M;
     T vacc = T(0);
     acc_t acc;
     constexpr int kAhead = sizeof(T) == 4 ? GP_AHEAD_F32 : GP_AHEAD;
@@ -764,6 +807,7 @@ __global__ __launch_bounds__(Geo<T>::kThreads, Geo<T>::kWavesPerSimd) void predi
     e = e_next;
     grp = grp_next;
     GP_STAMP(5);   // variance reduction and store
+    }   // (kVar)
   }
 #if GP_STAMPS
   if (lane == 0 && p.dbg) {

@@ -11,8 +11,10 @@ import numpy as np
 from . import _lib
 
 
-def make_batch(gps, precision=np.float64, device=None):
-    """Pack a list of GaussianProcess objects sharing ``inputs`` into one BatchModel."""
+def make_batch(gps, precision=np.float64, device=None, do_unc=True):
+    """Pack a list of GaussianProcess objects sharing ``inputs`` into one BatchModel.  ``do_unc=False``:
+    no invQ is stacked or uploaded (2101 bands x 250^2 x 8 B = 1.05 GB); the batch then serves
+    ``predict_mean_grad`` only."""
     if not gps:
         raise ValueError("need at least one GaussianProcess")
     inputs = np.asarray(gps[0].inputs)
@@ -22,11 +24,11 @@ def make_batch(gps, precision=np.float64, device=None):
             raise ValueError("per-band emulators must share the same training inputs")
     expX = np.stack([np.exp(gp.theta) for gp in gps])
     invQt = np.stack([np.asarray(gp.invQt) for gp in gps])
-    invQ = np.stack([np.asarray(gp.invQ) for gp in gps])
+    invQ = np.stack([np.asarray(gp.invQ) for gp in gps]) if do_unc else None
     return _lib.BatchModel(_lib.default_context(device), expX, inputs, invQt, invQ, precision)
 
 
-def predict_bands(gps, testing, precision=np.float64, device=None, devices=None, predict_fn=None):
+def predict_bands(gps, testing, precision=np.float64, device=None, devices=None, predict_fn=None, do_unc=True):
     """mu (E, M), var (E, M), deriv (E, M, D) for the E emulators in ``gps``.
 
     ``devices`` (a list of device ids) shards the EMULATORS over the GPUs of a node -- BASELINE
@@ -35,12 +37,16 @@ def predict_bands(gps, testing, precision=np.float64, device=None, devices=None,
     all E inverses (1 GB for 2101 bands).  One Python thread and one context per device (the C
     ABI releases the GIL), every device's slab pipeline writing its own ``[e0:e1]`` slice of the
     three output arrays: a host gather, no collective.  ``predict_fn(device, gps_block, testing)
-    -> (mu, var, deriv)`` replaces the HIP path in the CPU tests of the sharding logic."""
+    -> (mu, var, deriv)`` replaces the HIP path in the CPU tests of the sharding logic.
+
+    ``do_unc=False``: mu (E, M) and deriv (E, M, D) only, from the mean+gradient kernels (bit for
+    bit those of ``do_unc=True``); no invQ is stacked or uploaded, and ``predict_fn`` then
+    returns ``(mu, deriv)``."""
     testing = np.asarray(testing)
     if devices is None:
-        batch = make_batch(gps, precision, device)
+        batch = make_batch(gps, precision, device, do_unc=do_unc)
         try:
-            return batch.predict(testing)
+            return batch.predict(testing) if do_unc else batch.predict_mean_grad(testing)
         finally:
             batch.close()
     import threading
@@ -49,7 +55,8 @@ def predict_bands(gps, testing, precision=np.float64, device=None, devices=None,
         raise ValueError("need at least one GaussianProcess")
     E, (M, D) = len(gps), testing.shape
     dt = np.float64 if (testing.dtype == np.float64 or np.dtype(precision) == np.float64) else np.float32
-    mu, var, deriv = np.empty((E, M), dt), np.empty((E, M), dt), np.empty((E, M, D), dt)
+    mu, deriv = np.empty((E, M), dt), np.empty((E, M, D), dt)
+    var = np.empty((E, M), dt) if do_unc else None
     blocks = multi_gpu.row_shards(E, len(devices))       # contiguous blocks of emulators
     errors = []
 
@@ -58,16 +65,22 @@ def predict_bands(gps, testing, precision=np.float64, device=None, devices=None,
             if e1 <= e0:
                 return
             if predict_fn is not None:
-                mu[e0:e1], var[e0:e1], deriv[e0:e1] = predict_fn(dev, gps[e0:e1], testing)
+                if do_unc:
+                    mu[e0:e1], var[e0:e1], deriv[e0:e1] = predict_fn(dev, gps[e0:e1], testing)
+                else:
+                    mu[e0:e1], deriv[e0:e1] = predict_fn(dev, gps[e0:e1], testing)
                 return
             ctx, lock = multi_gpu._device_context(dev)
             with lock:
                 part = gps[e0:e1]
                 batch = _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in part]), np.asarray(part[0].inputs),
                                         np.stack([np.asarray(gp.invQt) for gp in part]),
-                                        np.stack([np.asarray(gp.invQ) for gp in part]), precision)
+                                        np.stack([np.asarray(gp.invQ) for gp in part]) if do_unc else None, precision)
                 try:
-                    batch.predict(testing, out=(mu[e0:e1], var[e0:e1], deriv[e0:e1]))
+                    if do_unc:
+                        batch.predict(testing, out=(mu[e0:e1], var[e0:e1], deriv[e0:e1]))
+                    else:
+                        batch.predict_mean_grad(testing, out=(mu[e0:e1], deriv[e0:e1]))
                 finally:
                     batch.close()
         except BaseException as exc:          # surfaced to the caller below
@@ -84,7 +97,7 @@ def predict_bands(gps, testing, precision=np.float64, device=None, devices=None,
         t.join()
     if errors:
         raise errors[0]
-    return mu, var, deriv
+    return (mu, var, deriv) if do_unc else (mu, deriv)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -117,8 +117,9 @@ int gp_predict_rows_f32_h64(gp_ctx* ctx, const double* expX, const double* input
  * gp_model_create_*: pack (host side, in double) and upload the per-emulator constants the
  * reference re-uploads for every block (predict.cu:17-33): sqrt(e)-scaled training inputs
  * + invQt, and invQ folded to S' in matrix-core fragment order.  compute dtype = the
- * function's dtype.  invQ may be NULL: the model then serves gp_hessian_device only and
- * gp_predict_device on it fails with GP_ERR_INVALID. */
+ * function's dtype.  invQ may be NULL: the model then serves gp_hessian_* and
+ * gp_predict_mean_grad_* only (nothing of N x N size is packed or uploaded), and gp_predict_device
+ * / gp_predict_host on it fail with GP_ERR_INVALID. */
 int gp_model_create_f64(gp_ctx* ctx, const double* expX, const double* inputs,
                         const double* invQt, const double* invQ,
                         int n_train, int n_inputs, int theta_size, gp_model** out);
@@ -134,7 +135,8 @@ int gp_model_create_f32_h64(gp_ctx* ctx, const double* expX, const double* input
  * GaussianProcess per band, all on the SAME training inputs, each with its own theta,
  * invQ, invQt), which the reference can only run as a Python loop over predict_wrap.
  *   expX [E*theta_size], inputs [n_train*n_inputs] (shared), invQt [E*n_train],
- *   invQ [E*n_train*n_train].
+ *   invQ [E*n_train*n_train], or NULL as for gp_model_create_* (a batch for
+ *   gp_predict_mean_grad_* only).
  * gp_predict_device on such a model runs ALL emulators over the shared test rows in one
  * launch; outputs are emulator-major: mu [E][M], var [E][M], deriv [E][M*D]. */
 int gp_batch_create_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs,
@@ -172,6 +174,27 @@ int gp_predict_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
 int gp_predict_host(gp_ctx* ctx, const gp_model* model, int host_dtype, const void* testing,
                     void* result, void* error, void* deriv, int64_t n_predict, int deriv_layout,
                     int64_t max_block_rows);
+/* ---- mean and gradient without the variance --------------------------------------------
+ * The GPU form of the reference's cpu_predict(testing, do_unc=False), which returns
+ * (mu, deriv) and skips the uncertainty (gp_emulator/GaussianProcess.py:211-251); the
+ * reference's GPU path always computes the variance (:327-341).  Same kernels as
+ * gp_predict_device / gp_predict_host -- the few-row or the throughput form by the same rule,
+ * or the general-shape kernel -- in instances that issue none of the variance work, so mu and
+ * deriv are bit for bit those of the full call.  The model may have been created without invQ
+ * (single or batched).
+ * gp_predict_mean_grad_device: one launch on the context's stream (asynchronous); DEVICE
+ *   pointers of the model's dtype: testing [M*D] row-major, mu [E][M], deriv [E][M*D] in
+ *   deriv_layout. */
+int gp_predict_mean_grad_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
+                                void* d_mu, void* d_deriv, int64_t n_predict, int deriv_layout);
+/* gp_predict_mean_grad_host: gp_predict_host without the error array -- the same routes (one
+ * direct launch for small calls, page-locked caller arrays, the staged slab pipeline), the same
+ * host_dtype rules (float64 rows on a float32 model are pre-scaled while staged, outputs
+ * widened), deriv_layout, batched models and max_block_rows.  Returns when the outputs are
+ * written. */
+int gp_predict_mean_grad_host(gp_ctx* ctx, const gp_model* model, int host_dtype, const void* testing,
+                              void* result, void* deriv, int64_t n_predict, int deriv_layout,
+                              int64_t max_block_rows);
 /* number of host threads (caller included) the context uses for staging copies */
 int gp_ctx_host_threads(gp_ctx* ctx, int* n_threads);
 /* NUMA node the device is attached to (sysfs, by PCI bus id; -1 = unknown).  The context's helper
@@ -218,7 +241,8 @@ int gp_reconstruct_device(gp_ctx* ctx, int dtype, const void* d_basis, const voi
  * caller that asks for one state vector (or a few) at a time: `model` is the batch of the n_pcs
  * per-PC emulators (gp_batch_create_*), d_basis their basis functions [n_pcs][n_bands] on the
  * device (model's dtype), y host rows [n_rows][n_inputs].  Fills host arrays fwd [n_rows][n_bands]
- * and, unless jac is NULL, jac [n_rows][n_inputs][n_bands]: rows up, batched predict,
+ * and, unless jac is NULL, jac [n_rows][n_inputs][n_bands]: rows up, batched mean+gradient predict
+ * (the variance is not needed: the kernels of gp_predict_mean_grad_device),
  * reconstruction and Jacobian on the device, results down (one copy when jac == fwd +
  * n_rows * n_bands, i.e. the two arrays are laid out back to back), one synchronisation.  At most 1 GiB
  * of results per call (GP_ERR_UNSUPPORTED beyond: split the rows). */
