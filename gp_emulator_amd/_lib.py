@@ -61,6 +61,8 @@ SIGNATURES = {
     "gp_kernel_ksteps": (c_int, [c_int, c_int, ctypes.POINTER(c_int)]),
     "gp_hessian_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_hessian_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
+    "gp_hessian_weighted_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
+    "gp_hessian_weighted_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_hessian_f64": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_hessian_f32": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_reconstruct_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
@@ -560,7 +562,8 @@ class BatchModel(Model):
     expX (E, D+2), inputs (N, D), invQt (E, N), invQ (E, N, N) or None (a batch for
     ``predict_mean_grad`` only: no inverse is packed or uploaded).
     ``predict`` (inherited: the slab pipeline) returns mu (E, M), var (E, M), deriv (E, M, D);
-    ``predict_mean_grad`` mu (E, M), deriv (E, M, D).
+    ``predict_mean_grad`` mu (E, M), deriv (E, M, D); ``hessian`` (E, M, D, D) and
+    ``hessian_weighted`` the weighted sum over the emulators (M, D, D).
     """
 
     def __init__(self, ctx, expX, inputs, invQt, invQ, precision=np.float64):
@@ -585,8 +588,62 @@ class BatchModel(Model):
                  self.n_train, self.n_inputs, expX.shape[1], ctypes.byref(h)), "gp_batch_create")
         self.h = h
 
+    def hessian_device(self, d_testing, d_hess, n_predict):
+        """Asynchronous Hessian launch for the whole batch; device pointers, hess is
+        (E, n_predict, D, D): emulator e bit for bit what a ``Model`` of it gives on the same rows."""
+        Model.hessian_device(self, d_testing, d_hess, n_predict)
+
+    def _hessian_rows(self, testing):
+        """The rows as the library takes them, their dtype and whether the float64-rows-on-a-float32-model
+        entry point serves the call (rules of ``Model.hessian``)."""
+        testing = np.asarray(testing)
+        h64 = testing.dtype == np.float64 and self.dtype != np.float64
+        hdt = np.dtype(np.float64) if h64 else self.dtype
+        testing = np.ascontiguousarray(testing, dtype=hdt)
+        if testing.ndim != 2 or testing.shape[1] != self.n_inputs:
+            raise ValueError("testing must be (n_predict, %d)" % self.n_inputs)
+        return testing, hdt, h64
+
     def hessian(self, testing, out=None):
-        raise GpuPredictError("hessian is per emulator; build a Model for the emulator wanted")
+        """(E, M, D, D) Hessians of the E means for host rows (``gp_hessian_host`` on the batch: one
+        launch per slab for all emulators).  dtype rules of ``Model.hessian``."""
+        testing, hdt, h64 = self._hessian_rows(testing)
+        M, D = testing.shape
+        shape = (self.n_emulators, M, D, D)
+        hess = self.ctx.out_pool.take(shape, hdt) if out is None else out
+        if (not isinstance(hess, np.ndarray) or hess.shape != shape or hess.dtype != hdt
+                or not hess.flags["C_CONTIGUOUS"] or not hess.flags["WRITEABLE"]):
+            raise ValueError("out must be a writeable C-contiguous %s %s array" % (shape, hdt))
+        if M:
+            fn = self.ctx.lib.gp_hessian_host_h64 if h64 else self.ctx.lib.gp_hessian_host
+            check(fn(self.ctx.h, self.h, _ptr(testing), _ptr(hess), M), "gp_hessian_host")
+        return hess
+
+    def hessian_weighted_device(self, d_testing, d_weights, d_out, n_predict):
+        """Asynchronous ``out[m] = sum_e weights[e][m] * H_e[m]``; device pointers of the model's dtype,
+        weights (E, n_predict), out (n_predict, D, D)."""
+        check(self.ctx.lib.gp_hessian_weighted_device(self.ctx.h, self.h, d_testing, d_weights, d_out,
+                                                      int(n_predict)), "gp_hessian_weighted_device")
+
+    def hessian_weighted(self, testing, weights, out=None):
+        """(M, D, D): ``sum_e weights[e, m] * H_e[m]`` for host rows and host weights (E, M), summed on
+        the device in ascending e (``gp_hessian_weighted_host``); the (E, M, D, D) intermediate never
+        exists beyond a bounded device scratch.  dtype rules of ``Model.hessian``."""
+        testing, hdt, _ = self._hessian_rows(testing)
+        M, D = testing.shape
+        weights = np.ascontiguousarray(weights, dtype=hdt)
+        if weights.shape != (self.n_emulators, M):
+            raise ValueError("weights must be (%d, %d)" % (self.n_emulators, M))
+        shape = (M, D, D)
+        res = self.ctx.out_pool.take(shape, hdt) if out is None else out
+        if (not isinstance(res, np.ndarray) or res.shape != shape or res.dtype != hdt
+                or not res.flags["C_CONTIGUOUS"] or not res.flags["WRITEABLE"]):
+            raise ValueError("out must be a writeable C-contiguous %s %s array" % (shape, hdt))
+        if M:
+            check(self.ctx.lib.gp_hessian_weighted_host(
+                self.ctx.h, self.h, GP_F64 if hdt == np.float64 else GP_F32, _ptr(testing), _ptr(weights),
+                _ptr(res), M), "gp_hessian_weighted_host")
+        return res
 
 
 def pack_model(expX, inputs, invQt, invQ, precision=np.float64):

@@ -26,6 +26,7 @@
 #include "gp_generic_kernel.hpp"
 #include "gp_hessian_kernel.hpp"
 #include "gp_hessian_win_kernel.hpp"
+#include "gp_hessian_combine_kernel.hpp"
 #include "gp_host_pool.hpp"
 #include "gp_predict_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
@@ -46,6 +47,8 @@ GP_FOR_EACH_KERNEL_NB(GP_DECL)
 #undef GP_DECL
 hipError_t launch_hessian_f32(int, const HessianArgs<float>&, int, hipStream_t);
 hipError_t launch_hessian_f64(int, const HessianArgs<double>&, int, hipStream_t);
+hipError_t launch_hess_combine_f32(const HessCombineArgs<float>&, hipStream_t);
+hipError_t launch_hess_combine_f64(const HessCombineArgs<double>&, hipStream_t);
 #define GP_DECL(nk)                                                                         \
   hipError_t launch_predict_f32_##nk(int, const PredictArgs<float>&, int, hipStream_t);     \
   hipError_t launch_predict_f64_##nk(int, const PredictArgs<double>&, int, hipStream_t);    \
@@ -107,10 +110,12 @@ struct gp_model {
   std::vector<double> scale_host, centre_host;
   // Hessian on the matrix core (gp_hessian_win_kernel.hpp): the constant products
   // x''_id x''_id2 in fragment order, built on the first Hessian call from a host copy of the
-  // scaled rows (double, [16 * kernel_nb slots][kernel_d])
+  // scaled rows (double, [16 * kernel_nb slots][kernel_d]).  A batch keeps no host copy (47 MB for 2101 bands):
+  // its operands are packed emulator by emulator from the packed rows on the device, which hold the same values.
   std::vector<double> xs_host;
   std::mutex h_mutex;
-  void* d_pfrags;
+  void* d_pfrags;                          // [n_emulators][pfrags_stride]
+  long long pfrags_stride;
 };
 
 // Host-pointer path (predict_host): slabs of the caller's arrays flow through kPipeSlots slots,
@@ -496,6 +501,7 @@ static int model_create(gp_ctx* ctx, int E, const TH* expX, const TH* inputs, co
   m->sd_stride = sd_len;
   m->d_xa = m->d_frags = m->d_sd = nullptr;
   m->d_pfrags = nullptr;
+  m->pfrags_stride = 0;
   hipError_t e = hipMalloc(&m->d_xa, sizeof(T) * xa_len * E);
   if (e == hipSuccess && invQ) e = hipMalloc(&m->d_frags, sizeof(T) * fr_len * E);
   if (e == hipSuccess) e = hipMalloc(&m->d_sd, sizeof(T) * sd_len * E);
@@ -659,7 +665,7 @@ hipError_t launch_hessm<double>(int knb, int kd, const gpk::HessMfmaArgs<double>
 }
 
 static bool hessian_on_matrix_core(const gp_model* m) {
-  if (m->kernel_nb <= 0 || m->n_emulators != 1 || m->xs_host.empty()) return false;
+  if (m->kernel_nb <= 0 || (m->n_emulators == 1 && m->xs_host.empty())) return false;
   if (const char* ev = getenv("GP_HESS_VALU"))      // A/B switch: force the VALU kernel
     if (atoi(ev) != 0) return false;
   return m->kernel_d == 8 || m->kernel_d == 10 || m->kernel_d == 11 || m->kernel_d == 12 || m->kernel_d == 16;
@@ -670,67 +676,102 @@ static bool hessian_on_matrix_core(const gp_model* m) {
 // of (d, d2); fragment (block c, training block I, k-step s) lane l = the product for training
 // point 16 I + own(s, l >> 4) and the block's element that MFMA output row (l & 15) stands for.
 // Fragments are packed k-step-major (hess_win_frag_index), padded to whole chunks of WGeo::kChunk.
+// A batch has one operand per emulator (the products depend on its length scales), pfrags_stride elements
+// apart: hess_frag_count_padded(D, NB, 32) * 64 * sizeof(T) each = 192 KiB at N = 250, kernel D = 10 or 11, fp64
+// (2.3 MB for 12 principal components, 413 MB for 2101 bands).  They are packed and uploaded emulator by
+// emulator through one bounded host buffer; the rounded x'' of emulator e are read back from its packed rows.
 template <typename T>
 static int ensure_hess_frags(gp_ctx* ctx, gp_model* m) {
   std::lock_guard<std::mutex> lock(m->h_mutex);
   if (m->d_pfrags) return GP_OK;
-  const int kd = m->kernel_d, knb = m->kernel_nb, N = m->n_train;
+  const int kd = m->kernel_d, knb = m->kernel_nb, N = m->n_train, E = m->n_emulators;
   const int nblk = gpk::hess_blocks(kd);
   const size_t n = (size_t)gpk::hess_frag_count_padded(kd, knb, gpk::WGeo::kChunk) * 64;
-  std::vector<T> fr(n, T(0));
-  for (int c = 0; c < nblk; ++c)
-    for (int I = 0; I < knb; ++I)
-      for (int s = 0; s < 4; ++s) {
-        T* f = fr.data() + (size_t)gpk::hess_win_frag_index(c, I, s, nblk) * 64;
-        for (int l = 0; l < 64; ++l) {
-          const int i = gpk::own_index<T>(I, s, l >> 4);   // slot; padding slots hold zero rows
-          const int q = l & 15;             // MFMA output row = accumulator r of lane group g
-          const int d = 4 * gpk::hess_block_bi(c) + gpk::hess_row_r<T>(q);
-          const int d2 = 4 * gpk::hess_block_bj(c) + gpk::hess_row_g<T>(q);
-          if (gpk::slot_point<T>(i) >= N) continue;
-          if (gpk::hess_block_bi(c) == gpk::hess_block_bj(c)) {
-            // the kernel takes G_n = sum w x''_n and s = sum w from the unused mirror slots of the
-            // diagonal blocks (gp_hessian_win_kernel.hpp, hess_gslot_*)
-            const int n = gpk::hess_gslot_of(gpk::hess_block_bi(c), gpk::hess_row_r<T>(q), gpk::hess_row_g<T>(q));
-            if (n >= 0) {
-              f[l] = n < kd ? (T)m->xs_host[(size_t)i * kd + n] : n == kd ? T(1) : T(0);
-              continue;
-            }
-          }
-          if (d >= kd || d2 >= kd) continue;
-          f[l] = (T)(m->xs_host[(size_t)i * kd + d] * m->xs_host[(size_t)i * kd + d2]);
-        }
-      }
+  const int DSk = row_stride_of(kd), NPk = rows_padded(N, knb);
   void* dp = nullptr;
-  HIP_TRY(hipMalloc(&dp, sizeof(T) * n));
-  hipError_t e = hipMemcpy(dp, fr.data(), sizeof(T) * n, hipMemcpyHostToDevice);
+  HIP_TRY(hipMalloc(&dp, sizeof(T) * n * E));
+  std::vector<T> fr(n), xa;
+  std::vector<double> xs_dev;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < E && e == hipSuccess; ++k) {
+    const double* xs = m->xs_host.data();
+    if (E > 1) {
+      // (the stream that uploaded the rows is idle since model_create; a blocking copy orders behind it anyway)
+      xa.resize((size_t)NPk * DSk);
+      e = hipMemcpy(xa.data(), (const T*)m->d_xa + (size_t)k * m->xa_stride, sizeof(T) * xa.size(), hipMemcpyDeviceToHost);
+      if (e != hipSuccess) break;
+      xs_dev.resize((size_t)NPk * kd);
+      for (int i = 0; i < NPk; ++i)
+        for (int d = 0; d < kd; ++d) xs_dev[(size_t)i * kd + d] = (double)xa[(size_t)i * DSk + d];
+      xs = xs_dev.data();
+    }
+    std::fill(fr.begin(), fr.end(), T(0));
+    for (int c = 0; c < nblk; ++c)
+      for (int I = 0; I < knb; ++I)
+        for (int s = 0; s < 4; ++s) {
+          T* f = fr.data() + (size_t)gpk::hess_win_frag_index(c, I, s, nblk) * 64;
+          for (int l = 0; l < 64; ++l) {
+            const int i = gpk::own_index<T>(I, s, l >> 4);   // slot; padding slots hold zero rows
+            const int q = l & 15;             // MFMA output row = accumulator r of lane group g
+            const int d = 4 * gpk::hess_block_bi(c) + gpk::hess_row_r<T>(q);
+            const int d2 = 4 * gpk::hess_block_bj(c) + gpk::hess_row_g<T>(q);
+            if (gpk::slot_point<T>(i) >= N) continue;
+            if (gpk::hess_block_bi(c) == gpk::hess_block_bj(c)) {
+              // the kernel takes G_n = sum w x''_n and s = sum w from the unused mirror slots of the
+              // diagonal blocks (gp_hessian_win_kernel.hpp, hess_gslot_*)
+              const int gn = gpk::hess_gslot_of(gpk::hess_block_bi(c), gpk::hess_row_r<T>(q), gpk::hess_row_g<T>(q));
+              if (gn >= 0) {
+                f[l] = gn < kd ? (T)xs[(size_t)i * kd + gn] : gn == kd ? T(1) : T(0);
+                continue;
+              }
+            }
+            if (d >= kd || d2 >= kd) continue;
+            f[l] = (T)(xs[(size_t)i * kd + d] * xs[(size_t)i * kd + d2]);
+          }
+        }
+    e = hipMemcpy((T*)dp + (size_t)k * n, fr.data(), sizeof(T) * n, hipMemcpyHostToDevice);
+  }
   if (e != hipSuccess) {
     (void)hipFree(dp);
     return fail(GP_ERR_HIP, "hessian operand upload: %s", hipGetErrorString(e));
   }
+  m->pfrags_stride = (long long)n;
   m->d_pfrags = dp;
   return GP_OK;
 }
 
+// Emulators [e0, e0 + ne) of the model (ne < 0: all of them) on the rows given; emulator e0 + k writes
+// d_hess + k * hess_stride (hess_stride < 0: M * D * D, i.e. d_hess is [ne][M][D][D]).
 template <typename T>
 static int hessian_device(gp_ctx* ctx, const gp_model* m, const void* d_testing, void* d_hess, int64_t M,
-                          hipStream_t stream = nullptr) {
+                          hipStream_t stream = nullptr, long long hess_stride = -1, int e0 = 0, int ne = -1) {
   if (!stream) stream = ctx->stream;
   if (m->n_inputs > GP_MAX_KERNEL_D)
     return fail(GP_ERR_UNSUPPORTED, "hessian kernels are compiled for n_inputs <= %d", GP_MAX_KERNEL_D);
+  if (ne < 0) ne = m->n_emulators - e0;
+  if (e0 < 0 || ne < 1 || e0 + ne > m->n_emulators) return fail(GP_ERR_INVALID, "bad emulator range");
+  if (hess_stride < 0) hess_stride = (long long)M * m->n_inputs * m->n_inputs;
+  // batched items are numbered in 32 bits (with room for the tickets drawn beyond the end)
+  if (ne > 1 && (M + 63) / 64 * (int64_t)ne > (int64_t)0x7fffffff - 4 * 1024 * 1024)
+    return fail(GP_ERR_INVALID, "n_predict x n_emulators too large for one launch: split the rows");
   if (hessian_on_matrix_core(m)) {
     int rc = ensure_hess_frags<T>(ctx, const_cast<gp_model*>(m));
     if (rc) return rc;
     gpk::HessMfmaArgs<T> h;
-    h.xa = (const T*)m->d_xa;
-    h.pfrags = (const T*)m->d_pfrags;
-    h.sd = (const T*)m->d_sd;
+    h.xa = (const T*)m->d_xa + (size_t)e0 * m->xa_stride;
+    h.pfrags = (const T*)m->d_pfrags + (size_t)e0 * m->pfrags_stride;
+    h.sd = (const T*)m->d_sd + (size_t)e0 * m->sd_stride;
     h.testing = (const T*)d_testing;
     h.hess = (T*)d_hess;
     h.M = M;
     h.d_actual = m->n_inputs;
     h.dbg = (unsigned long long*)ctx->dbg;
     h.n_ksteps = (m->n_train + 3) / 4;
+    h.n_emulators = ne;
+    h.xa_stride = m->xa_stride;
+    h.sd_stride = m->sd_stride;
+    h.pfrags_stride = m->pfrags_stride;
+    h.hess_stride = hess_stride;
     // items drawn from a counter (see the kernel)
     h.tickets = h.tickets2 = nullptr;
     if (M < ((int64_t)1 << 36)) {      // (two launches per call at most: whole groups, rest)
@@ -738,23 +779,27 @@ static int hessian_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
       h.tickets = ctx->tickets + 4 * (slot % kTicketSlots);            // (4 words per launch: see the kernel)
       h.tickets2 = ctx->tickets + 4 * ((slot + 1) % kTicketSlots);
     }
-    // (the launcher sizes each launch: min(grid, its 64-row groups))
+    // (the launcher sizes each launch: min(grid, its items))
     const int grid = ctx->compute_units * gpk::win_wg_per_cu<T>();
     hipError_t e = launch_hessm<T>(m->kernel_nb, m->kernel_d, h, grid, stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "hessian kernel launch: %s", hipGetErrorString(e));
     return GP_OK;
   }
   gpk::HessianArgs<T> a;
-  a.xa = (const T*)m->d_xa;
-  a.sd = (const T*)m->d_sd;
+  a.xa = (const T*)m->d_xa + (size_t)e0 * m->xa_stride;
+  a.sd = (const T*)m->d_sd + (size_t)e0 * m->sd_stride;
   a.testing = (const T*)d_testing;
   a.hess = (T*)d_hess;
   a.M = M;
   a.d_actual = m->n_inputs;
   a.nb = (m->n_train + 15) / 16;     // the loop over training points is a run-time loop
+  a.n_emulators = ne;
+  a.xa_stride = m->xa_stride;
+  a.sd_stride = m->sd_stride;
+  a.hess_stride = hess_stride;
   if (sizeof(T) * (16 * (size_t)a.nb * gpk::row_stride(m->kernel_d) + 2 * m->kernel_d) > 160 * 1024)
     return fail(GP_ERR_UNSUPPORTED, "training set too large for the hessian kernel's LDS image");
-  const int64_t groups = (M + gpk::hkRowsPerWG - 1) / gpk::hkRowsPerWG;
+  const int64_t groups = (M + gpk::hkRowsPerWG - 1) / gpk::hkRowsPerWG * ne;
   int64_t grid = (int64_t)ctx->compute_units * 2;
   if (grid > groups) grid = groups;
   hipError_t e = launch_hessian<T>(m->kernel_d, a, (int)grid, stream);
@@ -1243,13 +1288,15 @@ static int predict_host(gp_ctx* ctx, const gp_model* m, const TH* testing, TH* r
   return run_slab_pipeline<T>(ctx, M, slab, (size_t)D, out_row, copy_in, launch, copy_out);
 }
 
-// Hessian for host arrays: (M, D, D) out, same pipeline (2 KiB per row of output at D = 16).
+// Hessian for host arrays: (M, D, D) out -- (E, M, D, D) for a batch -- same pipeline (2 KiB per row of output
+// at D = 16).  A batch's staged slab is [E][n][D][D]: emulator e's rows land at hess + e * M * D * D + s0 * D * D.
 template <typename T, typename TH = T>
 static int hessian_host_model(gp_ctx* ctx, const gp_model* m, const TH* testing, TH* hess, int64_t M) {
-  const int D = m->n_inputs;
+  const int D = m->n_inputs, E = m->n_emulators;
   if (M == 0) return GP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  const size_t out_row = (size_t)D * D;
+  const size_t dd = (size_t)D * D;
+  const size_t out_row = (size_t)E * dd;
   if (sizeof(T) == sizeof(TH) && (size_t)M * out_row * sizeof(T) <= ((size_t)8 << 20)) {      // small call: direct copies (see predict_host)
     const size_t n_in = (size_t)M * D, n_out = (size_t)M * out_row;
     int rc = ensure_scratch(ctx, (n_in + n_out) * sizeof(T));
@@ -1274,10 +1321,146 @@ static int hessian_host_model(gp_ctx* ctx, const gp_model* m, const TH* testing,
   auto launch = [=](T* d_in, T* d_out, int64_t n, hipStream_t st) {
     return hessian_device<T>(ctx, m, d_in, d_out, n, st);
   };
-  auto copy_out = [=](const T* o, int64_t s0, int64_t, int64_t lo, int64_t hi) {
-    convert_range(hess + (size_t)s0 * out_row, o, (size_t)lo * out_row, (size_t)hi * out_row);
+  auto copy_out = [=](const T* o, int64_t s0, int64_t n, int64_t lo, int64_t hi) {
+    // (batched emulators: a task is a share of the emulators with all the slab's rows, as in predict_host)
+    int e_lo = 0, e_hi = 1;
+    if (E > 1) {
+      e_lo = (int)((int64_t)E * lo / n);
+      e_hi = (int)((int64_t)E * hi / n);
+      lo = 0;
+      hi = n;
+    }
+    for (int e = e_lo; e < e_hi; ++e)
+      convert_range(hess + ((size_t)e * M + s0) * dd, o + (size_t)e * n * dd, (size_t)lo * dd, (size_t)hi * dd);
   };
   return run_slab_pipeline<T>(ctx, M, slab, (size_t)D, out_row, copy_in, launch, copy_out);
+}
+
+// ---- weighted sum over the emulators: out[m] = sum_e w[e][m] H_e[m] ---------------------------------------
+// Rows are cut into slabs; a slab's per-emulator matrices go to device scratch (the batched kernels above, one
+// launch, two on the matrix core) and gp_hessian_combine_kernel.hpp folds them over the emulators.  The scratch
+// is bounded by a fixed budget whatever E and M are (GP_HESS_WEIGHTED_MB, default 256 MiB): a slab is as many
+// whole 64-row groups as fit, and when even 64 rows of every emulator do not (2101 bands at D = 16), the emulators
+// are taken in chunks as well and the combine kernel continues its chain from `out`.  The chain is one fma per
+// emulator in ascending order from 0 however the call is cut, so two calls are bit-identical.
+static size_t weighted_budget_bytes() {      // (read per call: the tests run two budgets in one process)
+  const char* ev = getenv("GP_HESS_WEIGHTED_MB");
+  const long v = ev ? atol(ev) : 256;
+  return (size_t)(v < 1 ? 1 : v) << 20;
+}
+template <typename T>
+static void weighted_cut(const gp_model* m, int64_t M, int64_t* slab, int* e_chunk) {
+  const size_t row = (size_t)m->n_inputs * m->n_inputs * sizeof(T);
+  const size_t budget = weighted_budget_bytes();
+  int ec = m->n_emulators;
+  if ((size_t)ec * 64 * row > budget) ec = (int)(budget / (64 * row));
+  if (ec < 1) ec = 1;
+  int64_t r = (int64_t)(budget / ((size_t)ec * row)) / 64 * 64;
+  if (r < 64) r = 64;
+  if (r > M) r = M;
+  *slab = r;
+  *e_chunk = ec;
+}
+template <typename T>
+static hipError_t launch_hess_combine(const gpk::HessCombineArgs<T>& a, hipStream_t s) {
+  if constexpr (sizeof(T) == 8) return gpk::launch_hess_combine_f64(a, s);
+  else return gpk::launch_hess_combine_f32(a, s);
+}
+// one slab: n rows at d_testing, weights element (e, row) at d_w[e * w_stride + row], n x D x D out;
+// d_slab holds e_chunk x n matrices
+template <typename T>
+static int hessian_weighted_slab(gp_ctx* ctx, const gp_model* m, const T* d_testing, const T* d_w, long long w_stride,
+                                 T* d_out, int64_t n, T* d_slab, int e_chunk, hipStream_t st) {
+  const long long dd = (long long)m->n_inputs * m->n_inputs;
+  for (int e0 = 0; e0 < m->n_emulators; e0 += e_chunk) {
+    const int ne = e0 + e_chunk <= m->n_emulators ? e_chunk : m->n_emulators - e0;
+    int rc = hessian_device<T>(ctx, m, d_testing, d_slab, n, st, n * dd, e0, ne);
+    if (rc) return rc;
+    gpk::HessCombineArgs<T> c;
+    c.hess = d_slab;
+    c.weights = d_w + (long long)e0 * w_stride;
+    c.out = d_out;
+    c.rows = n;
+    c.dd = dd;
+    c.hess_stride = n * dd;
+    c.w_stride = w_stride;
+    c.n_emulators = ne;
+    c.accumulate = e0 > 0 ? 1 : 0;
+    hipError_t e = launch_hess_combine<T>(c, st);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "hessian combine kernel launch: %s", hipGetErrorString(e));
+  }
+  return GP_OK;
+}
+
+template <typename T>
+static int hessian_weighted_device(gp_ctx* ctx, const gp_model* m, const void* d_testing, const void* d_weights,
+                                   void* d_out, int64_t M) {
+  const int D = m->n_inputs;
+  int64_t slab;
+  int ec;
+  weighted_cut<T>(m, M, &slab, &ec);
+  int rc = ensure_scratch(ctx, (size_t)ec * slab * D * D * sizeof(T));
+  if (rc) return rc;
+  for (int64_t s0 = 0; s0 < M; s0 += slab) {
+    const int64_t n = s0 + slab <= M ? slab : M - s0;
+    rc = hessian_weighted_slab<T>(ctx, m, (const T*)d_testing + s0 * D, (const T*)d_weights + s0, M,
+                                  (T*)d_out + s0 * D * D, n, (T*)ctx->scratch, ec, ctx->stream);
+    if (rc) return rc;
+  }
+  return GP_OK;
+}
+
+// Host arrays: rows (M, D), weights (E, M), out (M, D, D).  One stream, slab after slab: a slab's rows and
+// weights go up, its sum comes down (the (E, n, D, D) intermediate never leaves the device).  Arrays of another
+// type than the model's (float64 on a float32 model) are converted through a host buffer per slab.
+template <typename T, typename TH>
+static int hessian_weighted_host(gp_ctx* ctx, const gp_model* m, const TH* testing, const TH* weights, TH* out, int64_t M) {
+  const int D = m->n_inputs, E = m->n_emulators;
+  const size_t dd = (size_t)D * D;
+  HIP_TRY(hipSetDevice(ctx->device));
+  int64_t slab;
+  int ec;
+  weighted_cut<T>(m, M, &slab, &ec);
+  const size_t n_in = (size_t)slab * D, n_w = (size_t)slab * E, n_out = (size_t)slab * dd;
+  int rc = ensure_scratch(ctx, (n_in + n_w + n_out + (size_t)ec * slab * dd) * sizeof(T));
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  T* d_in = (T*)ctx->scratch;
+  T* d_w = d_in + n_in;
+  T* d_o = d_w + n_w;
+  T* d_slab = d_o + n_out;
+  constexpr bool conv = sizeof(T) != sizeof(TH);
+  std::vector<T> h_in, h_w, h_out;
+  if (conv) { h_in.resize(n_in); h_w.resize(n_w); h_out.resize(n_out); }
+  hipError_t e = hipSuccess;
+  for (int64_t s0 = 0; s0 < M && e == hipSuccess && rc == GP_OK; s0 += slab) {
+    const int64_t n = s0 + slab <= M ? slab : M - s0;
+    if (conv) {
+      convert_range(h_in.data(), testing + (size_t)s0 * D, 0, (size_t)n * D);
+      for (int k = 0; k < E; ++k) convert_range(h_w.data() + (size_t)k * n, weights + (size_t)k * M + s0, 0, (size_t)n);
+      e = hipMemcpyAsync(d_in, h_in.data(), sizeof(T) * n * D, hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_w, h_w.data(), sizeof(T) * n * E, hipMemcpyHostToDevice, st);
+    } else {
+      e = hipMemcpyAsync(d_in, testing + (size_t)s0 * D, sizeof(T) * n * D, hipMemcpyHostToDevice, st);
+      if (e == hipSuccess)
+        e = hipMemcpy2DAsync(d_w, sizeof(T) * n, weights + s0, sizeof(T) * M, sizeof(T) * n, E, hipMemcpyHostToDevice, st);
+    }
+    if (e != hipSuccess) break;
+    rc = hessian_weighted_slab<T>(ctx, m, d_in, d_w, n, d_o, n, d_slab, ec, st);
+    if (rc) break;
+    if (conv) {
+      e = hipMemcpyAsync(h_out.data(), d_o, sizeof(T) * n * dd, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);      // the host buffers are reused by the next slab
+      if (e == hipSuccess) convert_range(out + (size_t)s0 * dd, h_out.data(), 0, (size_t)n * dd);
+    } else {
+      e = hipMemcpyAsync(out + (size_t)s0 * dd, d_o, sizeof(T) * n * dd, hipMemcpyDeviceToHost, st);
+    }
+  }
+  const hipError_t es = hipStreamSynchronize(st);       // whatever happened, leave the stream idle
+  if (rc) return rc;
+  if (e != hipSuccess || es != hipSuccess)
+    return fail(GP_ERR_HIP, "weighted hessian: %s", hipGetErrorString(e != hipSuccess ? e : es));
+  return GP_OK;
 }
 
 // ---- the context's model cache (see gp_cached_model) ---------------------------------------
@@ -1615,7 +1798,6 @@ int gp_hessian_host(gp_ctx* ctx, const gp_model* model, const void* testing, voi
   if (n_predict == 0) return GP_OK;
   if (!testing || !hess) return fail(GP_ERR_INVALID, "null pointer");
   if (model->device != ctx->device) return fail(GP_ERR_INVALID, "model lives on device %d, context on %d", model->device, ctx->device);
-  if (model->n_emulators != 1) return fail(GP_ERR_INVALID, "hessian is per emulator: batch of %d given", model->n_emulators);
   if (model->n_inputs > GP_MAX_KERNEL_D)
     return fail(GP_ERR_UNSUPPORTED, "hessian kernels are compiled for n_inputs <= %d", GP_MAX_KERNEL_D);
   if (model->dtype == GP_F64) return guarded([&] { return hessian_host_model<double>(ctx, model, (const double*)testing, (double*)hess, n_predict); });
@@ -1628,7 +1810,6 @@ int gp_hessian_host_h64(gp_ctx* ctx, const gp_model* model, const double* testin
   if (n_predict == 0) return GP_OK;
   if (!testing || !hess) return fail(GP_ERR_INVALID, "null pointer");
   if (model->device != ctx->device) return fail(GP_ERR_INVALID, "model lives on device %d, context on %d", model->device, ctx->device);
-  if (model->n_emulators != 1) return fail(GP_ERR_INVALID, "hessian is per emulator: batch of %d given", model->n_emulators);
   if (model->n_inputs > GP_MAX_KERNEL_D)
     return fail(GP_ERR_UNSUPPORTED, "hessian kernels are compiled for n_inputs <= %d", GP_MAX_KERNEL_D);
   if (model->dtype == GP_F64) return guarded([&] { return hessian_host_model<double>(ctx, model, testing, hess, n_predict); });
@@ -1667,10 +1848,39 @@ int gp_hessian_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
   if (n_predict == 0) return GP_OK;
   if (!d_testing || !d_hess) return fail(GP_ERR_INVALID, "null device pointer");
   if (model->device != ctx->device) return fail(GP_ERR_INVALID, "model lives on device %d, context on %d", model->device, ctx->device);
-  if (model->n_emulators != 1) return fail(GP_ERR_INVALID, "hessian is per emulator: batch of %d given", model->n_emulators);
   HIP_TRY(hipSetDevice(ctx->device));
   if (model->dtype == GP_F64) return guarded([&] { return hessian_device<double>(ctx, model, d_testing, d_hess, n_predict); });
   return guarded([&] { return hessian_device<float>(ctx, model, d_testing, d_hess, n_predict); });
+}
+int gp_hessian_weighted_device(gp_ctx* ctx, const gp_model* model, const void* d_testing, const void* d_weights,
+                               void* d_out, int64_t n_predict) {
+  if (!ctx || !model) return fail(GP_ERR_INVALID, "null context or model");
+  if (n_predict < 0) return fail(GP_ERR_INVALID, "n_predict < 0");
+  if (n_predict == 0) return GP_OK;
+  if (!d_testing || !d_weights || !d_out) return fail(GP_ERR_INVALID, "null device pointer");
+  if (model->device != ctx->device) return fail(GP_ERR_INVALID, "model lives on device %d, context on %d", model->device, ctx->device);
+  if (model->n_inputs > GP_MAX_KERNEL_D)
+    return fail(GP_ERR_UNSUPPORTED, "hessian kernels are compiled for n_inputs <= %d", GP_MAX_KERNEL_D);
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (model->dtype == GP_F64) return guarded([&] { return hessian_weighted_device<double>(ctx, model, d_testing, d_weights, d_out, n_predict); });
+  return guarded([&] { return hessian_weighted_device<float>(ctx, model, d_testing, d_weights, d_out, n_predict); });
+}
+int gp_hessian_weighted_host(gp_ctx* ctx, const gp_model* model, int host_dtype, const void* testing,
+                             const void* weights, void* out, int64_t n_predict) {
+  if (!ctx || !model) return fail(GP_ERR_INVALID, "null context or model");
+  if (n_predict < 0) return fail(GP_ERR_INVALID, "n_predict < 0");
+  if (n_predict == 0) return GP_OK;
+  if (!testing || !weights || !out) return fail(GP_ERR_INVALID, "null pointer");
+  if (model->device != ctx->device) return fail(GP_ERR_INVALID, "model lives on device %d, context on %d", model->device, ctx->device);
+  if (model->n_inputs > GP_MAX_KERNEL_D)
+    return fail(GP_ERR_UNSUPPORTED, "hessian kernels are compiled for n_inputs <= %d", GP_MAX_KERNEL_D);
+  if (model->dtype == GP_F64 && host_dtype == GP_F64)
+    return guarded([&] { return hessian_weighted_host<double, double>(ctx, model, (const double*)testing, (const double*)weights, (double*)out, n_predict); });
+  if (model->dtype == GP_F32 && host_dtype == GP_F32)
+    return guarded([&] { return hessian_weighted_host<float, float>(ctx, model, (const float*)testing, (const float*)weights, (float*)out, n_predict); });
+  if (model->dtype == GP_F32 && host_dtype == GP_F64)
+    return guarded([&] { return hessian_weighted_host<float, double>(ctx, model, (const double*)testing, (const double*)weights, (double*)out, n_predict); });
+  return fail(GP_ERR_INVALID, "host arrays must have the model's dtype, or be float64 for a float32 model");
 }
 int gp_hessian_f64(gp_ctx* ctx, const double* expX, const double* inputs, const double* invQt,
                    const double* testing, double* hess, int64_t n_predict, int n_train,

@@ -36,6 +36,10 @@ struct HessianArgs {
   long long M;
   int d_actual;
   int nb;             // 16-row blocks of training points
+  // Batched emulators (the BATCH instance; n_emulators == 1 runs the plain one, which never reads these):
+  // emulator e has its constants at xa + e * xa_stride, sd + e * sd_stride and writes hess + e * hess_stride
+  int n_emulators;
+  long long xa_stride, sd_stride, hess_stride;
 };
 
 // Hessian kernel geometry: 4 waves (one per SIMD) so that the D = 16 instance, which needs
@@ -144,7 +148,10 @@ __device__ __forceinline__ void hessian_pass(const T* s_xa, const T* s_sd, const
   }
 }
 
-template <typename T, int D>
+// BATCH: work items are (emulator, group of 64 test rows), emulator-major, dealt round-robin as in
+// predict_kernel; a workgroup whose next item belongs to another emulator reloads the LDS image between two
+// workgroup barriers.  An item's arithmetic is the plain instance's on that emulator's constants.
+template <typename T, int D, bool BATCH = false>
 __global__ __launch_bounds__(hkThreads, 2) void hessian_kernel(HessianArgs<T> p) {
   typedef Real<T> R;
   constexpr int DS = row_stride(D);
@@ -161,23 +168,48 @@ __global__ __launch_bounds__(hkThreads, 2) void hessian_kernel(HessianArgs<T> p)
   const int g = lane >> 4;
   const int np = 16 * p.nb;
 
-  for (int i = tid; i < np * DS; i += hkThreads) s_xa[i] = p.xa[i];
   // sqrt(e_d) and the centre stay in LDS (broadcast reads), not in registers: the
   // D(D+1)/2 accumulators need the register file
   T* s_sd = s_xa + np * DS;
-  if (tid < 2 * D) s_sd[tid] = ((tid % D) < p.d_actual) ? p.sd[tid] : T(0);
-  const T b = p.sd[2 * D];
+  const long long n_groups = (p.M + hkRowsPerWG - 1) / hkRowsPerWG;
+  const long long n_items = BATCH ? n_groups * p.n_emulators : n_groups;
+  T b;
+  auto load_emulator = [&](int e_) __attribute__((always_inline)) {
+    const T* xa_ = p.xa;
+    const T* sd_ = p.sd;
+    if constexpr (BATCH) {
+      xa_ += (long long)e_ * p.xa_stride;
+      sd_ += (long long)e_ * p.sd_stride;
+    }
+    for (int i = tid; i < np * DS; i += hkThreads) s_xa[i] = xa_[i];
+    if (tid < 2 * D) s_sd[tid] = ((tid % D) < p.d_actual) ? sd_[tid] : T(0);
+    b = sd_[2 * D];
+  };
+  int cur_e = BATCH ? (int)(blockIdx.x / n_groups) : 0;
+  load_emulator(cur_e);
   __syncthreads();
 
-  const long long n_groups = (p.M + hkRowsPerWG - 1) / hkRowsPerWG;
-  for (long long grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+  for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
+    long long grp = item;
+    T* hess_e = p.hess;
+    if constexpr (BATCH) {
+      const int e = (int)(item / n_groups);
+      grp = item - e * n_groups;
+      hess_e += (long long)e * p.hess_stride;
+      if (e != cur_e) {        // (uniform: the item number is the workgroup's)
+        cur_e = e;
+        __syncthreads();       // everyone is done with the previous emulator's image
+        load_emulator(e);
+        __syncthreads();
+      }
+    }
     const long long m = grp * hkRowsPerWG + wave * kTile + ml;
     const long long mc = m < p.M ? m : p.M - 1;
     T t[D];
 #pragma unroll
     for (int d = 0; d < D; ++d)
       t[d] = (d < p.d_actual) ? s_sd[d] * (p.testing[mc * p.d_actual + d] - s_sd[D + d]) : T(0);
-    T* out = p.hess + mc * (long long)p.d_actual * p.d_actual;
+    T* out = hess_e + mc * (long long)p.d_actual * p.d_actual;
     const bool row_ok = m < p.M;
     // D(D+1)/2 fp64 accumulators do not fit the VALU-addressable registers beyond D ~ 11
     // (the compiler parks the excess in AGPRs and pays two moves per fma); above that the

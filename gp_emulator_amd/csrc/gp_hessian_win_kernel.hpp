@@ -1,5 +1,6 @@
-// Hessian of the GP mean on the matrix core: hessian_win_kernel<T, D, NB> (kernel D >= 8; smaller D and
-// batched emulators run the VALU kernel of gp_hessian_kernel.hpp).
+// Hessian of the GP mean on the matrix core: hessian_win_kernel<T, D, NB> (kernel D >= 8; smaller D runs the
+// VALU kernel of gp_hessian_kernel.hpp).  One emulator, or a batch of emulators on shared training inputs and
+// shared test rows (the BATCH instances).
 //
 // The reference (gp_emulator/GaussianProcess.py:345-366) forms, for every test row t,
 //   hess[d][d2] = sum_i w_i (e_d (x_id - t_d) e_d2 (x_id2 - t_d2) - [d == d2] e_d),   w_i = k_i alpha_i.
@@ -151,6 +152,12 @@ struct HessMfmaArgs {
   int n_ksteps;              // ceil(n_train / 4): k-steps that hold training points
   unsigned* tickets2;        // host side only: the counter of the call's second launch (rows beyond the last whole 64-row group)
   unsigned* tickets;         // the launch's item counter (0 on entry and on exit), or null: items dealt round-robin
+  // Batched emulators (the BATCH instances; n_emulators == 1 runs the plain ones, which never read these): E
+  // emulators share the test rows; emulator e has its constants at xa + e * xa_stride, sd + e * sd_stride,
+  // pfrags + e * pfrags_stride and writes hess + e * hess_stride.  hess_stride is the CALL's M * d_actual^2,
+  // not this launch's: the ragged rest of a call is a second launch with its own M, testing and hess offsets.
+  int n_emulators;
+  long long xa_stride, sd_stride, pfrags_stride, hess_stride;
 };
 
 // G and s ride on the matrix core.  A diagonal 4 x 4 block computes every off-diagonal pair twice --
@@ -209,7 +216,13 @@ template <typename T> __host__ __device__ constexpr bool win_lds_out(int D) {
 // issues neither their weights nor their ten matrix instructions (instantiated for the BASELINE shapes only:
 // hess_win_short_last).
 template <typename T> __host__ __device__ constexpr bool hess_win_short_last(int NB) { return NB == 16 || NB == 19; }
-template <typename T, int D, int NB, bool LDSOUT, int KL = 4>
+// BATCH: work items are (emulator, group of 64 test rows), emulator-major, as in predict_kernel: item
+// it = e * n_groups + group.  The ticket counter counts E * n_groups items; a workgroup whose next item belongs
+// to another emulator reloads the training rows and s_sd between two workgroup barriers (every wave of the
+// workgroup sees the same item number, so the barriers are uniform).  At any moment the chip works on one or
+// two emulators, whose operands (192 KiB each at N = 250, D = 11, fp64) stay in L2.  Everything an item computes
+// is the arithmetic of the plain instance on that emulator's constants: a batch is bit for bit E single calls.
+template <typename T, int D, int NB, bool LDSOUT, int KL = 4, bool BATCH = false>
 __global__ __launch_bounds__(WGeo::kThreads, (win_wg_per_cu<T>()))
 void hessian_win_kernel(HessMfmaArgs<T> p) {
   typedef Real<T> R;
@@ -246,12 +259,30 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
   const int ml = lane & 15;
   const int g = lane >> 4;
 
-  for (int i = tid; i < NP * DS; i += kThreads) s_xa[i] = p.xa[(i / DS) * DSG + i % DS];
-  if (tid < 2 * D + 1) s_sd[tid] = (tid == 2 * D || (tid % D) < p.d_actual) ? p.sd[tid] : T(0);
-  __syncthreads();
-  const T b = s_sd[2 * D];
-
   const long long n_groups = (p.M + kRowsPerWG - 1) / kRowsPerWG;
+  // BATCH: the host keeps E * n_groups (+ two grids of tickets beyond the end) below 2^32
+  const unsigned ng = (unsigned)n_groups;
+  const long long n_items = BATCH ? n_groups * p.n_emulators : n_groups;
+  // the training rows and scalars of emulator e_ into LDS (callers put the barriers around it)
+  auto load_emulator = [&](int e_) __attribute__((always_inline)) {
+    const T* xa_ = p.xa;
+    const T* sd_ = p.sd;
+    if constexpr (BATCH) {
+      xa_ += (long long)e_ * p.xa_stride;
+      sd_ += (long long)e_ * p.sd_stride;
+    }
+    for (int i = tid; i < NP * DS; i += kThreads) s_xa[i] = xa_[(i / DS) * DSG + i % DS];
+    if (tid < 2 * D + 1) s_sd[tid] = (tid == 2 * D || (tid % D) < p.d_actual) ? sd_[tid] : T(0);
+  };
+  int cur_e = 0;
+  if constexpr (BATCH) {
+    cur_e = (int)(blockIdx.x / ng);
+    if (cur_e >= p.n_emulators) cur_e = 0;       // (never: the grid is at most n_items)
+  }
+  load_emulator(cur_e);
+  __syncthreads();
+  T b = s_sd[2 * D];
+
 #if GP_STAMPS   // diagnostic build (tools/hess_stamps.py): [0] item start, [1] phase A, [2] phase B, [3] reductions, [4] finish + stores
   unsigned long long seg_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long seg_t0;
@@ -277,7 +308,7 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
       }
     }
   };
-  if ((long long)blockIdx.x < n_groups) load_row(blockIdx.x);
+  if ((long long)blockIdx.x < n_items) load_row(BATCH ? (long long)(blockIdx.x % ng) : (long long)blockIdx.x);
   // Items (groups of 64 test rows) are DRAWN, not dealt: the two workgroups of a CU do not advance at the same
   // rate -- the SIMD's arbiter favours the older wave, and with the static round-robin of round 2 the
   // workgroups dispatched first were through their share at 74 % of the launch while the others carried on
@@ -289,9 +320,20 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
   // beyond the end, so a launch draws n_groups tickets, and the lane that received the last one puts the
   // counter back to 0 for the next launch that uses it.  (p.tickets == nullptr: the same flow with the
   // round-robin numbers.)
+  // Where the ticket is published.  With several chunks per item: in front of the item's SECOND chunk barrier --
+  // a wave that is still reading s_next[0] in the previous item's finish has not passed this item's first chunk
+  // barrier, so the writer cannot be there yet.  With ONE chunk per item (NCH == 1: D = 8 with NB <= 2, every D
+  // with NB = 1) the item's only chunk barrier is its first, and a write in front of it could overtake the
+  // slower waves' reads of the previous ticket (grp = next_grp() at the end of their finish).  The LDSOUT
+  // instance therefore publishes it in front of the FINISH's barrier: the writer has passed the item's chunk
+  // barrier by then, which every wave reaches only after its last read of the previous ticket, and every read
+  // of the new one (the next row's prefetch, grp = next_grp()) lies behind the finish's barrier.  The
+  // direct-store instance has no finish barrier but, for an odd NCH, a barrier at the top of the item, which
+  // separates the previous item's reads from the write in the same way.
   __shared__ unsigned s_next[1 + kWaves];       // [0] the ticket; [1 + wave] where the other waves' copies go
   const bool dyn = p.tickets != nullptr;
-  const unsigned last_ticket = (unsigned)(n_groups - 1);
+  constexpr bool kTicketInFinish = LDSOUT && NCH == 1;
+  const unsigned last_ticket = (unsigned)(n_items - 1);
   unsigned drawn = 0;
   unsigned pending = ~0u;
   long long grp = blockIdx.x;
@@ -299,8 +341,22 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
 #if GP_STAMPS == 2
   unsigned long long life_ta = 0, life_tb = 0, life_tc = 0;
 #endif
-  while (grp < n_groups) {
+  while (grp < n_items) {
     ++items_done;
+    long long rgrp = grp;         // the item's group of 64 test rows
+    int e = 0;                    // and its emulator
+    if constexpr (BATCH) {
+      const unsigned item = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)grp);
+      e = (int)(item / ng);
+      rgrp = (long long)(item - (unsigned)e * ng);
+      if (e != cur_e) {           // (uniform over the workgroup: every wave holds the same item number)
+        cur_e = e;
+        __syncthreads();          // everyone is done with the previous emulator's rows and scalars
+        load_emulator(e);
+        __syncthreads();
+        b = s_sd[2 * D];
+      }
+    }
     if (tid == 0) {
       if (dyn && pending == last_ticket) *(volatile unsigned*)p.tickets = 0u;
       const unsigned stat = blockIdx.x + drawn * gridDim.x;
@@ -312,6 +368,7 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
     // used, instead of being hoisted out of the item loop into ~190 scalar registers that live in a vector
     // register's lanes and come back through v_readlane)
     const T* pfr = p.pfrags;
+    if constexpr (BATCH) pfr += (long long)e * p.pfrags_stride;
     asm volatile("" : "+s"(pfr));
     if constexpr (kLdsOut) {
       // chunk 0 goes to buffer 0, which is also the finish's staging space of waves 0 and 1 (below): each
@@ -332,6 +389,12 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       t[d] = s_sd[d] * (rraw[d] - s_sd[D + d]);
+      // fp32 forms x'' - t'' per training point.  Left to itself the compiler fuses this product into SOME of
+      // those subtractions (x'' - sd * u as one fma, unrounded t'') and not into others, as register pressure
+      // falls -- differently in every instance, so that a row's Hessian depended in its last bits on which
+      // instance ran it.  t'' is one rounded value everywhere: the plain and the BATCH instances agree bit for
+      // bit.  (fp64 adds x''.t'' with explicit fmas: nothing to fuse, nothing changed.)
+      if constexpr (!R::kExpand) asm volatile("" : "+v"(t[d]));
       gm = fma(t[d], t[d], gm);
     }
     gm *= T(-0.5);
@@ -432,7 +495,7 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
       if constexpr (fl == 0) {
         GP_STAMP(2);
         dma_wait();       // this wave's pieces of chunk ch have landed
-        if constexpr (ch == (NCH > 1 ? 1 : 0))   // the next item's ticket (returned by now), published by the barrier below
+        if constexpr (!kTicketInFinish && ch == (NCH > 1 ? 1 : 0))   // the next item's ticket (returned by now), published by the barrier below
           s_next[wave == 0 ? 0 : 1 + wave] = (unsigned)__builtin_amdgcn_readfirstlane((int)pending);
         if constexpr (!(GP_HESS_ABL & 1)) __syncthreads();  // chunk ch visible; everyone finished reading chunk ch-1
 #if GP_STAMPS == 2
@@ -521,6 +584,16 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
         }
       }
     };
+    // the next item's test row (the ticket has been published by now: see s_next above)
+    auto load_next_row = [&]() __attribute__((always_inline)) {
+      const long long nx = next_grp();
+      if constexpr (BATCH) {
+        const unsigned nxu = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)nx);
+        load_row(nx < n_items ? (long long)(nxu % ng) : rgrp);
+      } else {
+        load_row(nx < n_groups ? nx : grp);
+      }
+    };
     if constexpr (kLdsOut) {
       static_for<NBLK>([&](auto cbc) __attribute__((always_inline)) {      // finish in place
         T v[4];
@@ -530,6 +603,8 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
       // every wave has read its last fragment: both fragment buffers are free until chunk 0 of the next
       // item is staged (by the waves whose staging space it lands in, after their own finish)
       GP_STAMP(3);
+      if constexpr (kTicketInFinish)      // one chunk per item: the ticket goes out here (see s_next above)
+        s_next[wave == 0 ? 0 : 1 + wave] = (unsigned)__builtin_amdgcn_readfirstlane((int)pending);
       __syncthreads();
       GP_STAMP(6);
       // Whole-line stores.  Lane (ml, g) holds, over the blocks, complete rows 4 p + g (p = 0 .. NB4 - 1) of
@@ -549,16 +624,16 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
       int lo = lane;                                   // (opaque per item: the piece addresses below are recomputed
       asm volatile("" : "+v"(lo));                     //  from it with a few integer instructions, not hoisted and spilled)
       const int mlo = lo & 15, glo = lo >> 4;
-      const long long m0 = grp * kRowsPerWG + wave * kTile;
+      const long long m0 = rgrp * kRowsPerWG + wave * kTile;
       T* out0 = p.hess + m0 * (long long)(D * D);
+      if constexpr (BATCH) out0 += (long long)e * p.hess_stride;
       static_for<NB4>([&](auto ppc) __attribute__((always_inline)) {
         constexpr int pp = decltype(ppc)::value;
         if constexpr (pp == GP_HESS_ROW_PASS) {
           // the next item's test row: most accumulators are dead by now, and the remaining row blocks' LDS round
           // trips and stores cover a part of the HBM latency (loaded earlier it lived in scratch: 91 registers)
           __builtin_amdgcn_sched_barrier(0);
-          const long long nx = next_grp();
-          load_row(nx < n_groups ? nx : grp);
+          load_next_row();
           __builtin_amdgcn_sched_barrier(0);
         }
         constexpr int nrows = D - 4 * pp < 4 ? D - 4 * pp : 4;
@@ -619,16 +694,27 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
         __builtin_amdgcn_wave_barrier();
       });
     } else {
-    const long long m = grp * kRowsPerWG + wave * kTile + ml;
+    const long long m = rgrp * kRowsPerWG + wave * kTile + ml;
     const bool row_ok = m < p.M;
-    T* out = p.hess + (row_ok ? m : p.M - 1) * (long long)da * da;
-    const bool vec_ok = (da % (16 / (int)sizeof(T)) == 0) && (((unsigned long long)p.hess & 15) == 0);
+    T* hess_e = p.hess;
+    if constexpr (BATCH) hess_e += (long long)e * p.hess_stride;
+    T* out = hess_e + (row_ok ? m : p.M - 1) * (long long)da * da;
+    const bool vec_ok = (da % (16 / (int)sizeof(T)) == 0) && (((unsigned long long)hess_e & 15) == 0);
     static_for<NBLK>([&](auto cbc) {
       constexpr int cbv = decltype(cbc)::value;
       constexpr int bi = hess_block_bi(cbv), bj = hess_block_bj(cbv);
       const int d2 = 4 * bj + g;
       T v[4];
       block_values(cbc, v);
+      if constexpr (cbv == NBLK - 1) {
+        // The next item's test row, in front of the last block's stores (the other blocks' accumulators are dead
+        // by now).  This instance used to keep the row of the workgroup's FIRST item for all its items: right for
+        // the rest of a call (one item per workgroup) and for calls of up to two workgroups' worth of rows per CU,
+        // wrong beyond that for every shape it serves whole calls of (odd n_inputs, n_inputs below the kernel's D).
+        __builtin_amdgcn_sched_barrier(0);
+        load_next_row();
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #if GP_HESS_ABL & 2
       if (v[0] + v[1] + v[2] + v[3] == T(-12345.678)) out[0] = v[0];
       if (vec_ok && v[0] == T(-12345.678) && v[1] == T(-1.5))

@@ -249,3 +249,75 @@ class MultivariateEmulator(object):
             _lib.check(rc, "gp_mv_predict_host_checked")
             r0 = r1
         return (fwd, jac) if do_deriv else fwd
+
+    # ---- second derivatives ---------------------------------------------------------------------
+    def hessian(self, y, is_gpu=False, weights=None):
+        """Hessian of the reconstructed output at ONE input vector ``y``: ``(N_params, N_params, N_full)`` (axes
+        as ``predict``'s ``(N_params, N_full)`` Jacobian), or with ``weights (N_full,)`` the weighted sum over
+        the output ``sum_b weights[b] * d2 f_b / dy dy``, ``(N_params, N_params)`` -- the curvature term of a
+        cost function with residuals ``weights``.  Not in the reference (which has ``GaussianProcess.hessian``
+        only).  ``hessian_many`` on one row."""
+        y = np.atleast_2d(y)
+        if y.shape[0] != 1:
+            raise ValueError("hessian takes one input vector; hessian_many takes rows")
+        if weights is not None:
+            weights = np.atleast_2d(weights)
+        return self.hessian_many(y, is_gpu=is_gpu, weights=weights)[0]
+
+    def hessian_many(self, Y, is_gpu=True, precision=np.float64, weights=None):
+        """``(M, N_params, N_params, N_full)`` Hessians of the reconstructed outputs for M input rows, or with
+        ``weights (M, N_full)`` their weighted sums over the output ``(M, N_params, N_params)``.  The numpy
+        branch is ``sum_p basis[p] * emulators[p].hessian(Y)``.  On the GPU all per-PC Hessians are ONE batched
+        launch on the device-resident emulator (``_gpu_state``; the host arrays are digested before use and
+        the resident copy rebuilt when they were edited in place); the full form is then the reconstruction
+        kernel over rows ``(m, d, d2)``, the weighted form ``c[p, m] = sum_b basis[p, b] weights[m, b]`` and the
+        device's weighted sum over the PCs -- only the result crosses PCIe."""
+        Y = np.atleast_2d(Y)
+        M, D = Y.shape
+        B = self.basis_functions.shape[1]
+        basis = np.asarray(self.basis_functions)
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.shape != (M, B):
+                raise ValueError("weights must be (%d, %d), got %s" % (M, B, weights.shape))
+            # (P, M), one matrix-vector product per row: a row's coefficients -- and so its result -- do not depend
+            # on how many rows the call has (a matrix-matrix product rounds a column differently per shape)
+            b64 = np.ascontiguousarray(basis, dtype=np.float64)
+            coef = np.stack([b64 @ weights[m] for m in range(M)], axis=1) if M else np.zeros((self.n_pcs, 0))
+        if not is_gpu:
+            hp = np.stack([gp.hessian(Y) for gp in self.emulators])           # (P, M, D, D)
+            if weights is None:
+                return np.einsum("pmde,pb->mdeb", hp, basis)
+            return np.einsum("pmde,pm->mde", hp, coef)
+        from . import _lib
+        dt = np.dtype(precision)
+        st = self._gpu_state(dt)
+        if not st["blocks"].unchanged():
+            # the host arrays were edited in place since the resident copy was made: rebuild it from what they
+            # hold now (the staleness contract of predict_many)
+            self._release(st)
+            del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
+            st = self._gpu_state(dt)
+        ctx, batch = st["ctx"], st["batch"]
+        Yc = np.ascontiguousarray(Y, dtype=dt)
+        if weights is not None:
+            return np.array(batch.hessian_weighted(Yc, np.ascontiguousarray(coef, dtype=dt)))
+        P, isz = self.n_pcs, dt.itemsize
+        # rows per round: at most 1 GiB of results on the device (as gp_mv_predict_host)
+        step = max(1, (1 << 30) // (D * D * B * isz))
+        out = ctx.out_pool.take((M, D, D, B), dt)
+        d_y = ctx.malloc(max(1, min(M, step) * D * isz))
+        d_h = ctx.malloc(max(1, P * min(M, step) * D * D * isz))
+        d_o = ctx.malloc(max(1, min(M, step) * D * D * B * isz))
+        try:
+            for r0 in range(0, M, step):
+                n = min(M, r0 + step) - r0
+                ctx.h2d(d_y, Yc[r0:r0 + n])
+                batch.hessian_device(d_y, d_h, n)                              # [P][n][D][D]
+                ctx.reconstruct_device(dt, st["d_basis"], d_h, d_o, n * D * D, P, B)
+                _lib.check(ctx.lib.gp_memcpy_d2h(ctx.h, _lib._ptr(out[r0:r0 + n]), d_o, n * D * D * B * isz),
+                           "gp_memcpy_d2h")
+        finally:
+            for p_ in (d_y, d_h, d_o):
+                ctx.free(p_)
+        return out

@@ -100,6 +100,100 @@ def predict_bands(gps, testing, precision=np.float64, device=None, devices=None,
     return (mu, var, deriv) if do_unc else (mu, deriv)
 
 
+def _check_shared_inputs(gps):
+    if not gps:
+        raise ValueError("need at least one GaussianProcess")
+    inputs = np.asarray(gps[0].inputs)
+    for gp in gps[1:]:
+        other = np.asarray(gp.inputs)
+        if other.shape != inputs.shape or not np.array_equal(other, inputs):
+            raise ValueError("per-band emulators must share the same training inputs")
+    return inputs
+
+
+def hessian_bands(gps, testing, precision=np.float64, weights=None, device=None, devices=None, hessian_fn=None):
+    """Hessians of the E emulators' means over shared test rows: ``(E, M, D, D)``, or with ``weights``
+    ``(E, M)`` the weighted sum over the emulators ``sum_e weights[e, m] * H_e[m]``, ``(M, D, D)`` -- the
+    second-derivative term of a spectral cost function, summed on the device (the per-band result of 2101
+    bands x 1e5 rows could never be stored).  One batched launch per slab of rows (``BatchModel.hessian`` /
+    ``hessian_weighted``); no inverse is stacked or uploaded.
+
+    ``devices`` shards the EMULATORS like ``predict_bands``: device g takes a contiguous block.  Unweighted,
+    every device writes its own ``[e0:e1]`` slice; weighted, every device returns the partial sum of its block
+    and the partial sums are added on the host in device order (so the result does not depend on which device
+    finishes first).  ``hessian_fn(device, gps_block, testing[, weights_block])`` replaces the HIP path in the
+    CPU tests of the sharding logic."""
+    testing = np.asarray(testing)
+    if testing.ndim != 2:
+        raise ValueError("testing must be (n_predict, n_inputs)")
+    inputs = _check_shared_inputs(gps)
+    E, (M, D) = len(gps), testing.shape
+    if D != inputs.shape[1]:
+        raise ValueError("testing has %d columns, the emulators have %d inputs" % (D, inputs.shape[1]))
+    if weights is not None:
+        weights = np.asarray(weights)
+        if weights.shape != (E, M):
+            raise ValueError("weights must be (%d, %d), got %s" % (E, M, weights.shape))
+    if devices is None:
+        if hessian_fn is not None:
+            return hessian_fn(device, gps, testing) if weights is None else hessian_fn(device, gps, testing, weights)
+        batch = make_batch(gps, precision, device, do_unc=False)
+        try:
+            return batch.hessian(testing) if weights is None else batch.hessian_weighted(testing, weights)
+        finally:
+            batch.close()
+    import threading
+    from . import multi_gpu
+    if len(devices) < 1:
+        raise ValueError("devices must name at least one device")
+    dt = np.float64 if (testing.dtype == np.float64 or np.dtype(precision) == np.float64) else np.float32
+    blocks = multi_gpu.row_shards(E, len(devices))       # contiguous blocks of emulators
+    out = np.empty((E, M, D, D), dt) if weights is None else None
+    partial = [None] * len(devices)
+    errors = []
+
+    def work(k, dev, e0, e1):
+        try:
+            if e1 <= e0:
+                return
+            part = gps[e0:e1]
+            if hessian_fn is not None:
+                if weights is None:
+                    out[e0:e1] = hessian_fn(dev, part, testing)
+                else:
+                    partial[k] = np.asarray(hessian_fn(dev, part, testing, weights[e0:e1]))
+                return
+            ctx, lock = multi_gpu._device_context(dev)
+            with lock:
+                batch = _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in part]), inputs,
+                                        np.stack([np.asarray(gp.invQt) for gp in part]), None, precision)
+                try:
+                    if weights is None:
+                        batch.hessian(testing, out=out[e0:e1])
+                    else:
+                        partial[k] = np.array(batch.hessian_weighted(testing, weights[e0:e1]))   # (own memory, not the pool's)
+                finally:
+                    batch.close()
+        except BaseException as exc:          # surfaced to the caller below
+            errors.append(exc)
+
+    threads = [threading.Thread(target=work, args=(k, dev, e0, e1))
+               for k, (dev, (e0, e1)) in enumerate(zip(devices, blocks))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        raise errors[0]
+    if weights is None:
+        return out
+    total = np.zeros((M, D, D), dt)
+    for part in partial:                      # device order
+        if part is not None:
+            total += part
+    return total
+
+
 # ---------------------------------------------------------------------------------------------
 # Training many per-band emulators at once
 # ---------------------------------------------------------------------------------------------

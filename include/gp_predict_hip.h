@@ -209,7 +209,11 @@ int gp_device_numa_node(int device, int* node);
  * gp_hessian_f64/_f32: host pointers in and out (invQ is not needed by the Hessian).
  * Every element and its mirror image are stored from the same value: the result is exactly
  * symmetric.  n_inputs >= 6 (with n_train <= 320) runs on the matrix core; the first Hessian
- * call on a model packs and uploads that kernel's constant operand (once, thread-safe). */
+ * call on a model packs and uploads that kernel's constant operand (once, thread-safe).
+ * A batched model (gp_batch_create_*) gives hess (n_emulators, n_predict, n_inputs, n_inputs) in ONE launch
+ * (two on the matrix core: whole 64-row groups, rest), bit for bit what n_emulators single-emulator
+ * calls on the same rows give; its matrix-core operands are packed per emulator
+ * (192 KiB each at n_train = 250, n_inputs = 10 or 11, float64). */
 int gp_hessian_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
                       void* d_hess, int64_t n_predict);
 /* host arrays of the model's dtype in and out, through the same slab pipeline as gp_predict_host */
@@ -220,6 +224,18 @@ int gp_hessian_host(gp_ctx* ctx, const gp_model* model, const void* testing, voi
  * means for a float64 caller; numpy casts of the (M, D, D) result cost more than the kernel) */
 int gp_hessian_host_h64(gp_ctx* ctx, const gp_model* model, const double* testing, double* hess,
                         int64_t n_predict);
+/* Weighted sum over the emulators of a batch: out[m] = sum_e weights[e][m] * H_e[m], out (n_predict, n_inputs,
+ * n_inputs), weights (n_emulators, n_predict) -- the second-derivative term of a spectral cost function
+ * (sum over bands of residual x Hessian), for which the per-emulator result can be far too large to exist.  The
+ * rows are cut into slabs whose per-emulator matrices live in device scratch of bounded size (256 MiB,
+ * GP_HESS_WEIGHTED_MB; independent of n_emulators and n_predict) and are folded by a second kernel: the
+ * emulators in ascending order, no atomics, so two calls agree bit for bit and the result is exactly symmetric.
+ * _device: device pointers of the model's dtype, asynchronous on the context's stream.
+ * _host: host arrays, host_dtype as for gp_predict_host (the model's dtype, or GP_F64 on a GP_F32 model). */
+int gp_hessian_weighted_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
+                               const void* d_weights, void* d_out, int64_t n_predict);
+int gp_hessian_weighted_host(gp_ctx* ctx, const gp_model* model, int host_dtype, const void* testing,
+                             const void* weights, void* out, int64_t n_predict);
 int gp_hessian_f64(gp_ctx* ctx, const double* expX, const double* inputs, const double* invQt,
                    const double* testing, double* hess,
                    int64_t n_predict, int n_train, int n_inputs, int theta_size);
