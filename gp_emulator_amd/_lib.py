@@ -76,6 +76,9 @@ SIGNATURES = {
                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gp_pack_sizes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                               ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "gp_launch_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_int),
+                               ctypes.POINTER(c_i64), ctypes.POINTER(c_int), ctypes.POINTER(c_i64),
+                               ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "gp_pack_model_f64": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int] + [c_void_p] * 4),
     "gp_pack_model_f32": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int] + [c_void_p] * 4),
     "gp_pinned_alloc": (c_int, [c_void_p, c_i64, PP]),
@@ -644,6 +647,35 @@ class BatchModel(Model):
                 self.ctx.h, self.h, GP_F64 if hdt == np.float64 else GP_F32, _ptr(testing), _ptr(weights),
                 _ptr(res), M), "gp_hessian_weighted_host")
         return res
+
+
+GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT = 0, 1, 2, 3
+PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
+                6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide"}
+_PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
+             "reconstruct": GP_OP_RECONSTRUCT}
+
+
+def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_pcs=0, n_bands=0,
+                compute_units=256, aligned16=True):
+    """How the device call ``op`` ("predict", "mean_grad", "hessian", "reconstruct") on ``n_rows`` rows would be
+    launched on a device of ``compute_units`` (``gp_launch_plan``: host arithmetic shared with the launch path, no
+    GPU needed).  Returns dict(kernel, rows_per_item, items, workgroups, rest_items, rest_workgroups): the
+    kernel family and instance (a ``PLAN_KERNELS`` name), the rows of one work item, and the work items and
+    workgroups of the launch (``rest_*``: the windowed Hessian's second launch for the rows behind the last whole
+    64-row group).  ``items > workgroups``: workgroups run several items.  ``aligned16``: a Hessian call's row and
+    output pointers are 16-byte aligned.  reconstruct takes ``n_pcs`` and ``n_bands``."""
+    code = _PLAN_OPS[op]
+    recon = code == GP_OP_RECONSTRUCT
+    k, wg, rwg, rpi = c_int(0), c_int(0), c_int(0), c_int(0)
+    items, ritems = c_i64(0), c_i64(0)
+    check(load().gp_launch_plan(
+        code, GP_F64 if np.dtype(precision) == np.float64 else GP_F32, int(n_train), int(n_pcs if recon else n_inputs),
+        int(n_emulators), int(n_rows), int(n_bands if recon else 0), int(compute_units), int(bool(aligned16)),
+        ctypes.byref(k), ctypes.byref(items), ctypes.byref(wg), ctypes.byref(ritems), ctypes.byref(rwg),
+        ctypes.byref(rpi)), "gp_launch_plan")
+    return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
+                rest_items=ritems.value, rest_workgroups=rwg.value)
 
 
 def pack_model(expX, inputs, invQt, invQ, precision=np.float64):

@@ -28,6 +28,7 @@
 #include "gp_hessian_win_kernel.hpp"
 #include "gp_hessian_combine_kernel.hpp"
 #include "gp_host_pool.hpp"
+#include "gp_launch_plan.hpp"
 #include "gp_predict_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
 #include "gp_train_args.hpp"
@@ -555,6 +556,39 @@ hipError_t launch_generic<double>(const gpk::GenericArgs<double>& a, int grid, h
   return gpk::launch_generic_f64(a, grid, s);
 }
 
+// ---- launch sizing: what predict_device / hessian_device launch and gp_launch_plan reports ----------
+// (the arithmetic is gp_launch_plan.hpp's; here it meets the kernels' geometry constants and the switches)
+static gpk::GridPlan plan_generic(int64_t M, int compute_units) {
+  return gpk::plan_grid(M, gpk::kTile, 1, (int64_t)compute_units * 4);
+}
+struct PredictPlan {
+  bool few;             // predict_few_kernel: a workgroup per 16-row tile
+  bool too_large;       // more row groups than one launch numbers
+  int rows_per_item;
+  gpk::GridPlan grid;
+};
+// Few rows (one state vector at a time): the latency form, a workgroup per 16-row tile with the
+// tile's work shared by its waves (gp_predict_few_kernel.hpp), while every tile still gets a
+// workgroup of its own in one round of the chip.  GP_NO_FEW=1: always the throughput kernel.
+template <typename T>
+static PredictPlan plan_predict(int64_t M, int n_emulators, bool want_var, int compute_units) {
+  PredictPlan p = {false, false, gpk::kTile, {0, 0}};
+  const char* few_ev = getenv("GP_NO_FEW");          // read per call: the tests run both kernels in one process
+  const bool no_few = few_ev && atoi(few_ev) != 0;
+  const gpk::GridPlan tiles = gpk::plan_grid(M, gpk::kTile, n_emulators, (int64_t)0x7fffffff);
+  if (!no_few && gpk::plan_predict_few(tiles.items, compute_units)) {
+    p.few = true;
+    p.grid = tiles;
+    return p;
+  }
+  p.rows_per_item = want_var ? gpk::Geo<T>::kRowsPerWG : gpk::Geo<T, false>::kRowsPerWG;
+  p.too_large = (M + p.rows_per_item - 1) / p.rows_per_item > 0x7fffffffLL;
+  // persistent grid: the kernel's occupancy (full: 2 waves per SIMD), grid-stride over work items
+  p.grid = gpk::plan_grid(M, p.rows_per_item, n_emulators,
+                          (int64_t)compute_units * (want_var ? gpk::Geo<T>::kWGPerCU : gpk::Geo<T, false>::kWGPerCU));
+  return p;
+}
+
 // d_var == nullptr: mean and gradient only (the *_mean_grad entry points), on the no-variance
 // instance of whichever kernel the rule below picks for a full predict of the same call.
 template <typename T>
@@ -583,10 +617,8 @@ static int predict_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
     g.dk = m->kernel_d;
     g.deriv_row_major = layout == GP_DERIV_ROWMAJOR;
     g.want_var = want_var ? 1 : 0;
-    int64_t tiles = (M + 15) / 16;
-    int64_t grid = (int64_t)ctx->compute_units * 4;
-    if (grid > tiles) grid = tiles;
-    hipError_t e = launch_generic<T>(g, (int)grid, stream);
+    const gpk::GridPlan gp = plan_generic(M, ctx->compute_units);
+    hipError_t e = launch_generic<T>(g, gp.workgroups, stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "generic kernel launch: %s", hipGetErrorString(e));
     return GP_OK;
   }
@@ -607,27 +639,16 @@ static int predict_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
   a.sd_stride = m->sd_stride;
   a.dbg = (unsigned long long*)ctx->dbg;
   a.rows_prescaled = rows_prescaled ? 1 : 0;
-  // Few rows (one state vector at a time): the latency form, a workgroup per 16-row tile with the
-  // tile's work shared by its waves (gp_predict_few_kernel.hpp), while every tile still gets a
-  // workgroup of its own in one round of the chip.  GP_NO_FEW=1: always the throughput kernel.
-  const char* few_ev = getenv("GP_NO_FEW");          // read per call: the tests run both kernels in one process
-  const bool no_few = few_ev && atoi(few_ev) != 0;
-  const int64_t tiles = (M + gpk::kTile - 1) / gpk::kTile * m->n_emulators;
-  if (!no_few && tiles <= 2 * (int64_t)ctx->compute_units) {
+  const PredictPlan pp = plan_predict<T>(M, m->n_emulators, want_var, ctx->compute_units);
+  if (pp.few) {
     hipError_t e;
-    if constexpr (sizeof(T) == 8) e = gpk::launch_few_f64(m->kernel_d, a, m->kernel_nb, (int)tiles, want_var, stream);
-    else e = gpk::launch_few_f32(m->kernel_d, a, m->kernel_nb, (int)tiles, want_var, stream);
+    if constexpr (sizeof(T) == 8) e = gpk::launch_few_f64(m->kernel_d, a, m->kernel_nb, pp.grid.workgroups, want_var, stream);
+    else e = gpk::launch_few_f32(m->kernel_d, a, m->kernel_nb, pp.grid.workgroups, want_var, stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "kernel launch (few rows): %s", hipGetErrorString(e));
     return GP_OK;
   }
-  const int kRowsPerWG = want_var ? gpk::Geo<T>::kRowsPerWG : gpk::Geo<T, false>::kRowsPerWG;
-  const int64_t groups = (M + kRowsPerWG - 1) / kRowsPerWG * m->n_emulators;
-  if ((M + kRowsPerWG - 1) / kRowsPerWG > 0x7fffffffLL)
-    return fail(GP_ERR_INVALID, "n_predict too large for one launch");
-  // persistent grid: the kernel's occupancy (full: 2 waves per SIMD), grid-stride over work items
-  int64_t grid = (int64_t)ctx->compute_units * (want_var ? gpk::Geo<T>::kWGPerCU : gpk::Geo<T, false>::kWGPerCU);
-  if (grid > groups) grid = groups;
-  hipError_t e = launch<T>(m->kernel_nk, m->kernel_d, a, (int)grid, want_var, stream);
+  if (pp.too_large) return fail(GP_ERR_INVALID, "n_predict too large for one launch");
+  hipError_t e = launch<T>(m->kernel_nk, m->kernel_d, a, pp.grid.workgroups, want_var, stream);
   if (e != hipSuccess) return fail(GP_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return GP_OK;
 }
@@ -664,11 +685,23 @@ hipError_t launch_hessm<double>(int knb, int kd, const gpk::HessMfmaArgs<double>
   return hipErrorInvalidValue;
 }
 
-static bool hessian_on_matrix_core(const gp_model* m) {
-  if (m->kernel_nb <= 0 || (m->n_emulators == 1 && m->xs_host.empty())) return false;
+static bool hessian_on_matrix_core(int kernel_d, int kernel_nb) {
+  if (kernel_nb <= 0) return false;
   if (const char* ev = getenv("GP_HESS_VALU"))      // A/B switch: force the VALU kernel
     if (atoi(ev) != 0) return false;
-  return m->kernel_d == 8 || m->kernel_d == 10 || m->kernel_d == 11 || m->kernel_d == 12 || m->kernel_d == 16;
+  return gpk::hess_win_kernel_d(kernel_d);
+}
+static bool hessian_on_matrix_core(const gp_model* m) {
+  if (m->n_emulators == 1 && m->xs_host.empty()) return false;
+  return hessian_on_matrix_core(m->kernel_d, m->kernel_nb);
+}
+template <typename T> static int hess_win_cap(int compute_units) { return compute_units * gpk::win_wg_per_cu<T>(); }
+static int hess_valu_nb(int n_train) { return (n_train + 15) / 16; }     // the loop over training points is a run-time loop
+static bool hess_valu_fits_lds(int elem_bytes, int n_train, int kernel_d) {
+  return gpk::hess_valu_lds_bytes(elem_bytes, hess_valu_nb(n_train), gpk::row_stride(kernel_d), kernel_d) <= 160 * 1024;
+}
+static gpk::GridPlan plan_hess_valu(int64_t M, int n_emulators, int compute_units) {
+  return gpk::plan_grid(M, gpk::hkRowsPerWG, n_emulators, (int64_t)compute_units * 2);
 }
 
 // The constant operand of hessian_win_kernel, built once per model: P[i][(d, d2)] =
@@ -752,7 +785,7 @@ static int hessian_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
   if (e0 < 0 || ne < 1 || e0 + ne > m->n_emulators) return fail(GP_ERR_INVALID, "bad emulator range");
   if (hess_stride < 0) hess_stride = (long long)M * m->n_inputs * m->n_inputs;
   // batched items are numbered in 32 bits (with room for the tickets drawn beyond the end)
-  if (ne > 1 && (M + 63) / 64 * (int64_t)ne > (int64_t)0x7fffffff - 4 * 1024 * 1024)
+  if (ne > 1 && !gpk::hess_items_fit(M, 64, ne))
     return fail(GP_ERR_INVALID, "n_predict x n_emulators too large for one launch: split the rows");
   if (hessian_on_matrix_core(m)) {
     int rc = ensure_hess_frags<T>(ctx, const_cast<gp_model*>(m));
@@ -780,7 +813,7 @@ static int hessian_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
       h.tickets2 = ctx->tickets + 4 * ((slot + 1) % kTicketSlots);
     }
     // (the launcher sizes each launch: min(grid, its items))
-    const int grid = ctx->compute_units * gpk::win_wg_per_cu<T>();
+    const int grid = hess_win_cap<T>(ctx->compute_units);
     hipError_t e = launch_hessm<T>(m->kernel_nb, m->kernel_d, h, grid, stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "hessian kernel launch: %s", hipGetErrorString(e));
     return GP_OK;
@@ -792,17 +825,14 @@ static int hessian_device(gp_ctx* ctx, const gp_model* m, const void* d_testing,
   a.hess = (T*)d_hess;
   a.M = M;
   a.d_actual = m->n_inputs;
-  a.nb = (m->n_train + 15) / 16;     // the loop over training points is a run-time loop
+  a.nb = hess_valu_nb(m->n_train);
   a.n_emulators = ne;
   a.xa_stride = m->xa_stride;
   a.sd_stride = m->sd_stride;
   a.hess_stride = hess_stride;
-  if (sizeof(T) * (16 * (size_t)a.nb * gpk::row_stride(m->kernel_d) + 2 * m->kernel_d) > 160 * 1024)
+  if (!hess_valu_fits_lds((int)sizeof(T), m->n_train, m->kernel_d))
     return fail(GP_ERR_UNSUPPORTED, "training set too large for the hessian kernel's LDS image");
-  const int64_t groups = (M + gpk::hkRowsPerWG - 1) / gpk::hkRowsPerWG * ne;
-  int64_t grid = (int64_t)ctx->compute_units * 2;
-  if (grid > groups) grid = groups;
-  hipError_t e = launch_hessian<T>(m->kernel_d, a, (int)grid, stream);
+  hipError_t e = launch_hessian<T>(m->kernel_d, a, plan_hess_valu(M, ne, ctx->compute_units).workgroups, stream);
   if (e != hipSuccess) return fail(GP_ERR_HIP, "hessian kernel launch: %s", hipGetErrorString(e));
   return GP_OK;
 }
@@ -1542,6 +1572,14 @@ static int hessian_host(gp_ctx* ctx, const T* expX, const T* inputs, const T* in
   return hessian_host_model<T>(ctx, m, testing, hess, M);
 }
 
+// geometry: rows that one 512-thread workgroup can cover whole (and that a 256-thread one
+// cannot) use the wide form; GP_RECON_WIDE=0/1 overrides for A/B measurements
+static int recon_wide(int dtype, int n_bands) {
+  int wide = gpk::recon_wide_default(n_bands, dtype == GP_F64 ? 2 : 4) ? 1 : 0;
+  if (const char* ev = getenv("GP_RECON_WIDE")) wide = atoi(ev) != 0;
+  return wide;
+}
+
 // out[r][band] = sum_p coef[p][r] basis[p][band] on `stream` (gp_reconstruct_kernel.hpp)
 static int reconstruct_on(gp_ctx* ctx, int dtype, const void* d_basis, const void* d_coef, void* d_out,
                           int64_t n_rows, int n_pcs, int n_bands, hipStream_t stream) {
@@ -1550,11 +1588,7 @@ static int reconstruct_on(gp_ctx* ctx, int dtype, const void* d_basis, const voi
   if (n_rows == 0) return GP_OK;
   if (!d_basis || !d_coef || !d_out) return fail(GP_ERR_INVALID, "null device pointer");
   if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
-  // geometry: rows that one 512-thread workgroup can cover whole (and that a 256-thread one
-  // cannot) use the wide form; GP_RECON_WIDE=0/1 overrides for A/B measurements
-  const int vec = dtype == GP_F64 ? 2 : 4;
-  int wide = (n_bands > 256 * 2 * vec && n_bands <= 512 * 3 * vec) ? 1 : 0;
-  if (const char* ev = getenv("GP_RECON_WIDE")) wide = atoi(ev) != 0;
+  const int wide = recon_wide(dtype, n_bands);
   hipError_t e;
   if (dtype == GP_F64) {
     gpk::ReconArgs<double> a{(const double*)d_basis, (const double*)d_coef, (double*)d_out, n_rows, n_pcs, n_bands};
@@ -1713,6 +1747,84 @@ int gp_kernel_ksteps(int n_train, int n_inputs, int* ksteps) {
   int rc = pick_kernel(n_train, n_inputs, &kd, &knb, &knk);
   if (rc) return rc;
   *ksteps = knk;
+  return GP_OK;
+}
+
+int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
+                   int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
+                   int64_t* rest_items, int* rest_workgroups, int* rows_per_item) {
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_rows <= 0 || compute_units <= 0 || n_emulators <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  const bool f64 = dtype == GP_F64;
+  int k = 0, rpi = 0;
+  gpk::GridPlan g = {0, 0}, rest = {0, 0};
+  if (op == GP_OP_RECONSTRUCT) {
+    // (n_inputs = n_pcs here; aux = n_bands)
+    if (n_inputs <= 0 || aux <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    if (n_inputs > 16) return fail(GP_ERR_UNSUPPORTED, "reconstruction kernels are compiled for n_pcs <= 16");
+    const int wide = recon_wide(dtype, aux);
+    const long long bw = f64 ? (wide ? gpk::recon_bands_per_wg<double, 512, 3>() : gpk::recon_bands_per_wg<double, 256, 2>())
+                             : (wide ? gpk::recon_bands_per_wg<float, 512, 3>() : gpk::recon_bands_per_wg<float, 256, 2>());
+    k = wide ? GP_PLAN_RECON_WIDE : GP_PLAN_RECON_NARROW;
+    rpi = gpk::rkRows;
+    g = gpk::plan_recon(n_rows, gpk::rkRows, aux, bw, gpk::recon_cap(compute_units, wide != 0));
+  } else if (op == GP_OP_PREDICT || op == GP_OP_MEAN_GRAD || op == GP_OP_HESSIAN) {
+    int kd, knb;
+    int rc = pick_kernel(n_train, n_inputs, &kd, &knb);
+    if (rc) return rc;
+    if (op != GP_OP_HESSIAN) {
+      const bool var = op == GP_OP_PREDICT;
+      if (knb == 0) {
+        if (n_emulators != 1)
+          return fail(GP_ERR_UNSUPPORTED, "batched emulators need n_train <= %d and n_inputs <= %d",
+                      16 * GP_MAX_KERNEL_NB, GP_MAX_KERNEL_D);
+        k = GP_PLAN_GENERIC;
+        rpi = gpk::kTile;
+        g = plan_generic(n_rows, compute_units);
+      } else {
+        const PredictPlan pp = f64 ? plan_predict<double>(n_rows, n_emulators, var, compute_units)
+                                   : plan_predict<float>(n_rows, n_emulators, var, compute_units);
+        if (!pp.few && pp.too_large) return fail(GP_ERR_INVALID, "n_predict too large for one launch");
+        k = pp.few ? GP_PLAN_PREDICT_FEW : GP_PLAN_PREDICT;
+        rpi = pp.rows_per_item;
+        g = pp.grid;
+      }
+    } else {
+      if (n_inputs > GP_MAX_KERNEL_D)
+        return fail(GP_ERR_UNSUPPORTED, "hessian kernels are compiled for n_inputs <= %d", GP_MAX_KERNEL_D);
+      if (n_emulators > 1 && !gpk::hess_items_fit(n_rows, 64, n_emulators))
+        return fail(GP_ERR_INVALID, "n_predict x n_emulators too large for one launch: split the rows");
+      if (hessian_on_matrix_core(kd, knb)) {
+        const gpk::WinPlan w = gpk::plan_hess_win(
+            n_rows, gpk::WGeo::kRowsPerWG, n_emulators, f64 ? hess_win_cap<double>(compute_units) : hess_win_cap<float>(compute_units),
+            f64 ? gpk::win_lds_out<double>(kd) : gpk::win_lds_out<float>(kd), n_inputs == kd, aligned16 != 0,
+            f64 ? gpk::hess_win_short_last<double>(knb) : gpk::hess_win_short_last<float>(knb), (n_train + 3) / 4, knb);
+        rpi = gpk::WGeo::kRowsPerWG;
+        if (w.ldsout_kl != 0) {
+          k = w.ldsout_kl == 3 ? GP_PLAN_HESS_WIN_KL3 : GP_PLAN_HESS_WIN_KL4;
+          g = w.main;
+          rest = w.rest;
+        } else {
+          k = GP_PLAN_HESS_WIN_DIRECT;
+          g = w.rest;
+        }
+      } else {
+        if (!hess_valu_fits_lds(f64 ? 8 : 4, n_train, kd))
+          return fail(GP_ERR_UNSUPPORTED, "training set too large for the hessian kernel's LDS image");
+        k = GP_PLAN_HESS_VALU;
+        rpi = gpk::hkRowsPerWG;
+        g = plan_hess_valu(n_rows, n_emulators, compute_units);
+      }
+    }
+  } else {
+    return fail(GP_ERR_INVALID, "bad op %d", op);
+  }
+  if (kernel) *kernel = k;
+  if (items) *items = g.items;
+  if (workgroups) *workgroups = g.workgroups;
+  if (rest_items) *rest_items = rest.items;
+  if (rest_workgroups) *rest_workgroups = rest.workgroups;
+  if (rows_per_item) *rows_per_item = rpi;
   return GP_OK;
 }
 

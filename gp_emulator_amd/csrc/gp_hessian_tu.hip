@@ -3,6 +3,7 @@
 #include "gp_hessian_kernel.hpp"
 #include "gp_hessian_combine_kernel.hpp"
 #include "gp_dispatch.hpp"
+#include "gp_launch_plan.hpp"
 
 #define GP_CAT2(a, b) a##b
 #define GP_CAT(a, b) GP_CAT2(a, b)
@@ -24,7 +25,7 @@ static hipError_t launch_one(const HessianArgs<GP_T>& a, int grid, size_t lds, h
 
 hipError_t GP_CAT(launch_hessian_, GP_TNAME)(int kernel_d, const HessianArgs<GP_T>& a, int grid,
                                              hipStream_t stream) {
-  const size_t lds = sizeof(GP_T) * (16 * (size_t)a.nb * row_stride(kernel_d) + 2 * kernel_d);
+  const size_t lds = (size_t)hess_valu_lds_bytes((int)sizeof(GP_T), a.nb, row_stride(kernel_d), kernel_d);
   switch (kernel_d) {
 #define GP_CASE(d) case d: return launch_one<d>(a, grid, lds, stream);
     GP_FOR_EACH_KERNEL_D(GP_CASE)

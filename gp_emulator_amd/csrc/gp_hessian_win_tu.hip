@@ -3,6 +3,7 @@
 // profiles/r01_hessian_kernels.txt).  Compiled by build.py with
 // -DGP_T=<float|double> -DGP_TNAME=<f32|f64> -DGP_NB=<blocks of 16 training points>.
 #include "gp_hessian_win_kernel.hpp"
+#include "gp_launch_plan.hpp"
 
 #define GP_CAT2(a, b, c) a##b##_##c
 #define GP_CAT(a, b, c) GP_CAT2(a, b, c)
@@ -13,38 +14,36 @@ namespace gpk {
 // min(grid, its work items): 64-row groups, times the emulators of a batch (BATCH instances: a.n_emulators > 1)
 template <int D, bool BATCH>
 static hipError_t launch_one(const HessMfmaArgs<GP_T>& a, int grid, hipStream_t stream) {
-  constexpr int kRows = WGeo::kRowsPerWG;
-  auto groups_of = [&](long long m) {
-    const long long g_ = (m + kRows - 1) / kRows * (BATCH ? a.n_emulators : 1);
-    return (int)(g_ < grid ? g_ : grid);
-  };
+  // which instance takes which rows, and the grid of each launch: plan_hess_win (gp_launch_plan.hpp)
+  const WinPlan w = plan_hess_win(a.M, WGeo::kRowsPerWG, BATCH ? a.n_emulators : 1, grid, win_lds_out<GP_T>(D),
+                                  a.d_actual == D, (((unsigned long long)a.hess | (unsigned long long)a.testing) & 15) == 0,
+                                  hess_win_short_last<GP_T>(GP_NB), a.n_ksteps, GP_NB);
   HessMfmaArgs<GP_T> rest = a;
   if constexpr (win_lds_out<GP_T>(D)) {
     // whole-line stores through LDS when the caller's rows are exactly D long and the matrix is aligned: the
     // whole 64-row groups of the call; what is left (< 64 rows) goes to the direct-store instance below (for a
     // batch: every emulator's rest, at the same offsets of its own matrix block -- hess_stride stays the call's)
-    const long long m_main = a.M / kRows * kRows;
-    if (m_main > 0 && a.d_actual == D && (((unsigned long long)a.hess | (unsigned long long)a.testing) & 15) == 0) {
+    if (w.ldsout_kl != 0) {
       HessMfmaArgs<GP_T> b = a;
-      b.M = m_main;
+      b.M = w.main_rows;
       bool done = false;
       if constexpr (hess_win_short_last<GP_T>(GP_NB)) {
-        if (a.n_ksteps == 4 * GP_NB - 1) {      // the last k-step holds nothing but padding: not issued
-          hipLaunchKernelGGL((hessian_win_kernel<GP_T, D, GP_NB, true, 3, BATCH>), dim3(groups_of(m_main)), dim3(WGeo::kThreads), 0, stream, b);
+        if (w.ldsout_kl == 3) {      // the last k-step holds nothing but padding: not issued
+          hipLaunchKernelGGL((hessian_win_kernel<GP_T, D, GP_NB, true, 3, BATCH>), dim3(w.main.workgroups), dim3(WGeo::kThreads), 0, stream, b);
           done = true;
         }
       }
       if (!done)
-        hipLaunchKernelGGL((hessian_win_kernel<GP_T, D, GP_NB, true, 4, BATCH>), dim3(groups_of(m_main)), dim3(WGeo::kThreads), 0, stream, b);
+        hipLaunchKernelGGL((hessian_win_kernel<GP_T, D, GP_NB, true, 4, BATCH>), dim3(w.main.workgroups), dim3(WGeo::kThreads), 0, stream, b);
       hipError_t e = hipGetLastError();
-      if (e != hipSuccess || m_main == a.M) return e;
-      rest.M = a.M - m_main;
-      rest.testing = a.testing + m_main * D;
-      rest.hess = a.hess + m_main * D * D;
+      if (e != hipSuccess || w.rest_rows == 0) return e;
+      rest.M = w.rest_rows;
+      rest.testing = a.testing + w.main_rows * D;
+      rest.hess = a.hess + w.main_rows * D * D;
       rest.tickets = a.tickets2;
     }
   }
-  hipLaunchKernelGGL((hessian_win_kernel<GP_T, D, GP_NB, false, 4, BATCH>), dim3(groups_of(rest.M)), dim3(WGeo::kThreads), 0, stream, rest);
+  hipLaunchKernelGGL((hessian_win_kernel<GP_T, D, GP_NB, false, 4, BATCH>), dim3(w.rest.workgroups), dim3(WGeo::kThreads), 0, stream, rest);
   return hipGetLastError();
 }
 

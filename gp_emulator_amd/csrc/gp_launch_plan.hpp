@@ -1,0 +1,85 @@
+// How a call is cut into work items and workgroups: host arithmetic only, shared by the launch
+// path (gp_abi.hip and the *_tu.hip launchers) and by gp_launch_plan, which reports it, so that the
+// report cannot drift from the launch.  Every hot kernel is persistent: a launch takes
+// min(cap, items) workgroups, cap = compute units x workgroups per CU, and a workgroup walks the
+// items it is dealt (grid-stride, or a ticket counter in hessian_win_kernel).  One ROUND of a
+// kernel is cap items = cap x rows_per_item test rows; beyond it workgroups run several items.
+// The geometry constants stay with the kernels (Geo, WGeo, hk*, gk*, rk*): callers pass them in.
+#pragma once
+
+namespace gpk {
+
+struct GridPlan {
+  long long items;      // work items of the launch
+  int workgroups;       // its grid
+};
+
+// Items = groups of rows_per_item rows, times the emulators of a batch (emulator-major); the grid is
+// the persistent cap or the items, whichever is smaller.
+inline GridPlan plan_grid(long long rows, int rows_per_item, long long n_emulators, long long cap) {
+  GridPlan p;
+  p.items = (rows + rows_per_item - 1) / rows_per_item * n_emulators;
+  p.workgroups = (int)(p.items < cap ? p.items : cap);
+  return p;
+}
+
+// predict: the few-rows kernel (a workgroup per 16-row tile) while every tile still gets a
+// workgroup of its own within two rounds of the chip
+inline bool plan_predict_few(long long tiles, int compute_units) { return tiles <= 2 * (long long)compute_units; }
+
+// dynamic LDS of hessian_kernel: the training rows and [sqrt(e), centre]
+inline unsigned long long hess_valu_lds_bytes(int elem_bytes, int nb, int row_stride, int kernel_d) {
+  return (unsigned long long)elem_bytes * (16 * (unsigned long long)nb * row_stride + 2 * kernel_d);
+}
+// kernel dimensions that hessian_win_kernel is compiled for (where the matrix-core form beats or ties the VALU one)
+inline bool hess_win_kernel_d(int kernel_d) {
+  return kernel_d == 8 || kernel_d == 10 || kernel_d == 11 || kernel_d == 12 || kernel_d == 16;
+}
+// batched Hessian items are numbered in 32 bits, with room for the tickets drawn beyond the end
+inline bool hess_items_fit(long long rows, int rows_per_item, long long n_emulators) {
+  return (rows + rows_per_item - 1) / rows_per_item * n_emulators <= 0x7fffffffLL - 4 * 1024 * 1024;
+}
+
+// hessian_win_kernel, one call = at most two launches.  The LDSOUT instance (whole-line stores through
+// LDS) takes the whole rows_per_item-row groups of the call when the kernel D has 16-byte rows
+// (lds_out_d), the caller's rows are exactly D long and both pointers are 16-byte aligned; KL 3 when
+// the instance without the last k-step exists for this block count (short_last) and the training set
+// leaves that k-step empty.  What is left, and every other call, goes to the direct-store instance.
+struct WinPlan {
+  int ldsout_kl;        // 0: no LDSOUT launch; 3 or 4: its KL
+  long long main_rows;  // rows of the LDSOUT launch (a multiple of rows_per_item)
+  GridPlan main;
+  long long rest_rows;  // rows of the direct-store launch (0: none)
+  GridPlan rest;
+};
+inline WinPlan plan_hess_win(long long rows, int rows_per_item, int n_emulators, int cap, bool lds_out_d,
+                             bool exact_d, bool aligned16, bool short_last, int n_ksteps, int kernel_nb) {
+  WinPlan w = {0, 0, {0, 0}, rows, {0, 0}};
+  const long long m_main = rows / rows_per_item * rows_per_item;
+  if (lds_out_d && m_main > 0 && exact_d && aligned16) {
+    w.ldsout_kl = short_last && n_ksteps == 4 * kernel_nb - 1 ? 3 : 4;
+    w.main_rows = m_main;
+    w.main = plan_grid(m_main, rows_per_item, n_emulators, cap);
+    w.rest_rows = rows - m_main;
+  }
+  if (w.rest_rows > 0) w.rest = plan_grid(w.rest_rows, rows_per_item, n_emulators, cap);
+  return w;
+}
+
+// reconstruct_kernel: the wide geometry (512 threads x 3 vectors) for band counts that one such
+// workgroup covers whole and a narrow one (256 x 2) cannot; vec = elements per 16 bytes
+inline bool recon_wide_default(int n_bands, int vec) { return n_bands > 256 * 2 * vec && n_bands <= 512 * 3 * vec; }
+// items = 64-row tiles x band chunks of bands_per_wg; memory-bound, so a few workgroups per CU
+// (cap), and every workgroup gets the same number of items (+-1): no workgroup is left with a
+// whole extra round at the end
+inline GridPlan plan_recon(long long n_rows, int rows_per_item, long long n_bands, long long bands_per_wg, long long cap) {
+  GridPlan p;
+  const long long chunks = (n_bands + bands_per_wg - 1) / bands_per_wg;
+  p.items = (n_rows + rows_per_item - 1) / rows_per_item * chunks;
+  const long long rounds = (p.items + cap - 1) / cap;
+  p.workgroups = (int)((p.items + rounds - 1) / rounds);
+  return p;
+}
+inline long long recon_cap(int compute_units, bool wide) { return (long long)compute_units * (wide ? 4 : 8); }
+
+}  // namespace gpk

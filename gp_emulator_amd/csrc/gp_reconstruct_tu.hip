@@ -1,6 +1,7 @@
 // reconstruct_kernel<T, PT, THREADS, NV> launchers: PT in {4, 8, 12, 16}, two geometries;
 // both dtypes in one unit.
 #include "gp_reconstruct_kernel.hpp"
+#include "gp_launch_plan.hpp"
 
 namespace gpk {
 
@@ -18,13 +19,8 @@ static hipError_t launch_geo(const ReconArgs<T>& a, int grid, hipStream_t stream
 template <typename T>
 static hipError_t launch_recon(const ReconArgs<T>& a, int wide, int cus, hipStream_t stream) {
   const long long bw = wide ? recon_bands_per_wg<T, 512, 3>() : recon_bands_per_wg<T, 256, 2>();
-  const long long chunks = (a.B + bw - 1) / bw;
-  const long long items = (a.R + rkRows - 1) / rkRows * chunks;
-  // memory-bound: a few blocks per CU, grid-stride; every block gets the same number of items
-  // (+-1) so that no block is left with a whole extra round at the end
-  const long long cap = (long long)cus * (wide ? 4 : 8);
-  const long long rounds = (items + cap - 1) / cap;
-  const int grid = (int)((items + rounds - 1) / rounds);
+  // items, and the balanced grid over them: plan_recon (gp_launch_plan.hpp)
+  const int grid = plan_recon(a.R, rkRows, a.B, bw, recon_cap(cus, wide != 0)).workgroups;
   return wide ? launch_geo<T, 512, 3>(a, grid, stream) : launch_geo<T, 256, 2>(a, grid, stream);
 }
 

@@ -298,6 +298,32 @@ int gp_frag_index(int kernel_nb, int I, int J, int s);
 int gp_kernel_ksteps(int n_train, int n_inputs, int* ksteps);
 int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kernel_nb,
                   int64_t* xa_len, int64_t* frags_len);
+/* How a device call would be launched (no GPU needed; computed by the helpers the launch path itself calls,
+ * gp_launch_plan.hpp, under the same switches GP_NO_FEW, GP_HESS_VALU, GP_RECON_WIDE).  Every hot kernel is
+ * persistent: a launch takes min(items, compute_units x workgroups per CU) workgroups and each walks the work
+ * items it is dealt; an item is rows_per_item test rows of one emulator (reconstruct: 64 rows of one band chunk).
+ * items > workgroups means that workgroups run several items.  op = GP_OP_RECONSTRUCT: n_inputs is n_pcs and
+ * aux n_bands (n_train unused); aux is unused elsewhere.  aligned16: the row and output pointers of a Hessian
+ * call are both 16-byte aligned.  kernel is a GP_PLAN_* value.  The windowed Hessian runs its whole 64-row groups
+ * on an LDSOUT instance and the rows behind them in a second, direct-store launch: rest_items / rest_workgroups
+ * (0 when there is no second launch).  Any output pointer may be NULL.  Unsupported shapes fail as gp_pack_sizes
+ * does. */
+#define GP_OP_PREDICT 0
+#define GP_OP_MEAN_GRAD 1
+#define GP_OP_HESSIAN 2
+#define GP_OP_RECONSTRUCT 3
+#define GP_PLAN_PREDICT_FEW 1      /* predict_few_kernel: a workgroup per 16-row tile */
+#define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
+#define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
+#define GP_PLAN_HESS_VALU 4        /* hessian_kernel */
+#define GP_PLAN_HESS_WIN_KL3 5     /* hessian_win_kernel, LDSOUT, last k-step not issued */
+#define GP_PLAN_HESS_WIN_KL4 6     /* hessian_win_kernel, LDSOUT */
+#define GP_PLAN_HESS_WIN_DIRECT 7  /* hessian_win_kernel, direct stores, for the whole call */
+#define GP_PLAN_RECON_NARROW 8     /* reconstruct_kernel, 256 threads x 2 vectors */
+#define GP_PLAN_RECON_WIDE 9       /* reconstruct_kernel, 512 threads x 3 vectors */
+int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
+                   int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
+                   int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
 int gp_pack_model_f64(const double* expX, const double* inputs, const double* invQt,
                       const double* invQ, int n_train, int n_inputs, int theta_size,
                       double* xa, double* frags, double* sd, double* b);
