@@ -71,6 +71,13 @@ SIGNATURES = {
     "gp_content_digest": (ctypes.c_uint64, [c_void_p, c_void_p, c_int]),
     "gp_mv_predict_host_checked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int, ctypes.c_uint64]),
+    "gp_mv_misfit_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64,
+                                    c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int]),
+    "gp_mv_gauss_newton_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
+    "gp_mv_misfit_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                  c_void_p, c_i64, c_int, c_void_p]),
+    "gp_mv_misfit_host_checked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                          c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_uint64]),
     "gp_frag_index": (c_int, [c_int, c_int, c_int, c_int]),
     "gp_likelihood_batch_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -365,6 +372,22 @@ class Context:
         check(self.lib.gp_reconstruct_device(self.h, code, d_basis, d_coef, d_out, int(n_rows),
                                              int(n_pcs), int(n_bands)), "gp_reconstruct_device")
 
+    def mv_misfit_device(self, dtype, d_basis, d_mu, d_deriv, d_obs, obs_stride, d_weights, weights_stride,
+                         d_cost, d_coef, d_grad, n_rows, n_pcs, n_bands, n_inputs):
+        """cost [M], coef [P][M] and grad [M][D] of the observation misfit from the per-PC mean [P][M] and
+        gradient [P][M][D] on the device (asynchronous; ``gp_mv_misfit_device``).  Strides in elements, 0 = one
+        vector for all rows; ``d_weights`` and any output may be None."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_mv_misfit_device(self.h, code, d_basis, d_mu, d_deriv, d_obs, int(obs_stride), d_weights,
+                                           int(weights_stride), d_cost, d_coef, d_grad, int(n_rows), int(n_pcs),
+                                           int(n_bands), int(n_inputs)), "gp_mv_misfit_device")
+
+    def mv_gauss_newton_device(self, dtype, d_deriv, d_A, d_gn, n_rows, n_pcs, n_inputs):
+        """gn[m] = deriv[:, m].T @ A @ deriv[:, m] on the device, exactly symmetric (asynchronous)."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_mv_gauss_newton_device(self.h, code, d_deriv, d_A, d_gn, int(n_rows), int(n_pcs),
+                                                 int(n_inputs)), "gp_mv_gauss_newton_device")
+
     def likelihood_batch(self, thetas, inputs, targets, want_inverse=False):
         """cost (E,), grad (E, D+2) [and invQ (E, N, N), invQt (E, N)] of the training
         objective for E hyper-parameter sets; targets (N,) shared or (E, N)."""
@@ -649,24 +672,25 @@ class BatchModel(Model):
         return res
 
 
-GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT = 0, 1, 2, 3
+GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT = 0, 1, 2, 3, 4
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
-                6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide"}
+                6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
+                10: "misfit"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
-             "reconstruct": GP_OP_RECONSTRUCT}
+             "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT}
 
 
 def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_pcs=0, n_bands=0,
                 compute_units=256, aligned16=True):
-    """How the device call ``op`` ("predict", "mean_grad", "hessian", "reconstruct") on ``n_rows`` rows would be
+    """How the device call ``op`` ("predict", "mean_grad", "hessian", "reconstruct", "misfit") on ``n_rows`` rows would be
     launched on a device of ``compute_units`` (``gp_launch_plan``: host arithmetic shared with the launch path, no
     GPU needed).  Returns dict(kernel, rows_per_item, items, workgroups, rest_items, rest_workgroups): the
     kernel family and instance (a ``PLAN_KERNELS`` name), the rows of one work item, and the work items and
     workgroups of the launch (``rest_*``: the windowed Hessian's second launch for the rows behind the last whole
     64-row group).  ``items > workgroups``: workgroups run several items.  ``aligned16``: a Hessian call's row and
-    output pointers are 16-byte aligned.  reconstruct takes ``n_pcs`` and ``n_bands``."""
+    output pointers are 16-byte aligned.  reconstruct and misfit take ``n_pcs`` and ``n_bands``."""
     code = _PLAN_OPS[op]
-    recon = code == GP_OP_RECONSTRUCT
+    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT)
     k, wg, rwg, rpi = c_int(0), c_int(0), c_int(0), c_int(0)
     items, ritems = c_i64(0), c_i64(0)
     check(load().gp_launch_plan(

@@ -29,6 +29,7 @@
 #include "gp_hessian_combine_kernel.hpp"
 #include "gp_host_pool.hpp"
 #include "gp_launch_plan.hpp"
+#include "gp_misfit_kernel.hpp"
 #include "gp_predict_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
 #include "gp_train_args.hpp"
@@ -37,6 +38,10 @@ namespace gpk {
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);
 hipError_t launch_reconstruct_f32(const ReconArgs<float>&, int wide, int cus, hipStream_t);
 hipError_t launch_reconstruct_f64(const ReconArgs<double>&, int wide, int cus, hipStream_t);
+hipError_t launch_misfit_f32(const MisfitArgs<float>&, int cus, hipStream_t);
+hipError_t launch_misfit_f64(const MisfitArgs<double>&, int cus, hipStream_t);
+hipError_t launch_gauss_newton_f32(const float* deriv, const float* A, float* gn, long long M, int P, int D, int cus, hipStream_t);
+hipError_t launch_gauss_newton_f64(const double* deriv, const double* A, double* gn, long long M, int P, int D, int cus, hipStream_t);
 hipError_t launch_few_f32(int, const PredictArgs<float>&, int, int, bool, hipStream_t);
 hipError_t launch_few_f64(int, const PredictArgs<double>&, int, int, bool, hipStream_t);
 hipError_t launch_generic_f32(const GenericArgs<float>&, int, hipStream_t);
@@ -1685,6 +1690,130 @@ static int mv_predict_host(gp_ctx* ctx, const gp_model* m, const T* d_basis, con
   return stale ? GP_STALE : GP_OK;
 }
 
+// ---- observation misfit of a multivariate emulator (gp_misfit_kernel.hpp) ---------------------------------------
+static int misfit_on(gp_ctx* ctx, int dtype, const void* d_basis, const void* d_mu, const void* d_deriv, const void* d_obs,
+                     int64_t obs_stride, const void* d_weights, int64_t weights_stride, void* d_cost, void* d_coef,
+                     void* d_grad, int64_t n_rows, int n_pcs, int n_bands, int n_inputs, hipStream_t stream) {
+  if (n_rows < 0 || n_pcs <= 0 || n_bands <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_pcs > gpk::mkMaxPcs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels are compiled for n_pcs <= %d", gpk::mkMaxPcs);
+  if (n_inputs > gpk::mkMaxInputs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels serve n_inputs <= %d", gpk::mkMaxInputs);
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if ((obs_stride != 0 && obs_stride < n_bands) || (d_weights && weights_stride != 0 && weights_stride < n_bands))
+    return fail(GP_ERR_INVALID, "a row stride is 0 (one vector for all rows) or >= n_bands");
+  if (n_rows == 0) return GP_OK;
+  if (!d_basis || !d_mu || !d_obs) return fail(GP_ERR_INVALID, "null device pointer");
+  if (d_grad && !d_deriv) return fail(GP_ERR_INVALID, "the gradient needs d_deriv");
+  hipError_t e;
+  if (dtype == GP_F64) {
+    gpk::MisfitArgs<double> a{(const double*)d_basis, (const double*)d_mu, (const double*)d_deriv, (const double*)d_obs,
+                              (const double*)d_weights, (double*)d_cost, (double*)d_coef, (double*)d_grad,
+                              n_rows, obs_stride, weights_stride, n_pcs, n_bands, n_inputs};
+    e = gpk::launch_misfit_f64(a, ctx->compute_units, stream);
+  } else {
+    gpk::MisfitArgs<float> a{(const float*)d_basis, (const float*)d_mu, (const float*)d_deriv, (const float*)d_obs,
+                             (const float*)d_weights, (float*)d_cost, (float*)d_coef, (float*)d_grad,
+                             n_rows, obs_stride, weights_stride, n_pcs, n_bands, n_inputs};
+    e = gpk::launch_misfit_f32(a, ctx->compute_units, stream);
+  }
+  if (e != hipSuccess) return fail(GP_ERR_HIP, "misfit kernel launch: %s", hipGetErrorString(e));
+  return GP_OK;
+}
+
+static int gauss_newton_on(gp_ctx* ctx, int dtype, const void* d_deriv, const void* d_A, void* d_gn, int64_t n_rows,
+                           int n_pcs, int n_inputs, hipStream_t stream) {
+  if (n_rows < 0 || n_pcs <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_pcs > gpk::mkMaxPcs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels are compiled for n_pcs <= %d", gpk::mkMaxPcs);
+  if (n_inputs > gpk::mkMaxInputs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels serve n_inputs <= %d", gpk::mkMaxInputs);
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_rows == 0) return GP_OK;
+  if (!d_deriv || !d_A || !d_gn) return fail(GP_ERR_INVALID, "null device pointer");
+  const hipError_t e = dtype == GP_F64
+      ? gpk::launch_gauss_newton_f64((const double*)d_deriv, (const double*)d_A, (double*)d_gn, n_rows, n_pcs, n_inputs,
+                                     ctx->compute_units, stream)
+      : gpk::launch_gauss_newton_f32((const float*)d_deriv, (const float*)d_A, (float*)d_gn, n_rows, n_pcs, n_inputs,
+                                     ctx->compute_units, stream);
+  if (e != hipSuccess) return fail(GP_ERR_HIP, "gauss-newton kernel launch: %s", hipGetErrorString(e));
+  return GP_OK;
+}
+
+// rows of `width` reals, `stride` reals apart on the host, packed on the device
+template <typename T>
+static hipError_t upload_rows(T* dst, const T* src, int64_t stride, int64_t rows, int64_t width, hipStream_t st) {
+  if (stride == width || rows == 1) return hipMemcpyAsync(dst, src, (size_t)rows * width * sizeof(T), hipMemcpyHostToDevice, st);
+  return hipMemcpy2DAsync(dst, (size_t)width * sizeof(T), src, (size_t)stride * sizeof(T), (size_t)width * sizeof(T),
+                          (size_t)rows, hipMemcpyHostToDevice, st);
+}
+
+// The data term of a variational retrieval in ONE call: rows, observations and weights up, the batched mean+gradient
+// predict of all principal components, the misfit kernel (and the Gauss-Newton kernel when A and want_gn are given),
+// cost | grad | coef | gn down in one copy, one synchronisation.  Same scratch, digest and GP_STALE contract as
+// mv_predict_host.
+constexpr size_t kMvUploadMax = (size_t)1 << 30;      // bytes of per-row observations + weights per call
+template <typename T>
+static int mv_misfit_host(gp_ctx* ctx, const gp_model* m, const T* d_basis, const T* y, int64_t y_stride, const T* obs,
+                          int64_t obs_stride, const T* weights, int64_t weights_stride, const T* A, int64_t M, int n_bands,
+                          T* out, const host_check* chk = nullptr) {
+  const int D = m->n_inputs, P = m->n_emulators;
+  const size_t n_y = (size_t)M * D, n_gp = (size_t)P * M * (1 + D);
+  const size_t n_obs = (size_t)(obs_stride ? M : 1) * n_bands;
+  const size_t n_w = weights ? (size_t)(weights_stride ? M : 1) * n_bands : 0;
+  const size_t n_res = (size_t)M * (1 + D + P), n_gn = A ? (size_t)M * D * D : 0, n_A = A ? (size_t)P * P : 0;
+  if (((obs_stride ? n_obs : 0) + (weights_stride ? n_w : 0)) * sizeof(T) > kMvUploadMax)
+    return fail(GP_ERR_UNSUPPORTED, "gp_mv_misfit_host uploads at most %zu MiB of per-row observations and weights per call: "
+                "split the rows", kMvUploadMax >> 20);
+  if ((n_res + n_gn) * sizeof(T) > kMvResultMax)
+    return fail(GP_ERR_UNSUPPORTED, "gp_mv_misfit_host returns at most %zu MiB per call: split the rows", kMvResultMax >> 20);
+  HIP_TRY(hipSetDevice(ctx->device));
+  int rc = ensure_scratch(ctx, (n_y + n_gp + n_res + n_gn + n_A + n_obs + n_w) * sizeof(T));
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  T* d_y = (T*)ctx->scratch;
+  T* d_mu = d_y + n_y;
+  T* d_der = d_mu + (size_t)P * M;
+  T* d_cost = d_y + n_y + n_gp;            // cost [M] | grad [M][D] | coef [P][M] | gn [M][D][D]
+  T* d_grad = d_cost + M;
+  T* d_coef = d_grad + (size_t)M * D;
+  T* d_gn = d_coef + (size_t)P * M;
+  T* d_A = d_gn + n_gn;
+  T* d_obs = d_A + n_A;
+  T* d_w = d_obs + n_obs;
+  HIP_TRY(upload_rows(d_y, y, y_stride, M, D, st));
+  HIP_TRY(upload_rows(d_obs, obs, obs_stride, obs_stride ? M : 1, n_bands, st));
+  if (weights) HIP_TRY(upload_rows(d_w, weights, weights_stride, weights_stride ? M : 1, n_bands, st));
+  if (A) HIP_TRY(hipMemcpyAsync(d_A, A, n_A * sizeof(T), hipMemcpyHostToDevice, st));
+  rc = predict_device<T>(ctx, m, d_y, d_mu, nullptr, d_der, M, GP_DERIV_ROWMAJOR, st);   // mean+gradient kernels
+  const int dtype = sizeof(T) == 8 ? GP_F64 : GP_F32;
+  if (!rc) rc = misfit_on(ctx, dtype, d_basis, d_mu, d_der, d_obs, obs_stride ? n_bands : 0, weights ? d_w : nullptr,
+                          weights_stride ? n_bands : 0, d_cost, d_coef, d_grad, M, P, n_bands, D, st);
+  if (!rc && A) rc = gauss_newton_on(ctx, dtype, d_der, d_A, d_gn, M, P, D, st);
+  bool stale = false;
+  if (!rc && chk && chk->n_blocks > 0) {      // while the device works (see mv_predict_host)
+    (void)hipStreamQuery(st);
+    stale = content_digest(chk->blocks, chk->nbytes, chk->n_blocks, &host_pool(ctx)) != chk->expected;
+  }
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(out, d_cost, (n_res + n_gn) * sizeof(T), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);       // whatever happened, leave the stream idle
+  if (rc) return rc;
+  if (e != hipSuccess || es != hipSuccess)
+    return fail(GP_ERR_HIP, "mv misfit: %s", hipGetErrorString(e != hipSuccess ? e : es));
+  return stale ? GP_STALE : GP_OK;
+}
+
+// host-side arguments of gp_mv_misfit_host[_checked]; sizes and kernel limits are misfit_on's to check
+static int mv_misfit_args(gp_ctx* ctx, const gp_model* model, const void* d_basis, const void* y, int64_t y_stride,
+                          const void* obs, int64_t obs_stride, const void* weights, int64_t weights_stride, int n_bands,
+                          void* out) {
+  if (!d_basis || !y || !obs || !out) return fail(GP_ERR_INVALID, "null pointer");
+  if (model->device != ctx->device) return fail(GP_ERR_INVALID, "model lives on device %d, context on %d", model->device, ctx->device);
+  if (model->n_emulators > gpk::mkMaxPcs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels are compiled for n_pcs <= %d", gpk::mkMaxPcs);
+  if (model->n_inputs > gpk::mkMaxInputs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels serve n_inputs <= %d", gpk::mkMaxInputs);
+  if (y_stride < model->n_inputs || (obs_stride != 0 && obs_stride < n_bands) ||
+      (weights && weights_stride != 0 && weights_stride < n_bands))
+    return fail(GP_ERR_INVALID, "bad row stride");
+  return GP_OK;
+}
+
 extern "C" {
 
 int gp_model_create_f64(gp_ctx* ctx, const double* expX, const double* inputs, const double* invQt,
@@ -1768,6 +1897,13 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     k = wide ? GP_PLAN_RECON_WIDE : GP_PLAN_RECON_NARROW;
     rpi = gpk::rkRows;
     g = gpk::plan_recon(n_rows, gpk::rkRows, aux, bw, gpk::recon_cap(compute_units, wide != 0));
+  } else if (op == GP_OP_MISFIT) {
+    // (n_inputs = n_pcs here; aux = n_bands)
+    if (n_inputs <= 0 || aux <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    if (n_inputs > gpk::mkMaxPcs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels are compiled for n_pcs <= %d", gpk::mkMaxPcs);
+    k = GP_PLAN_MISFIT;
+    rpi = gpk::mkRows;
+    g = gpk::plan_misfit(n_rows, gpk::mkRows, gpk::misfit_cap(compute_units));
   } else if (op == GP_OP_PREDICT || op == GP_OP_MEAN_GRAD || op == GP_OP_HESSIAN) {
     int kd, knb;
     int rc = pick_kernel(n_train, n_inputs, &kd, &knb);
@@ -2064,6 +2200,50 @@ int gp_mv_predict_host_checked(gp_ctx* ctx, const gp_model* model, const void* d
   if (model->dtype == GP_F64)
     return guarded([&] { return mv_predict_host<double>(ctx, model, (const double*)d_basis, (const double*)y, n_rows, n_bands, (double*)fwd, (double*)jac, &chk); });
   return guarded([&] { return mv_predict_host<float>(ctx, model, (const float*)d_basis, (const float*)y, n_rows, n_bands, (float*)fwd, (float*)jac, &chk); });
+}
+
+int gp_mv_misfit_device(gp_ctx* ctx, int dtype, const void* d_basis, const void* d_mu, const void* d_deriv,
+                        const void* d_obs, int64_t obs_stride, const void* d_weights, int64_t weights_stride,
+                        void* d_cost, void* d_coef, void* d_grad, int64_t n_rows, int n_pcs, int n_bands, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return misfit_on(ctx, dtype, d_basis, d_mu, d_deriv, d_obs, obs_stride, d_weights, weights_stride, d_cost, d_coef, d_grad,
+                   n_rows, n_pcs, n_bands, n_inputs, ctx->stream);
+}
+
+int gp_mv_gauss_newton_device(gp_ctx* ctx, int dtype, const void* d_deriv, const void* d_A, void* d_gn, int64_t n_rows,
+                              int n_pcs, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return gauss_newton_on(ctx, dtype, d_deriv, d_A, d_gn, n_rows, n_pcs, n_inputs, ctx->stream);
+}
+
+int gp_mv_misfit_host(gp_ctx* ctx, const gp_model* model, const void* d_basis, const void* y, int64_t y_stride,
+                      const void* obs, int64_t obs_stride, const void* weights, int64_t weights_stride, const void* A,
+                      int64_t n_rows, int n_bands, void* out) {
+  return gp_mv_misfit_host_checked(ctx, model, d_basis, y, y_stride, obs, obs_stride, weights, weights_stride, A, n_rows,
+                                   n_bands, out, nullptr, nullptr, 0, 0);
+}
+
+int gp_mv_misfit_host_checked(gp_ctx* ctx, const gp_model* model, const void* d_basis, const void* y, int64_t y_stride,
+                              const void* obs, int64_t obs_stride, const void* weights, int64_t weights_stride,
+                              const void* A, int64_t n_rows, int n_bands, void* out, const void* const* blocks,
+                              const int64_t* nbytes, int n_blocks, uint64_t expected) {
+  if (!ctx || !model) return fail(GP_ERR_INVALID, "null context or model");
+  if (n_rows < 0 || n_bands <= 0 || n_blocks < 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_blocks > 0 && (!blocks || !nbytes)) return fail(GP_ERR_INVALID, "null pointer");
+  host_check chk;
+  chk.blocks = blocks; chk.nbytes = nbytes; chk.n_blocks = n_blocks; chk.expected = expected;
+  if (n_rows == 0) return n_blocks > 0 && content_digest(blocks, nbytes, n_blocks) != expected ? GP_STALE : GP_OK;
+  const int rc = mv_misfit_args(ctx, model, d_basis, y, y_stride, obs, obs_stride, weights, weights_stride, n_bands, out);
+  if (rc) return rc;
+  if (model->dtype == GP_F64)
+    return guarded([&] { return mv_misfit_host<double>(ctx, model, (const double*)d_basis, (const double*)y, y_stride,
+                                                       (const double*)obs, obs_stride, (const double*)weights, weights_stride,
+                                                       (const double*)A, n_rows, n_bands, (double*)out, &chk); });
+  return guarded([&] { return mv_misfit_host<float>(ctx, model, (const float*)d_basis, (const float*)y, y_stride,
+                                                    (const float*)obs, obs_stride, (const float*)weights, weights_stride,
+                                                    (const float*)A, n_rows, n_bands, (float*)out, &chk); });
 }
 
 int gp_likelihood_batch_f64(gp_ctx* ctx, int n_sets, const double* theta, const double* inputs,

@@ -82,4 +82,15 @@ inline GridPlan plan_recon(long long n_rows, int rows_per_item, long long n_band
 }
 inline long long recon_cap(int compute_units, bool wide) { return (long long)compute_units * (wide ? 4 : 8); }
 
+// misfit_kernel: items = groups of rows_per_item rows (a 16-row tile per wave, all bands); four 4-wave
+// workgroups per CU (four waves per SIMD hide the observation stream), rounds balanced as above
+inline long long misfit_cap(int compute_units) { return (long long)compute_units * 4; }
+inline GridPlan plan_misfit(long long n_rows, int rows_per_item, long long cap) {
+  GridPlan p;
+  p.items = (n_rows + rows_per_item - 1) / rows_per_item;
+  const long long rounds = (p.items + cap - 1) / cap;
+  p.workgroups = (int)((p.items + rounds - 1) / rounds);
+  return p;
+}
+
 }  // namespace gpk

@@ -250,6 +250,137 @@ class MultivariateEmulator(object):
             r0 = r1
         return (fwd, jac) if do_deriv else fwd
 
+    # ---- observation misfit: the data term of a variational retrieval -------------------------------
+    def _misfit_args(self, Y, obs, weights, gauss_newton):
+        Y = np.atleast_2d(Y)
+        M = Y.shape[0]
+        B = self.basis_functions.shape[1]
+        obs = np.asarray(obs)
+        if obs.shape not in ((B,), (M, B)):
+            raise ValueError("obs must be (%d,) or (%d, %d), got %s" % (B, M, B, obs.shape))
+        if weights is not None:
+            weights = np.asarray(weights)
+            if weights.shape not in ((B,), (M, B)):
+                raise ValueError("weights must be (%d,) or (%d, %d), got %s" % (B, M, B, weights.shape))
+            if gauss_newton and weights.ndim == 2:
+                raise ValueError("gauss_newton=True needs weights shared by all rows: None or (%d,)" % B)
+        return Y, obs, weights
+
+    def _gauss_newton_matrix(self, weights):
+        """``basis diag(w) basis^T`` (P, P) in float64, formed once per call on the host."""
+        b64 = np.ascontiguousarray(self.basis_functions, dtype=np.float64)
+        return (b64 if weights is None else b64 * np.asarray(weights, dtype=np.float64)) @ b64.T
+
+    def misfit(self, y, obs, weights=None, is_gpu=False, precision=np.float64, do_deriv=True, gauss_newton=False,
+               return_coef=False):
+        """``misfit_many`` at ONE state vector ``y`` -- the call an optimiser makes per iteration: the scalar
+        cost, then (when asked for) ``grad (N_params,)``, ``gn (N_params, N_params)`` and ``coef (n_pcs,)``."""
+        y = np.atleast_2d(y)
+        if y.shape[0] != 1:
+            raise ValueError("misfit takes one input vector; misfit_many takes rows")
+        B = self.basis_functions.shape[1]
+        if np.shape(obs) != (B,) or (weights is not None and np.shape(weights) != (B,)):
+            raise ValueError("obs and weights must be (%d,)" % B)
+        out = self.misfit_many(y, obs, weights=weights, is_gpu=is_gpu, precision=precision, do_deriv=do_deriv,
+                               gauss_newton=gauss_newton, return_coef=return_coef)
+        if isinstance(out, tuple):
+            return tuple(o[0] for o in out)
+        return out[0]
+
+    def misfit_many(self, Y, obs, weights=None, is_gpu=True, precision=np.float64, do_deriv=True, gauss_newton=False,
+                    return_coef=False):
+        """Observation misfit ``J(y) = 1/2 sum_b w_b (f_b(y) - obs_b)^2`` of the reconstructed output ``f`` for M
+        input rows: ``cost (M,)`` and then, in this order and when asked for, its gradient ``grad (M, N_params)``
+        (``do_deriv``) ``= Jac (w * r)`` with ``r = f - obs``, the Gauss-Newton term ``gn (M, N_params, N_params)
+        = Jac diag(w) Jac^T`` (``gauss_newton``; weights shared by all rows) and ``coef (M, n_pcs)``
+        (``return_coef``) ``= basis (w * r)``, which ``hessian_many(Y, coef=coef)`` turns into the curvature term:
+        ``gn + hessian_many(Y, coef=coef)`` is the full second-order data term.  ``obs`` is ``(N_full,)`` or
+        ``(M, N_full)``; ``weights`` None (all 1), ``(N_full,)`` or ``(M, N_full)``.  Not in the reference, whose
+        caller contracts ``predict``'s Jacobian on the host.
+
+        Nothing of size ``N_params x N_full`` is formed: ``coef[p] = sum_b basis[p, b] w_b r_b`` and ``grad[d] =
+        sum_p coef[p] dmu_p/dy_d``.  The numpy branch states exactly that on the per-PC ``gp.predict`` outputs.  On
+        the GPU a call is one library call (``gp_mv_misfit_host_checked``) on the device-resident emulator: rows,
+        observations and weights up, the mean+gradient predict, the misfit kernel, ``1 + N_params + n_pcs``
+        numbers per row down."""
+        Y, obs, weights = self._misfit_args(Y, obs, weights, gauss_newton)
+        M, D = Y.shape
+        P, B = self.n_pcs, self.basis_functions.shape[1]
+        A = self._gauss_newton_matrix(weights) if gauss_newton else None
+        if not is_gpu:
+            basis = np.asarray(self.basis_functions, dtype=np.float64)
+            out = [gp.predict(Y) for gp in self.emulators]
+            mu = np.stack([o[0] for o in out])                      # (P, M)
+            grads = np.stack([o[2] for o in out])                   # (P, M, D)
+            r = mu.T @ basis - obs
+            wr = r if weights is None else weights * r
+            cost = 0.5 * np.sum(wr * r, axis=1)
+            coef = wr @ basis.T                                      # (M, P)
+            res = [cost]
+            if do_deriv:
+                res.append(np.einsum("mp,pmd->md", coef, grads))
+            if gauss_newton:
+                gn = np.triu(np.einsum("pmd,pq,qme->mde", grads, A, grads))
+                res.append(gn + np.swapaxes(np.triu(gn, 1), 1, 2))   # upper triangle mirrored: exactly symmetric
+            if return_coef:
+                res.append(coef)
+            return tuple(res) if len(res) > 1 else cost
+        from . import _lib
+        dt = np.dtype(precision)
+        isz = dt.itemsize
+        st = self._gpu_state(dt)
+        ctx = st["ctx"]
+        Yc = np.ascontiguousarray(Y, dtype=dt)
+        obs_c = np.ascontiguousarray(obs, dtype=dt)
+        w_c = None if weights is None else np.ascontiguousarray(weights, dtype=dt)
+        A_c = None if A is None else np.ascontiguousarray(A, dtype=dt)
+        per_obs, per_w = obs_c.ndim == 2, w_c is not None and w_c.ndim == 2
+        # rows per library call: at most 1 GiB of per-row observations and weights up, 1 GiB of results down
+        n_row = 1 + D + P + (D * D if gauss_newton else 0)
+        step = (1 << 30) // (n_row * isz)
+        if per_obs or per_w:
+            step = min(step, (1 << 30) // ((per_obs + per_w) * B * isz))
+        step = max(1, step)
+        cost = np.empty(M, dt)
+        grad = np.empty((M, D), dt)
+        coef = np.empty((M, P), dt)
+        gn = np.empty((M, D, D), dt) if gauss_newton else None
+        buf = np.empty(min(M, step) * n_row, dt)
+        r0 = 0
+        while r0 < M:
+            r1 = min(M, r0 + step)
+            n = r1 - r0
+            blocks = st["blocks"].refresh()
+            rc = ctx.lib.gp_mv_misfit_host_checked(
+                ctx.h, st["batch"].h, st["d_basis"], _lib._ptr(Yc[r0:r1]), D,
+                _lib._ptr(obs_c[r0:r1] if per_obs else obs_c), B if per_obs else 0,
+                None if w_c is None else _lib._ptr(w_c[r0:r1] if per_w else w_c), B if per_w else 0,
+                None if A_c is None else _lib._ptr(A_c), n, B, _lib._ptr(buf),
+                blocks.ptrs, blocks.lens, blocks.n, blocks.expected)
+            if rc == _lib.GP_STALE:
+                # the host arrays were edited in place since the resident copy was made: rebuild it and run the
+                # same rows again (the staleness contract of predict_many)
+                self._release(st)
+                del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
+                st = self._gpu_state(dt)
+                ctx = st["ctx"]
+                continue
+            _lib.check(rc, "gp_mv_misfit_host_checked")
+            cost[r0:r1] = buf[:n]
+            grad[r0:r1] = buf[n:n * (1 + D)].reshape(n, D)
+            coef[r0:r1] = buf[n * (1 + D):n * (1 + D + P)].reshape(P, n).T
+            if gauss_newton:
+                gn[r0:r1] = buf[n * (1 + D + P):n * n_row].reshape(n, D, D)
+            r0 = r1
+        res = [cost]
+        if do_deriv:
+            res.append(grad)
+        if gauss_newton:
+            res.append(gn)
+        if return_coef:
+            res.append(coef)
+        return tuple(res) if len(res) > 1 else cost
+
     # ---- second derivatives ---------------------------------------------------------------------
     def hessian(self, y, is_gpu=False, weights=None):
         """Hessian of the reconstructed output at ONE input vector ``y``: ``(N_params, N_params, N_full)`` (axes
@@ -264,18 +395,28 @@ class MultivariateEmulator(object):
             weights = np.atleast_2d(weights)
         return self.hessian_many(y, is_gpu=is_gpu, weights=weights)[0]
 
-    def hessian_many(self, Y, is_gpu=True, precision=np.float64, weights=None):
+    def hessian_many(self, Y, is_gpu=True, precision=np.float64, weights=None, coef=None):
         """``(M, N_params, N_params, N_full)`` Hessians of the reconstructed outputs for M input rows, or with
         ``weights (M, N_full)`` their weighted sums over the output ``(M, N_params, N_params)``.  The numpy
         branch is ``sum_p basis[p] * emulators[p].hessian(Y)``.  On the GPU all per-PC Hessians are ONE batched
         launch on the device-resident emulator (``_gpu_state``; the host arrays are digested before use and
         the resident copy rebuilt when they were edited in place); the full form is then the reconstruction
         kernel over rows ``(m, d, d2)``, the weighted form ``c[p, m] = sum_b basis[p, b] weights[m, b]`` and the
-        device's weighted sum over the PCs -- only the result crosses PCIe."""
+        device's weighted sum over the PCs -- only the result crosses PCIe.  ``coef (M, n_pcs)`` is an
+        alternative to ``weights`` (the two exclude each other): the projection ``basis @ weights[m]`` itself, as
+        ``misfit_many(return_coef=True)`` returns it from the device, so that nothing of size ``N_full`` is
+        touched on the host."""
         Y = np.atleast_2d(Y)
         M, D = Y.shape
         B = self.basis_functions.shape[1]
         basis = np.asarray(self.basis_functions)
+        if coef is not None:
+            if weights is not None:
+                raise ValueError("give weights or coef, not both")
+            coef = np.asarray(coef, dtype=np.float64)
+            if coef.shape != (M, self.n_pcs):
+                raise ValueError("coef must be (%d, %d), got %s" % (M, self.n_pcs, coef.shape))
+            coef = coef.T                                          # (P, M), as the projection below
         if weights is not None:
             weights = np.asarray(weights, dtype=np.float64)
             if weights.shape != (M, B):
@@ -286,7 +427,7 @@ class MultivariateEmulator(object):
             coef = np.stack([b64 @ weights[m] for m in range(M)], axis=1) if M else np.zeros((self.n_pcs, 0))
         if not is_gpu:
             hp = np.stack([gp.hessian(Y) for gp in self.emulators])           # (P, M, D, D)
-            if weights is None:
+            if coef is None:
                 return np.einsum("pmde,pb->mdeb", hp, basis)
             return np.einsum("pmde,pm->mde", hp, coef)
         from . import _lib
@@ -300,7 +441,7 @@ class MultivariateEmulator(object):
             st = self._gpu_state(dt)
         ctx, batch = st["ctx"], st["batch"]
         Yc = np.ascontiguousarray(Y, dtype=dt)
-        if weights is not None:
+        if coef is not None:
             return np.array(batch.hessian_weighted(Yc, np.ascontiguousarray(coef, dtype=dt)))
         P, isz = self.n_pcs, dt.itemsize
         # rows per round: at most 1 GiB of results on the device (as gp_mv_predict_host)

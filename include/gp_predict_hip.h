@@ -276,6 +276,45 @@ int gp_mv_predict_host_checked(gp_ctx* ctx, const gp_model* model, const void* d
                                int64_t n_rows, int n_bands, void* fwd, void* jac,
                                const void* const* blocks, const int64_t* nbytes, int n_blocks, uint64_t expected);
 
+/* ---- observation misfit of a multivariate emulator -------------------------------------------------
+ * The data term of a variational retrieval, J(y) = 1/2 sum_b w_b (f_b(y) - obs_b)^2 with f = the reconstruction
+ * sum_p mu_p basis[p], and its gradient Jac^T (w o r), r = f - obs, for n_rows state vectors at once and WITHOUT the
+ * (n_rows, n_inputs, n_bands) Jacobian: from the per-PC outputs of the mean+gradient predict, d_mu [n_pcs][n_rows]
+ * and d_deriv [n_pcs][n_rows][n_inputs] (GP_DERIV_ROWMAJOR),
+ *   coef[p][m] = sum_b basis[p][b] w[m][b] r[m][b]     d_coef [n_pcs][n_rows]  (the d_weights of
+ *                                                       gp_hessian_weighted_device: the curvature term)
+ *   grad[m][d] = sum_p coef[p][m] deriv[p][m][d]        d_grad [n_rows][n_inputs]
+ *   cost[m]    = 1/2 sum_b w[m][b] r[m][b]^2            d_cost [n_rows]
+ * d_obs: row m at d_obs + m * obs_stride (elements; 0 = one observation vector for all rows, else >= n_bands).
+ * d_weights: NULL (all 1), or as d_obs with weights_stride.  Any of the three outputs may be NULL (d_grad needs
+ * d_deriv).  Device pointers of `dtype`, asynchronous on the context's stream; n_pcs <= 16, n_inputs <= 64
+ * (GP_ERR_UNSUPPORTED beyond).  No atomics: a row's results do not depend on the other rows of the call, on the
+ * row's place in it or on the grid, and two calls agree bit for bit. */
+int gp_mv_misfit_device(gp_ctx* ctx, int dtype, const void* d_basis, const void* d_mu, const void* d_deriv,
+                        const void* d_obs, int64_t obs_stride, const void* d_weights, int64_t weights_stride,
+                        void* d_cost, void* d_coef, void* d_grad, int64_t n_rows, int n_pcs, int n_bands, int n_inputs);
+/* Gauss-Newton term gn[m][d][e] = sum_pq deriv[p][m][d] A[p][q] deriv[q][m][e], d_gn [n_rows][n_inputs][n_inputs], for a
+ * device matrix d_A [n_pcs][n_pcs] (basis diag(w) basis^T when the weights are shared by all rows): the upper
+ * triangle is computed and mirrored, so the result is exactly symmetric. */
+int gp_mv_gauss_newton_device(gp_ctx* ctx, int dtype, const void* d_deriv, const void* d_A, void* d_gn, int64_t n_rows,
+                              int n_pcs, int n_inputs);
+/* The whole data term in one call, the counterpart of gp_mv_predict_host[_checked]: `model` is the batch of the
+ * n_pcs per-PC emulators, d_basis their basis on the device, y / obs / weights host rows of the model's dtype with
+ * row strides in elements (y_stride >= n_inputs; obs_stride and weights_stride 0 or >= n_bands; weights may be
+ * NULL), A an optional host matrix [n_pcs][n_pcs].  Rows, observations and weights up, mean+gradient predict, the
+ * misfit kernel (and the Gauss-Newton kernel when A is given), results down in one copy, one synchronisation.
+ * out (host, model's dtype) is filled as cost [n_rows] | grad [n_rows][n_inputs] | coef [n_pcs][n_rows] and, when A
+ * is given, | gn [n_rows][n_inputs][n_inputs].  At most 1 GiB of per-row observations and weights is uploaded and at
+ * most 1 GiB returned per call (GP_ERR_UNSUPPORTED beyond: split the rows).  _checked digests the host blocks
+ * between the launches and the copy back and returns GP_STALE as gp_mv_predict_host_checked does. */
+int gp_mv_misfit_host(gp_ctx* ctx, const gp_model* model, const void* d_basis, const void* y, int64_t y_stride,
+                      const void* obs, int64_t obs_stride, const void* weights, int64_t weights_stride, const void* A,
+                      int64_t n_rows, int n_bands, void* out);
+int gp_mv_misfit_host_checked(gp_ctx* ctx, const gp_model* model, const void* d_basis, const void* y, int64_t y_stride,
+                              const void* obs, int64_t obs_stride, const void* weights, int64_t weights_stride,
+                              const void* A, int64_t n_rows, int n_bands, void* out, const void* const* blocks,
+                              const int64_t* nbytes, int n_blocks, uint64_t expected);
+
 /* ---- training objective (next after the predict path: SURVEY.md 8f rank 2) -------------------
  * For each of n_sets hyper-parameter vectors theta [n_sets][n_inputs+2]: what
  * GaussianProcess.loglikelihood + partial_devs compute (gp_emulator/GaussianProcess.py:52-125):
@@ -312,6 +351,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_MEAN_GRAD 1
 #define GP_OP_HESSIAN 2
 #define GP_OP_RECONSTRUCT 3
+#define GP_OP_MISFIT 4             /* n_inputs is n_pcs and aux n_bands, as for GP_OP_RECONSTRUCT */
 #define GP_PLAN_PREDICT_FEW 1      /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
@@ -321,6 +361,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_HESS_WIN_DIRECT 7  /* hessian_win_kernel, direct stores, for the whole call */
 #define GP_PLAN_RECON_NARROW 8     /* reconstruct_kernel, 256 threads x 2 vectors */
 #define GP_PLAN_RECON_WIDE 9       /* reconstruct_kernel, 512 threads x 3 vectors */
+#define GP_PLAN_MISFIT 10          /* misfit_kernel: an item is 64 rows over all bands */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
