@@ -311,6 +311,32 @@ template <typename T> __host__ __device__ constexpr int xa_lds_stride(int D) {
   return (GP_XA_PAD && sizeof(T) == 4 && row_stride(D) % 16 == 0) ? row_stride(D) + 4 : row_stride(D);
 }
 
+// Fragment buffers of predict_kernel<T, D, NK>, each Geo<T>::kChunk fragments long.  With three, phase B publishes
+// chunk c + 1 at the boundary that opens chunk c, so the A-operand ring reads across chunk ends instead of draining
+// at each of them (fp64, N = 250: 9 boundaries per item).  fp64 takes three wherever the workgroup's static LDS stays
+// inside the CU's 160 KB (<double,11,63> 153 968 B, <double,11,75> 160 112 B); the instances that do not fit
+// (D = 12 from NK = 80, D = 16 from NK = 63) and fp32 (three boundaries per item at N = 250, 96 KB in two buffers)
+// keep two.
+#ifndef GP_FRAG_BUFS
+#define GP_FRAG_BUFS 3
+#endif
+#ifndef GP_FRAG_BUFS_F32
+#define GP_FRAG_BUFS_F32 2
+#endif
+constexpr int kLdsBudget = 160 * 1024;
+constexpr int kLdsSlack = 32;          // alignment gaps between the arrays
+template <typename T>
+__host__ __device__ constexpr int predict_lds_bytes(int D, int NK, int bufs) {
+  const int NP = 16 * ((NK + 3) / 4);
+  return (int)sizeof(T) * (NP * xa_lds_stride<T>(D) + bufs * Geo<T>::kChunk * 64 + (2 * D + 1) + 2 * D +
+                           2 * Geo<T>::kWaves * kTile * D) + kLdsSlack;   // the kernel's five arrays (asserted there)
+}
+template <typename T>
+__host__ __device__ constexpr int frag_buffers(int D, int NK) {
+  const int want = sizeof(T) == 8 ? GP_FRAG_BUFS : GP_FRAG_BUFS_F32;
+  return want > 2 && predict_lds_bytes<T>(D, NK, want) <= kLdsBudget ? want : 2;
+}
+
 template <typename T>
 struct PredictArgs {
   const T* xa;        // [16*NB][row_stride(D)]  training rows [x'', alpha, h] (zero padded), NB = ceil(NK/4)
@@ -489,9 +515,12 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
   constexpr int NF = frag_count(NB);
   constexpr int kChunk = G::kChunk;
   constexpr int NCH = (NF + kChunk - 1) / kChunk;
+  // fragment buffers: two (chunk c + 1 lands while chunk c is read), or three where they fit
+  constexpr int kBufs = kVar ? frag_buffers<T>(D, NK) : 1;
+  constexpr int kLook = kBufs - 2;          // chunks published ahead of the one being read (phase B)
 
   __shared__ __attribute__((aligned(16))) T s_xa[NP * DS];
-  __shared__ __attribute__((aligned(16))) T s_fr[kVar ? 2 : 1][kVar ? kChunk * 64 : 1];
+  __shared__ __attribute__((aligned(16))) T s_fr[kBufs][kVar ? kChunk * 64 : 1];
   __shared__ T s_sd[2 * D + 1];   // sqrt(e_d), centre c_d, b: broadcast reads, no registers
   __shared__ T s_ts[2 * D];       // scale and centre applied to the test rows: s_sd's, or (1, 0)
   // raw test rows of the wave's tile, double-buffered and private to the wave: the NEXT item's
@@ -499,6 +528,9 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
   // picked up from here at the top of that item -- all waves of a workgroup are in step, so
   // nothing else would hide the HBM latency of those loads
   __shared__ T s_rows[2][G::kWaves][kTile * D];
+  // frag_buffers() chose kBufs from predict_lds_bytes(): that count and these declarations stay one
+  static_assert(!kVar || (int)(sizeof(s_xa) + sizeof(s_fr) + sizeof(s_sd) + sizeof(s_ts) + sizeof(s_rows)) + kLdsSlack ==
+                             predict_lds_bytes<T>(D, NK, kBufs), "predict_lds_bytes() does not count the kernel's LDS arrays");
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -527,6 +559,11 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
     }
   };
   auto stash_rows = [&](int buf_, const T (&regs)[NJ]) {
+    // the wait for the fetched rows, outside the branches below: a wait that only the taken side of a branch holds
+    // leaves the registers "in flight" for the compiler on the other side, and its next write to them (an A-operand
+    // read early in phase B) gets an s_waitcnt vmcnt(0) -- right behind a chunk's DMA issue, a whole L2 round trip
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) asm volatile("" ::"v"(regs[j]));
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
       if (lane + 64 * j < kTile * p.d_actual) s_rows[buf_][wave][lane + 64 * j] = regs[j];
@@ -565,9 +602,15 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
     const long long mc = m < p.M ? m : p.M - 1;
 
     if constexpr (kVar) {
-      // chunk 0 of S' goes L2 -> LDS by LDS-DMA now and lands under phase A
-      __syncthreads();  // previous item's readers of s_fr[0] are done; new rows visible
-      stage_chunk<T, G::kWaves, kChunk>(frags, &s_fr[0][0], wave, lane);
+      // the first 1 + kLook chunks of S' go L2 -> LDS by LDS-DMA now and land under phase A.  This barrier is behind
+      // every wave's last matrix instruction of the previous item, hence behind its last read of EVERY fragment
+      // buffer, and every DMA of that item was retired by its issuing wave at a chunk boundary of that item: all
+      // kBufs buffers are free.  It also makes the new emulator's rows visible.
+      __syncthreads();
+      static_for<1 + kLook>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        if constexpr (c < NCH) stage_chunk<T, G::kWaves, kChunk>(frags + c * kChunk * 64, &s_fr[c][0], wave, lane);
+      });
     } else {
       // no barrier per item: the only LDS written per item are the wave's own test-row buffers
       // (stash_rows below), written and read by this wave alone, in program order
@@ -719,14 +762,33 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
         ga[d] = sdv[d] * (R::kExpand ? fma(-t[d], mu_t, ga[d]) : ga[d]);
     }
 
+    // Lane group g stores the components d = 4 q + g: one store per quad of components for all four groups (the
+    // value picked by group, the layout tested once) instead of one store per component, each under its own branch
+    // and layout test -- three store regions at D = 11 where there were eleven with two stores each.
     if (m < p.M) {
       if (g == 0) o_mu[m] = mu_t;
+      // (the group number is made opaque here: its products with M and d_actual are per-lane 64-bit values that
+      // would otherwise be hoisted out of the item loop and kept, or spilled, across both phases)
+      int gs = g;
+      asm volatile("" : "+v"(gs));
+      T gq[(D + 3) / 4];
 #pragma unroll
-      for (int d = 0; d < D; ++d) {
-        if ((d & 3) == g && d < p.d_actual) {
-          if (p.deriv_row_major) o_der[m * p.d_actual + d] = ga[d];
-          else o_der[(long long)d * p.M + m] = ga[d];
-        }
+      for (int q = 0; q < (D + 3) / 4; ++q) {
+        gq[q] = ga[4 * q];
+#pragma unroll
+        for (int u = 1; u < 4; ++u)
+          if (4 * q + u < D) gq[q] = gs == u ? ga[4 * q + u] : gq[q];
+      }
+      if (p.deriv_row_major) {
+        T* o_row = o_der + m * p.d_actual + gs;
+#pragma unroll
+        for (int q = 0; q < (D + 3) / 4; ++q)
+          if (4 * q + gs < p.d_actual) o_row[4 * q] = gq[q];
+      } else {
+        T* o_row = o_der + gs * p.M + m;
+#pragma unroll
+        for (int q = 0; q < (D + 3) / 4; ++q)
+          if (4 * q + gs < p.d_actual) o_row[4 * q * p.M] = gq[q];
       }
     }
 
@@ -755,38 +817,65 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
       constexpr int c = f / kChunk, fl = f % kChunk;
       constexpr FragId fid = frag_at(f, NB);
       constexpr int I = fid.I, J = fid.J, s = fid.s;
+      // Chunk boundary.  Chunks up to c - 1 + kLook were published at the boundary before; this one publishes chunk
+      // c + kLook (the item's first one: chunks 0 .. kLook, issued at the item's top) and refills the buffer that
+      // chunk c - 1 has left with chunk c + kLook + 1:
+      //   * the wave retires its own DMA pieces (with three buffers they were issued a whole chunk of matrix
+      //     instructions ago), then the barrier publishes them;
+      //   * behind the barrier every wave has issued its last matrix instruction of chunk c - 1, so the LDS reads
+      //     that fed them have returned (reads return in order): buffer (c - 1) % kBufs = (c + kLook + 1) % kBufs
+      //     has no reader left in any wave.  With three buffers the reads still in flight are of chunks c and
+      //     c + 1, which live in the two OTHER buffers, so the barrier needs no wait for them: a bare s_barrier
+      //     (__syncthreads() would drain the ring with lgkmcnt(0)), fenced for the scheduler so that the matrix
+      //     instructions of chunk c - 1 stay in front of it;
+      //   * a boundary with nothing to publish (three buffers: the last one of the item) has no wait and no barrier.
       if constexpr (fl == 0) {
-#if GP_ABLATE == 4        // (timing only: no chunk barriers, no DMA behind the first chunk)
+#if GP_ABLATE == 4        // (timing only: no chunk barriers, no DMA behind the item's top)
         if constexpr (c == 0) { dma_wait(); __syncthreads(); }
 #else
-        dma_wait();       // this wave's pieces of chunk c have landed
-        __syncthreads();  // chunk c visible; everyone finished reading chunk c-1
-        if constexpr (c + 1 < NCH)
-          stage_chunk<T>(frags + (c + 1) * kChunk * 64, &s_fr[(c + 1) & 1][0], wave, lane);
+        if constexpr (c == 0 || c + kLook < NCH) {
+          dma_wait();
+          if constexpr (kLook > 0) {
+            if constexpr (c > 0) __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_barrier" ::: "memory");
+            if constexpr (c > 0) __builtin_amdgcn_sched_barrier(0);
+          } else {
+            __syncthreads();
+          }
+          if constexpr (c + kLook + 1 < NCH)
+            stage_chunk<T, G::kWaves, kChunk>(frags + (c + kLook + 1) * kChunk * 64,
+                                              &s_fr[(c + kLook + 1) % kBufs][0], wave, lane);
+        }
 #endif
-        // the chunk's first A operands (the ring below keeps kAhead - 1 reads in flight)
+        // the first A operands that the ring has not asked for yet (all of them at the item's first boundary and
+        // with two buffers; none later with three): the ring below keeps kAhead - 1 reads in flight
         static_for<kAhead - 1>([&](auto jc) {
-          constexpr int j = decltype(jc)::value;
+          constexpr int n = f + decltype(jc)::value;
+          if constexpr (n < NF && (c == 0 || n / kChunk > c - 1 + kLook)) {
 #if GP_ABLATE >= 3
-          if constexpr (j < kChunk && f + j < NF) afr[j % kAhead] = kv[j % NK];
+            afr[n % kAhead] = kv[n % NK];
 #else
-          if constexpr (j < kChunk && f + j < NF) afr[j % kAhead] = s_fr[c & 1][j * 64 + lane];
+            afr[n % kAhead] = s_fr[(n / kChunk) % kBufs][(n % kChunk) * 64 + lane];
 #endif
+          }
         });
       }
-      // A operands are read kAhead - 1 fragments ahead of their matrix instruction (inside the
-      // chunk: the next chunk becomes readable only behind its barrier), so the LDS latency
-      // hides behind the matrix instructions in between instead of in front of each pair
+      // A operands are read kAhead - 1 fragments ahead of their matrix instruction, as far as chunks are published
+      // (two buffers: inside the chunk), so the LDS latency hides behind the matrix instructions in between instead
+      // of in front of each pair
+      {
+        constexpr int n = f + kAhead - 1;
+        if constexpr (n < NF && n / kChunk <= c + kLook) {
 #if GP_ABLATE >= 3
-      if constexpr (fl + kAhead - 1 < kChunk && f + kAhead - 1 < NF)
-        afr[(fl + kAhead - 1) % kAhead] = kv[(f + 1) % NK];
+          afr[n % kAhead] = kv[(f + 1) % NK];
 #else
-      if constexpr (fl + kAhead - 1 < kChunk && f + kAhead - 1 < NF)
-        afr[(fl + kAhead - 1) % kAhead] = s_fr[c & 1][(fl + kAhead - 1) * 64 + lane];
+          afr[n % kAhead] = s_fr[(n / kChunk) % kBufs][(n % kChunk) * 64 + lane];
 #endif
+        }
+      }
       if constexpr (I == J && s == 0) acc = acc_t{T(0), T(0), T(0), T(0)};
       // (k-steps s >= KL of the last training block are padding: not issued)
-      if constexpr (4 * I + s < NK) acc = R::mfma(afr[fl % kAhead], kv[4 * I + s], acc);
+      if constexpr (4 * I + s < NK) acc = R::mfma(afr[f % kAhead], kv[4 * I + s], acc);
 #if GP_RING_PIN
       // the order written here is the order issued: left alone, the fp32 build pairs two reads into one
       // ds_read2st64_b32 on a fixed register pair and waits for it in front of its two matrix instructions
