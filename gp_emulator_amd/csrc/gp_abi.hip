@@ -282,6 +282,13 @@ static int pack_model(const TH* expX, const TH* inputs, const TH* invQt, const T
       xa[row + d] = xr;
       n2 += (double)xr * (double)xr;
     }
+    // The fp64 fused kernel's exp has no clamp: it relies on |x''_i|^2 / 2 <= 2^26 for every packed point and on
+    // its own guard per test row (gp_predict_kernel.hpp, Real<double>::kFarG, where both bounds are derived).  A
+    // point 11585 length scales from the training mean is no emulator anyone trained; it is refused, not clamped.
+    if (sizeof(T) == 8 && knb > 0 && 0.5 * n2 > gpk::Real<double>::kMaxHalfNorm2)
+      return fail(GP_ERR_UNSUPPORTED,
+                  "training point %d lies %.4g length scales from the training mean (the fused kernel takes up to %.0f)",
+                  i, std::sqrt(n2), std::sqrt(2.0 * gpk::Real<double>::kMaxHalfNorm2));
     xa[row + kd] = (T)invQt[i];
     xa[row + kd + 1] = (T)(lnb - 0.5 * n2);
   }

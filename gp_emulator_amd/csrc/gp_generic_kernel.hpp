@@ -76,7 +76,7 @@ __global__ __launch_bounds__(gkThreads) void predict_generic_kernel(GenericArgs<
         const T dl = row[d] - t[d];
         r2 = fma(dl, dl, r2);
       }
-      const T k = b * R::exp_(T(-0.5) * r2);
+      const T k = b * R::exp_clamped(T(-0.5) * r2);
       s_k[ml * ns + i] = k;
       mu = fma(k, row[p.acol], mu);
     }

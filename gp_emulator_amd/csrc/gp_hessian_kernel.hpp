@@ -106,7 +106,7 @@ __device__ __forceinline__ void hessian_pass(const T* s_xa, const T* s_sd, const
       for (int d = 0; d <= D; ++d) nxt[d] = row[d];
     }
     const T r2 = (r2p[0] + r2p[1]) + (r2p[2] + r2p[3]);
-    const T w = b * R::exp_(T(-0.5) * r2) * alpha;
+    const T w = b * R::exp_clamped(T(-0.5) * r2) * alpha;
     mu += w;
     int q = 0;
 #pragma unroll

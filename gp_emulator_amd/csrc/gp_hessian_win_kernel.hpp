@@ -530,7 +530,7 @@ void hessian_win_kernel(HessMfmaArgs<T> p) {
 #endif
     // (everything only the finish needs is formed here, not carried through the windows: the
     // registers are full there, and what does not fit goes to scratch and comes back slowly)
-    const T poison = gm - gm;   // NaN for rows holding a NaN or an infinity (exp_ clamps)
+    const T poison = gm - gm;   // NaN for rows holding a NaN or an infinity (exp_n clamps)
     // s and G_d from their accumulator slots: the value sits in one lane group; zero elsewhere and the
     // sum over the four groups (exact) hands it to all of them
     auto slot_value = [&](auto nc) __attribute__((always_inline)) {

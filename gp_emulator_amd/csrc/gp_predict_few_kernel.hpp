@@ -99,7 +99,7 @@ __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T
       k = row[D + 1] + gm;
 #pragma unroll
       for (int d = 0; d < D; ++d) k = fma(x[d], t[d], k);
-      k = R::exp_(k);
+      k = R::exp_clamped(k);
     } else {
       T r2 = T(0);
 #pragma unroll
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(fkThreads, 2) void predict_few_kernel(PredictArgs<T
         x[d] -= t[d];
         r2 = fma(x[d], x[d], r2);
       }
-      k = b * R::exp_(T(-0.5) * r2);
+      k = b * R::exp_clamped(T(-0.5) * r2);
     }
     if constexpr (kVar) s_k[ks][lane] = k;
     const T wgt = k * al;

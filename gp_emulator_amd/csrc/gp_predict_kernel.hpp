@@ -49,7 +49,10 @@ namespace gpk {
 #endif
 // Timing-only ablations for tools/ab_bench.py (outputs are wrong when set): GP_ABLATE=1 skips
 // the matrix-core phase, GP_ABLATE=2 replaces phase A's arithmetic by a trivial fill, GP_ABLATE=3 takes the matrix
-// instructions' A operands from registers instead of the LDS fragments (barriers and DMA stay).
+// instructions' A operands from registers instead of the LDS fragments (barriers and DMA stay), GP_ABLATE=4 drops the
+// chunk barriers and the DMA behind the item's top, GP_ABLATE=5 drops the top-of-item barrier and staging after a
+// workgroup's first item, GP_ABLATE=6 the same with the seam's bare barrier at the item's last chunk boundary (the bound
+// of what the seam, GP_SEAM, can gain: profiles/r08_predict_exp_seam.txt).
 #ifndef GP_ABLATE
 #define GP_ABLATE 0
 #endif
@@ -71,6 +74,9 @@ namespace gpk {
 #endif
 #ifndef GP_ESTRIN
 #define GP_ESTRIN 0     // 1: Estrin form of the exp polynomial (A/B: slower, more registers)
+#endif
+#ifndef GP_EXP_FUSED
+#define GP_EXP_FUSED 1    // 0: fp64 exp with clamp, multiply, v_rndne and convert (17 instructions; A/B, profiles/r08_predict_exp_seam.txt)
 #endif
 #ifndef GP_DOTSPLIT
 #define GP_DOTSPLIT 1     // independent partial sums of the exponent's dot product
@@ -155,16 +161,31 @@ template <> struct Real<double> {
   __device__ static inline acc_t mfma(double a, double b, acc_t c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
   }
-  // exp for arguments that are <= 0 up to rounding (-0.5 * squared distance + ln b):
+  // exp for arguments that are <= 0 up to rounding (-0.5 * squared distance + ln b), 15 instructions:
   // n = rint(x / ln2), r = x - n ln2 (two-step, fma), exp(r) by the degree-10 Chebyshev
   // interpolant of exp on |r| <= ln2/2 (max relative error 3.3e-16, coefficients derived in
   // 80-bit arithmetic), scaled by v_ldexp_f64, which also delivers the gradual underflow to
-  // 0.  No overflow path is needed.  The lower clamp (one v_max_f64) keeps n inside int32
-  // for absurdly distant points; it would turn a NaN argument into exp(-1000) = 0, so the
-  // caller adds the NaN back per test row (see `poison` in predict_kernel).
-  __device__ static inline double exp_(double x) {
+  // 0.  No overflow path is needed.
+  // n comes from one fma: s = x log2e + 1.5 2^52 has an ulp of 1, so the fma's single rounding IS the rounding to an
+  // integer, n = s - 1.5 2^52 is exact, and the low dword of s is n as an int32 (the mantissa of s is 2^51 + n): no
+  // multiply, no v_rndne, no convert.  The product is rounded once where rint(x * log2e) rounds twice, so n may
+  // differ when x log2e lies within an ulp of a half-integer; |r| then exceeds ln2/2 by 2^-52 at the most, where
+  // the interpolant is as good as inside.
+  // CONTRACT: |x log2e| < 2^31 (|x| < 1.488e9), or the low dword is not n.  There is no clamp in here: the caller
+  // bounds the argument once per test row and the host once per training point (kFarG, kMaxHalfNorm2 below).
+  // NaN in, NaN out.  exp_clamped() is the form for callers that bound nothing.
+  // (__host__ as well: tests/test_exp_cpu.py runs it against long double expl)
+  static constexpr double kRoundMagic = 6755399441055744.0;      // 1.5 2^52
+  __host__ __device__ static inline double exp_(double x) {
+#if GP_EXP_FUSED
+    const double s = fma(x, 1.4426950408889634, kRoundMagic);
+    const double n = s - kRoundMagic;
+    const int ni = (int)(unsigned)__builtin_bit_cast(unsigned long long, s);
+#else   // (A/B: the form before, 17 instructions)
     x = __builtin_fmax(x, -1000.0);
     const double n = __builtin_rint(x * 1.4426950408889634);
+    const int ni = (int)n;
+#endif
     double r = fma(n, -6.93147180559945286e-01, x);
     r = fma(n, -2.31904681384629956e-17, r);
 #if GP_ESTRIN
@@ -197,18 +218,38 @@ template <> struct Real<double> {
     p = fma(p, r, 1.00000000000000666e+00);
     p = fma(p, r, 1.0);
 #endif
-    return ldexp(p, (int)n);
+    return ldexp(p, ni);
   }
-  // exp_ of GP values, written step by step across the values: GP independent dependency chains
+  // exp_ behind a lower clamp (one v_max_f64), for the kernels whose argument is -r^2/2 of an arbitrary row or that
+  // have no row guard (general-shape, few-rows and Hessian kernels): the clamp keeps n inside int32 for absurdly
+  // distant points.  It would turn a NaN argument into exp(-1000) = 0, so those callers add the NaN back per test
+  // row (their `poison`).
+  __host__ __device__ static inline double exp_clamped(double x) { return exp_(__builtin_fmax(x, -1000.0)); }
+  // exp_clamped of GP values, written step by step across the values: GP independent dependency chains
   // side by side in program order (for kernels that run one wave per SIMD, where nothing else
-  // hides the latency of a dependent fp64 instruction)
+  // hides the latency of a dependent fp64 instruction).  Same rounding by one fma as exp_; the clamp stays,
+  // because the windowed Hessian kernel that calls this has no row guard.
   template <int GP>
   __device__ static inline void exp_n(double (&x)[GP]) {
     double n[GP], r[GP], p[GP];
+    int ni[GP];
 #pragma unroll
     for (int u = 0; u < GP; ++u) x[u] = __builtin_fmax(x[u], -1000.0);
+#if GP_EXP_FUSED
 #pragma unroll
-    for (int u = 0; u < GP; ++u) n[u] = __builtin_rint(x[u] * 1.4426950408889634);
+    for (int u = 0; u < GP; ++u) r[u] = fma(x[u], 1.4426950408889634, kRoundMagic);
+#pragma unroll
+    for (int u = 0; u < GP; ++u) {
+      n[u] = r[u] - kRoundMagic;
+      ni[u] = (int)(unsigned)__builtin_bit_cast(unsigned long long, r[u]);
+    }
+#else
+#pragma unroll
+    for (int u = 0; u < GP; ++u) {
+      n[u] = __builtin_rint(x[u] * 1.4426950408889634);
+      ni[u] = (int)n[u];
+    }
+#endif
 #pragma unroll
     for (int u = 0; u < GP; ++u) r[u] = fma(n[u], -6.93147180559945286e-01, x[u]);
 #pragma unroll
@@ -224,8 +265,23 @@ template <> struct Real<double> {
       for (int u = 0; u < GP; ++u) p[u] = fma(p[u], r[u], c[j]);
     }
 #pragma unroll
-    for (int u = 0; u < GP; ++u) x[u] = ldexp(p[u], (int)n[u]);
+    for (int u = 0; u < GP; ++u) x[u] = ldexp(p[u], ni[u]);
   }
+  // The bounds that stand in for the clamp in predict_kernel (expansion form: the argument of exp_ is
+  // a_i = h_i + g + x''_i . t'', h_i = ln b - |x''_i|^2 / 2, g = -|t''|^2 / 2; exactly, a_i = ln b - |x''_i - t''|^2 / 2).
+  //   * The host packs no training point with |x''_i|^2 / 2 > kMaxHalfNorm2 = 2^26, i.e. |x''_i| <= X = 2^13.5 = 11585
+  //     length scales from the training mean (pack_model refuses the emulator; fp64 fused kernels only).
+  //   * A test row with g < -kFarG = -2^27, i.e. |t''| > T = 2^14 = 16384, is "far": for every packed point
+  //     |x''_i - t''| >= T - X > 4798, so a_i <= ln b - 4798^2 / 2 < 709.8 - 1.15e7, a long way below -745.14, where
+  //     exp rounds to 0 (the smallest denormal is 2^-1074, ln b <= ln DBL_MAX = 709.8): every k_i of the row IS 0.
+  //     The row set-up gives such a row t'' = 0 and g = -kFarG, so a_i = h_i - 2^27 in [-2^26 - 745.2 - 2^27, 709.8 - 2^27]:
+  //     exp_ returns exactly 0 (ldexp of a positive p by n <= -1.9e8), mu = 0, deriv = 0, var = b, as with the clamp.
+  //   * Every other row has |t''| <= T, so |a_i| <= |ln b| + X^2 / 2 + T^2 / 2 + X T = 745.2 + 2^26 + 2^27 + 2^27.5
+  //     < 3.92e8 (rounding of the D + 2 terms: below 1), and |a_i log2e| < 5.7e8 < 2^31 = 2.1e9.
+  // NaN and infinite rows fail `g >= -kFarG` too and are treated as far; their `poison`, taken from g before the
+  // guard, turns every output of the row into NaN as before.
+  static constexpr double kMaxHalfNorm2 = 67108864.0;     // 2^26
+  static constexpr double kFarG = 134217728.0;            // 2^27
 };
 template <> struct Real<float> {
   typedef f32x4 acc_t;
@@ -243,6 +299,7 @@ template <> struct Real<float> {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
   }
   __device__ static inline float exp_(float x) { return __expf(x); }
+  __device__ static inline float exp_clamped(float x) { return __expf(x); }
   template <int GP>
   __device__ static inline void exp_n(float (&x)[GP]) {
 #pragma unroll
@@ -303,7 +360,7 @@ __host__ __device__ constexpr int row_stride(int D) { return (D + 2 + 3) & ~3; }
 // ...): two different rows per LDS cycle.  fp64 pairs adjacent rows (own_sub = 4 r + g), 128 bytes apart at D = 11:
 // opposite halves of the 256-byte bank row.  fp32 pairs rows FOUR apart (own_sub = 4 g + r): with 64-byte rows that
 // is 256 bytes, the same banks, and every read took two cycles per group (SQ_LDS_BANK_CONFLICT 29 % of the kernel's
-// LDS cycles, profiles/r03_fp32_lds_conflicts.txt) -- one more 16-byte piece per row moves the partner 64 bytes on.
+// LDS cycles, profiles/r03_fp32_kernel.txt) -- one more 16-byte piece per row moves the partner 64 bytes on.
 #ifndef GP_XA_PAD
 #define GP_XA_PAD 1
 #endif
@@ -322,6 +379,14 @@ template <typename T> __host__ __device__ constexpr int xa_lds_stride(int D) {
 #endif
 #ifndef GP_FRAG_BUFS_F32
 #define GP_FRAG_BUFS_F32 2
+#endif
+// The fragment ring runs across items (instances with three buffers whose chunk count is a multiple of three, so
+// that chunk c of every item lives in buffer c % 3): the last two boundaries of an item stage chunks 0 and 1 of the
+// workgroup's next item, and that item starts without barrier, DMA issue or drain.  0: every item opens the ring anew.
+// 2: the two boundaries stage unconditionally (no branch inside the unrolled matrix phase; what is staged in front of an
+// emulator switch or behind the last item is retired unused).
+#ifndef GP_SEAM
+#define GP_SEAM 2
 #endif
 constexpr int kLdsBudget = 160 * 1024;
 constexpr int kLdsSlack = 32;          // alignment gaps between the arrays
@@ -518,6 +583,11 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
   // fragment buffers: two (chunk c + 1 lands while chunk c is read), or three where they fit
   constexpr int kBufs = kVar ? frag_buffers<T>(D, NK) : 1;
   constexpr int kLook = kBufs - 2;          // chunks published ahead of the one being read (phase B)
+  constexpr bool kSeamOk = kVar && kBufs == 3 && NCH >= 3 && NCH % 3 == 0;
+  constexpr bool kSeamAblated = (GP_ABLATE == 5 || GP_ABLATE == 6) && kSeamOk;
+  constexpr bool kSeam = GP_SEAM && !kSeamAblated && kSeamOk;
+  constexpr bool kSeamTop = kSeam || kSeamAblated;     // the ring is opened at emulator switches only
+  constexpr bool kSeamAlways = kSeam && GP_SEAM == 2;
 
   __shared__ __attribute__((aligned(16))) T s_xa[NP * DS];
   __shared__ __attribute__((aligned(16))) T s_fr[kBufs][kVar ? kChunk * 64 : 1];
@@ -581,8 +651,21 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
 #endif
 
   for (; e < p.n_emulators;) {
+    const T* frags = p.frags + e * p.frags_stride;
+    // The first 1 + kLook chunks of S' go L2 -> LDS by LDS-DMA and land under phase A.  The barrier is behind every
+    // wave's last matrix instruction of the previous item, hence behind its last read of EVERY fragment buffer, and
+    // every DMA of that item was retired by its issuing wave at a chunk boundary of that item: all kBufs buffers are
+    // free.  It also makes a new emulator's rows visible.
+    auto open_ring = [&]() {
+      __syncthreads();
+      static_for<1 + kLook>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        if constexpr (c < NCH) stage_chunk<T, G::kWaves, kChunk>(frags + c * kChunk * 64, &s_fr[c][0], wave, lane);
+      });
+    };
     if (e != cur_e) {   // (re)load this emulator's training rows and scalars
       cur_e = e;
+      if constexpr (kSeamAlways) dma_wait();   // (chunks of the emulator before, staged for an item that is not its)
       __syncthreads();  // everyone is done with the previous emulator's rows
       const T* xa = p.xa + e * p.xa_stride;
       for (int i = tid; i < NP * DSG; i += kThreads) s_xa[(i / DSG) * DS + i % DSG] = xa[i];
@@ -594,23 +677,20 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
           s_ts[tid] = !live ? T(0) : !p.rows_prescaled ? sdp[tid] : tid < D ? T(1) : T(0);
       }
       if constexpr (!kVar) __syncthreads();   // new rows visible (the full instance's item barrier does it there)
+      // Seam instances open the ring HERE only, at a workgroup's first item and at an emulator switch.  Every other
+      // item follows one of the same emulator, which issued chunks 0 and 1 at its last two boundaries into the
+      // buffers it had done with (`ahead` below), and nothing else in LDS changes hands between the two: the rows
+      // in s_rows are the wave's own, and the next write to a fragment buffer is behind this item's first chunk
+      // barrier, which every wave reaches only after its last matrix instruction of the item before.
+      if constexpr (kVar && kSeamTop) open_ring();
     }
-    const T* frags = p.frags + e * p.frags_stride;
     T* o_mu = p.mu + e * p.M;
     T* o_der = p.deriv + e * p.M * p.d_actual;
     const long long m = (long long)grp * kRowsPerWG + wave * kTile + ml;
     const long long mc = m < p.M ? m : p.M - 1;
 
     if constexpr (kVar) {
-      // the first 1 + kLook chunks of S' go L2 -> LDS by LDS-DMA now and land under phase A.  This barrier is behind
-      // every wave's last matrix instruction of the previous item, hence behind its last read of EVERY fragment
-      // buffer, and every DMA of that item was retired by its issuing wave at a chunk boundary of that item: all
-      // kBufs buffers are free.  It also makes the new emulator's rows visible.
-      __syncthreads();
-      static_for<1 + kLook>([&](auto cc) {
-        constexpr int c = decltype(cc)::value;
-        if constexpr (c < NCH) stage_chunk<T, G::kWaves, kChunk>(frags + c * kChunk * 64, &s_fr[c][0], wave, lane);
-      });
+      if constexpr (!kSeamTop) open_ring();   // every item opens the ring anew
     } else {
       // no barrier per item: the only LDS written per item are the wave's own test-row buffers
       // (stash_rows below), written and read by this wave alone, in program order
@@ -648,8 +728,16 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
     }
     gm *= T(-0.5);
     // 0 for finite test rows, NaN for rows holding a NaN or an infinity: added to every
-    // output of the row so that bad inputs surface as NaN despite the clamp inside exp_
+    // output of the row so that bad inputs surface as NaN despite the guard below (fp32: despite __expf)
     const T poison = gm - gm;
+    if constexpr (R::kExpand && GP_EXP_FUSED) {
+      // the far-row guard that exp_ relies on (derivation at Real<double>::kFarG): a row more than 2^14 length
+      // scales from the training mean is given t'' = 0 and g = -2^27, so that all its k_i come out exactly 0
+      const bool in_reach = gm >= T(-R::kFarG);       // (false for NaN)
+#pragma unroll
+      for (int d = 0; d < D; ++d) t[d] = in_reach ? t[d] : T(0);
+      gm = in_reach ? gm : T(-R::kFarG);
+    }
 
     asm volatile("" :: "v"(gm));
     // next item (scalar bookkeeping); its test rows are fetched now, in flight during phase A
@@ -658,6 +746,9 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
     // unconditional (a harmless re-fetch of this item's rows when there is no next item):
     // no branch, so the fetched values' live range stays simple for the register allocator
     fetch_rows(e_next < p.n_emulators ? grp_next : grp, rregs);
+    // seam: the workgroup has a next item and it is this emulator's (no next item: e_next = n_emulators > e).  That
+    // item finds e == cur_e at its top and opens nothing, so what is staged for it and what it expects are one test.
+    const bool ahead = kSeam && e_next == e;
 
     GP_STAMP(1);   // test rows loaded and scaled
     T kv[NK];
@@ -759,7 +850,8 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
       for (int d = 0; d < D; ++d) sdv[d] = s_sd[d];
 #pragma unroll
       for (int d = 0; d < D; ++d)
-        ga[d] = sdv[d] * (R::kExpand ? fma(-t[d], mu_t, ga[d]) : ga[d]);
+        // (difference form: the poison rides on the scaling, an fma in the multiply's place; expansion: NaN through mu_t)
+        ga[d] = R::kExpand ? sdv[d] * fma(-t[d], mu_t, ga[d]) : fma(sdv[d], ga[d], poison);
     }
 
     // Lane group g stores the components d = 4 q + g: one store per quad of components for all four groups (the
@@ -828,7 +920,8 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
       //     c + 1, which live in the two OTHER buffers, so the barrier needs no wait for them: a bare s_barrier
       //     (__syncthreads() would drain the ring with lgkmcnt(0)), fenced for the scheduler so that the matrix
       //     instructions of chunk c - 1 stay in front of it;
-      //   * a boundary with nothing to publish (three buffers: the last one of the item) has no wait and no barrier.
+      //   * a boundary with nothing to publish (three buffers: the last one of the item) has no wait and no barrier,
+      //     unless it stages for the next item (kSeam, below).
       if constexpr (fl == 0) {
 #if GP_ABLATE == 4        // (timing only: no chunk barriers, no DMA behind the item's top)
         if constexpr (c == 0) { dma_wait(); __syncthreads(); }
@@ -842,9 +935,27 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
           } else {
             __syncthreads();
           }
-          if constexpr (c + kLook + 1 < NCH)
+          if constexpr (c + kLook + 1 < NCH) {
             stage_chunk<T, G::kWaves, kChunk>(frags + (c + kLook + 1) * kChunk * 64,
                                               &s_fr[(c + kLook + 1) % kBufs][0], wave, lane);
+          } else if constexpr (kSeam && c == NCH - 2) {
+            // seam: the NEXT item's chunk 0 into buffer (NCH - 3) % 3 = 0, which chunk NCH - 3 has left
+            if (kSeamAlways || ahead) stage_chunk<T, G::kWaves, kChunk>(frags, &s_fr[0][0], wave, lane);
+          }
+        } else if constexpr (GP_ABLATE == 6 && kSeamAblated && c == NCH - 1) {
+          __builtin_amdgcn_sched_barrier(0);
+          asm volatile("s_barrier" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+        } else if constexpr (kSeam && c == NCH - 1) {
+          // seam: nothing to publish, so no wait; the barrier is here for the buffer alone.  Behind it every wave has
+          // issued its last matrix instruction of chunk NCH - 2, whose buffer (NCH - 2) % 3 = 1 takes the next
+          // item's chunk 1.  Both chunks are retired and published by that item's first boundary.
+          if (kSeamAlways || ahead) {
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_barrier" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            stage_chunk<T, G::kWaves, kChunk>(frags + kChunk * 64, &s_fr[1][0], wave, lane);
+          }
         }
 #endif
         // the first A operands that the ring has not asked for yet (all of them at the item's first boundary and
@@ -898,6 +1009,7 @@ __global__ __launch_bounds__((Geo<T, kVar>::kThreads), (Geo<T, kVar>::kWavesPerS
     GP_STAMP(5);   // variance reduction and store
     }   // (kVar)
   }
+  if constexpr (kSeamAlways) dma_wait();     // (staged behind the workgroup's last item)
 #if GP_STAMPS
   if (lane == 0 && p.dbg) {
     for (int k_ = 0; k_ < 8; ++k_) atomicAdd(&p.dbg[k_], seg_sum[k_]);

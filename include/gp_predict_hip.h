@@ -119,7 +119,10 @@ int gp_predict_rows_f32_h64(gp_ctx* ctx, const double* expX, const double* input
  * + invQt, and invQ folded to S' in matrix-core fragment order.  compute dtype = the
  * function's dtype.  invQ may be NULL: the model then serves gp_hessian_* and
  * gp_predict_mean_grad_* only (nothing of N x N size is packed or uploaded), and gp_predict_device
- * / gp_predict_host on it fail with GP_ERR_INVALID. */
+ * / gp_predict_host on it fail with GP_ERR_INVALID.
+ * A float64 model for the fused kernels whose scaled training point lies more than 2^13.5 = 11585 length scales
+ * from the training mean is refused with GP_ERR_UNSUPPORTED: that kernel's exp has no clamp and relies on the
+ * bound (gp_predict_kernel.hpp, Real<double>::kFarG). */
 int gp_model_create_f64(gp_ctx* ctx, const double* expX, const double* inputs,
                         const double* invQt, const double* invQ,
                         int n_train, int n_inputs, int theta_size, gp_model** out);
