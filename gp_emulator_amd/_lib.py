@@ -63,6 +63,10 @@ SIGNATURES = {
     "gp_hessian_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_hessian_weighted_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_hessian_weighted_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64]),
+    "gp_band_misfit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
+    "gp_band_misfit_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_hessian_f64": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_hessian_f32": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_reconstruct_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
@@ -589,7 +593,8 @@ class BatchModel(Model):
     ``predict_mean_grad`` only: no inverse is packed or uploaded).
     ``predict`` (inherited: the slab pipeline) returns mu (E, M), var (E, M), deriv (E, M, D);
     ``predict_mean_grad`` mu (E, M), deriv (E, M, D); ``hessian`` (E, M, D, D) and
-    ``hessian_weighted`` the weighted sum over the emulators (M, D, D).
+    ``hessian_weighted`` the weighted sum over the emulators (M, D, D); ``misfit`` the observation
+    misfit summed over the emulators: cost (M,), grad (M, D) and the second-order terms (M, D, D).
     """
 
     def __init__(self, ctx, expX, inputs, invQt, invQ, precision=np.float64):
@@ -670,6 +675,60 @@ class BatchModel(Model):
                 self.ctx.h, self.h, GP_F64 if hdt == np.float64 else GP_F32, _ptr(testing), _ptr(weights),
                 _ptr(res), M), "gp_hessian_weighted_host")
         return res
+
+    def misfit_device(self, d_testing, d_obs, obs_strides, d_weights, w_strides, d_cost, d_grad, n_rows,
+                      d_wr=None, d_gn=None, d_hess=None):
+        """Asynchronous observation misfit of the batch's emulators over shared rows (``gp_band_misfit_device``);
+        device pointers of the model's dtype.  ``obs_strides`` / ``w_strides`` = (emulator stride, row stride) in
+        elements: (1, 0) a vector shared by all rows, (n_rows, 1) an (E, n_rows) array; ``d_weights`` None: 1.
+        cost (n_rows), grad (n_rows, D) and, when their pointers are given, wr (E, n_rows), gn and hess
+        (n_rows, D, D)."""
+        ws = w_strides if d_weights is not None else (0, 0)
+        check(self.ctx.lib.gp_band_misfit_device(
+            self.ctx.h, self.h, d_testing, d_obs, int(obs_strides[0]), int(obs_strides[1]), d_weights, int(ws[0]),
+            int(ws[1]), d_cost, d_grad, d_wr, d_gn, d_hess, int(n_rows)), "gp_band_misfit_device")
+
+    def _em_array(self, a, M, hdt, name):
+        """An (E,) or (E, M) host array as the library takes it, and its (emulator, row) strides."""
+        a = np.ascontiguousarray(a, dtype=hdt)
+        E = self.n_emulators
+        if a.shape == (E,):
+            return a, (1, 0)
+        if a.shape == (E, M):
+            return a, (M, 1)
+        raise ValueError("%s must be (%d,) or (%d, %d), got %s" % (name, E, E, M, a.shape))
+
+    def misfit(self, testing, obs, weights=None, second_order=None, return_residual=False):
+        """Data term of a variational retrieval for host rows (M, D): with ``r[e, m] = mu_e(x_m) - obs[e, m]``,
+        ``cost[m] = 1/2 sum_e w r^2`` (M,), ``grad = sum_e w r dmu_e/dx`` (M, D), then with
+        ``second_order="gauss_newton"`` ``gn = sum_e w dmu_e dmu_e^T`` or with ``"full"``
+        ``hess = gn + sum_e w r H_e`` (M, D, D), then with ``return_residual`` ``wr = w r`` (E, M) -- the weights of
+        ``hessian_weighted``.  ``obs`` and ``weights`` are (E,) (shared by all rows) or (E, M).  Summed on the
+        device (``gp_band_misfit_host``): the per-emulator means and gradients never leave it.  dtype rules of
+        ``Model.hessian``."""
+        if second_order not in (None, "gauss_newton", "full"):
+            raise ValueError("second_order must be None, 'gauss_newton' or 'full'")
+        testing, hdt, _ = self._hessian_rows(testing)
+        M, D = testing.shape
+        obs, os_ = self._em_array(obs, M, hdt, "obs")
+        ws = (0, 0)
+        if weights is not None:
+            weights, ws = self._em_array(weights, M, hdt, "weights")
+        cost, grad = np.empty((M,), hdt), np.empty((M, D), hdt)
+        second = np.empty((M, D, D), hdt) if second_order else None
+        wr = np.empty((self.n_emulators, M), hdt) if return_residual else None
+        if M:
+            check(self.ctx.lib.gp_band_misfit_host(
+                self.ctx.h, self.h, GP_F64 if hdt == np.float64 else GP_F32, _ptr(testing), _ptr(obs), os_[0], os_[1],
+                _ptr(weights) if weights is not None else None, ws[0], ws[1], _ptr(cost), _ptr(grad),
+                _ptr(wr) if wr is not None else None, _ptr(second) if second_order == "gauss_newton" else None,
+                _ptr(second) if second_order == "full" else None, M), "gp_band_misfit_host")
+        out = (cost, grad)
+        if second_order:
+            out += (second,)
+        if return_residual:
+            out += (wr,)
+        return out
 
 
 GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT = 0, 1, 2, 3, 4

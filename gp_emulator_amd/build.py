@@ -138,6 +138,8 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
                                            "-o", os.path.join(OBJ, "reconstruct.o")])
     tasks.append([HIPCC] + FLAGS + defines + ["-c", os.path.join(CSRC, "gp_misfit_tu.hip"),
                                            "-o", os.path.join(OBJ, "misfit.o")])
+    tasks.append([HIPCC] + FLAGS + defines + ["-c", os.path.join(CSRC, "gp_band_misfit_tu.hip"),
+                                           "-o", os.path.join(OBJ, "band_misfit.o")])
     tasks.append([HIPCC] + FLAGS + defines + ["-c", os.path.join(CSRC, "gp_train_tu.hip"),
                                            "-o", os.path.join(OBJ, "train.o")])
     # plain host C++ (no device pass): the content digest with its per-ISA clones

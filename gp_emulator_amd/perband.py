@@ -194,6 +194,136 @@ def hessian_bands(gps, testing, precision=np.float64, weights=None, device=None,
     return total
 
 
+def _em_broadcast(a, E, M, name):
+    """An (E,) or (E, M) array as (E, 1) or (E, M) float64."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape == (E,):
+        return a[:, None]
+    if a.shape == (E, M):
+        return a
+    raise ValueError("%s must be (%d,) or (%d, %d), got %s" % (name, E, E, M, a.shape))
+
+
+def _misfit_numpy(gps, X, obs, weights, second_order, return_residual):
+    """The formulas as they stand, emulator after emulator, from ``cpu_predict`` and ``hessian``."""
+    E, (M, D) = len(gps), X.shape
+    cost, grad = np.zeros(M), np.zeros((M, D))
+    second = np.zeros((M, D, D)) if second_order else None
+    wr = np.empty((E, M)) if return_residual else None
+    for e, gp in enumerate(gps):
+        mu, deriv = gp.cpu_predict(X, do_unc=False)
+        w = np.broadcast_to(weights[e], (M,)) if weights is not None else np.ones(M)
+        r = mu - np.broadcast_to(obs[e], (M,))
+        cost += 0.5 * w * r * r
+        grad += (w * r)[:, None] * deriv
+        if second_order:
+            second += w[:, None, None] * (deriv[:, :, None] * deriv[:, None, :])     # (exactly symmetric)
+        if second_order == "full":
+            second += (w * r)[:, None, None] * gp.hessian(X)
+        if return_residual:
+            wr[e] = w * r
+    out = (cost, grad)
+    if second_order:
+        out += (second,)
+    if return_residual:
+        out += (wr,)
+    return out
+
+
+def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=False, is_gpu=True,
+                 precision=np.float64, device=None, devices=None, misfit_fn=None):
+    """Data term of a variational retrieval on E per-band emulators over shared rows ``X`` (M, D):
+
+        r[e, m] = mu_e(x_m) - obs[e, m]            w = 1 without ``weights``
+        cost[m] = 1/2 sum_e w r^2                  grad[m] = sum_e w r dmu_e/dx
+        gn[m]   = sum_e w dmu_e/dx dmu_e/dx^T      hess[m] = gn[m] + sum_e w r H_e[m]
+
+    Returns ``cost (M,), grad (M, D)``, then ``gn`` (``second_order="gauss_newton"``) or ``hess`` (``"full"``)
+    ``(M, D, D)``, then with ``return_residual`` ``wr = w r (E, M)`` -- the ``weights`` of ``hessian_bands``.
+    ``obs`` and ``weights`` are ``(E,)`` (one spectrum for all rows) or ``(E, M)``.  On the GPU
+    (``BatchModel.misfit``, ``gp_band_misfit_host``) the per-emulator means, gradients and residuals never leave the
+    device; no inverse is stacked or uploaded.  ``is_gpu=False`` is the explicit numpy branch, built from each
+    emulator's ``cpu_predict(do_unc=False)`` and ``hessian``; never a fallback.
+
+    ``devices`` shards the EMULATORS like ``hessian_bands``: every device returns the partial sums of its block and
+    they are added on the host in device order (``wr`` rows are the blocks' own).  ``misfit_fn(device, gps_block, X,
+    obs_block, weights_block, second_order, return_residual)`` replaces the HIP path in the CPU tests of that logic."""
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("X must be (n_rows, n_inputs)")
+    if second_order not in (None, "gauss_newton", "full"):
+        raise ValueError("second_order must be None, 'gauss_newton' or 'full'")
+    inputs = _check_shared_inputs(gps)
+    E, (M, D) = len(gps), X.shape
+    if D != inputs.shape[1]:
+        raise ValueError("X has %d columns, the emulators have %d inputs" % (D, inputs.shape[1]))
+    obs = _em_broadcast(obs, E, M, "obs")
+    if weights is not None:
+        weights = _em_broadcast(weights, E, M, "weights")
+
+    def block(a, e0, e1):           # a block of emulators in the shape the caller gave: (e,) or (e, M)
+        if a is None:
+            return None
+        return a[e0:e1, 0] if a.shape[1] == 1 and M != 1 else a[e0:e1]
+
+    def on_device(ctx, part, o, w):
+        batch = _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in part]), inputs,
+                                np.stack([np.asarray(gp.invQt) for gp in part]), None, precision)
+        try:
+            return batch.misfit(X, o, w, second_order, return_residual)
+        finally:
+            batch.close()
+
+    if devices is None:
+        o, w = block(obs, 0, E), block(weights, 0, E)
+        if misfit_fn is not None:
+            return tuple(misfit_fn(device, gps, X, o, w, second_order, return_residual))
+        if not is_gpu:
+            return _misfit_numpy(gps, np.asarray(X, dtype=np.float64), obs, weights, second_order, return_residual)
+        return on_device(_lib.default_context(device), gps, o, w)
+    import threading
+    from . import multi_gpu
+    if len(devices) < 1:
+        raise ValueError("devices must name at least one device")
+    if not is_gpu and misfit_fn is None:
+        raise ValueError("devices= shards the GPU path; the numpy branch runs in the calling thread")
+    blocks = multi_gpu.row_shards(E, len(devices))       # contiguous blocks of emulators
+    partial = [None] * len(devices)
+    errors = []
+
+    def work(k, dev, e0, e1):
+        try:
+            if e1 <= e0:
+                return
+            o, w = block(obs, e0, e1), block(weights, e0, e1)
+            if misfit_fn is not None:
+                partial[k] = tuple(misfit_fn(dev, gps[e0:e1], X, o, w, second_order, return_residual))
+                return
+            ctx, lock = multi_gpu._device_context(dev)
+            with lock:
+                partial[k] = on_device(ctx, gps[e0:e1], o, w)
+        except BaseException as exc:          # surfaced to the caller below
+            errors.append(exc)
+
+    threads = [threading.Thread(target=work, args=(k, dev, e0, e1))
+               for k, (dev, (e0, e1)) in enumerate(zip(devices, blocks))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        raise errors[0]
+    parts = [p for p in partial if p is not None]          # device order
+    n_sum = 3 if second_order else 2
+    total = [np.array(a) for a in parts[0][:n_sum]]
+    for p in parts[1:]:
+        for acc, a in zip(total, p[:n_sum]):
+            acc += a
+    if return_residual:
+        total.append(np.concatenate([p[n_sum] for p in parts], axis=0))
+    return tuple(total)
+
+
 # ---------------------------------------------------------------------------------------------
 # Training many per-band emulators at once
 # ---------------------------------------------------------------------------------------------

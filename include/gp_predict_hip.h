@@ -318,6 +318,40 @@ int gp_mv_misfit_host_checked(gp_ctx* ctx, const gp_model* model, const void* d_
                               const void* A, int64_t n_rows, int n_bands, void* out, const void* const* blocks,
                               const int64_t* nbytes, int n_blocks, uint64_t expected);
 
+/* ---- observation misfit of per-band emulators -------------------------------------------------------
+ * The same data term for the per-band pattern: `batch` holds n_emulators independent emulators (one per band) on
+ * shared training inputs (gp_batch_create_*; a batch created without invQ serves these calls), and for n_rows shared
+ * rows x_m, with r[e][m] = mu_e(x_m) - obs[e][m] and w = 1 when d_weights is NULL,
+ *   cost[m]        = 1/2 sum_e w[e][m] r[e][m]^2                        d_cost [n_rows]
+ *   grad[m][d]     = sum_e w r dmu_e/dx_d                               d_grad [n_rows][n_inputs]
+ *   wr[e][m]       = w[e][m] r[e][m]                                    d_wr   [n_emulators][n_rows]   (nullable)
+ *   gn[m][d][d2]   = sum_e w dmu_e/dx_d dmu_e/dx_d2                     d_gn   [n_rows][n_inputs][n_inputs] (nullable)
+ *   hess[m]        = gn[m] + sum_e wr[e][m] H_e[m]                      d_hess [n_rows][n_inputs][n_inputs] (nullable)
+ * Element (e, m) of obs is d_obs[e * obs_estride + m * obs_mstride] (elements): (1, 0) is one observation vector
+ * shared by all rows, (n_rows, 1) the (n_emulators, n_rows) array; the weights follow the same rule.  The
+ * per-emulator means, gradients and residuals never leave the device: row slabs of the mean+gradient predict kernel
+ * go to device scratch under the budget of gp_hessian_weighted_* (GP_HESS_WEIGHTED_MB; a slab is never less than
+ * 64 rows of one emulator and, with d_hess, their n_emulators residuals; the _host form's upload and download blocks
+ * of a slab lie beside it, at most 3 n_emulators + 2 n_inputs^2 + 2 n_inputs + 1 elements per row of the slab) and a second kernel folds them over the emulators in ascending order, in double in
+ * both precisions, each result rounded once on store.  No atomics: a row's results do not depend on the other rows,
+ * on the row's place in the call or on how the call was cut, two calls agree bit for bit, gn and hess are exactly
+ * symmetric.  The slab is always written by the throughput predict kernel: it is bit for bit what
+ * gp_predict_mean_grad_* returns when that kernel serves the call (more than 2 x compute units 16-row tiles x
+ * emulators, or GP_NO_FEW=1), and agrees with it to rounding otherwise.  The curvature sum in hess is bit for bit
+ * gp_hessian_weighted_device's for the weights wr, added to gn with one addition per element.
+ * GP_ERR_UNSUPPORTED for a batch on the general-shape kernel (as batched predict) and, with d_hess, beyond the
+ * Hessian kernels' n_inputs.
+ * _device: device pointers of the model's dtype, asynchronous on the context's stream.
+ * _host: host arrays, host_dtype as for gp_predict_host; rows, observations and weights go up per slab (a shared
+ * vector once), cost | grad | gn | hess come down, wr only when its pointer is given. */
+int gp_band_misfit_device(gp_ctx* ctx, const gp_model* batch, const void* d_testing, const void* d_obs,
+                          int64_t obs_estride, int64_t obs_mstride, const void* d_weights, int64_t w_estride,
+                          int64_t w_mstride, void* d_cost, void* d_grad, void* d_wr, void* d_gn, void* d_hess,
+                          int64_t n_rows);
+int gp_band_misfit_host(gp_ctx* ctx, const gp_model* batch, int host_dtype, const void* testing, const void* obs,
+                        int64_t obs_estride, int64_t obs_mstride, const void* weights, int64_t w_estride,
+                        int64_t w_mstride, void* cost, void* grad, void* wr, void* gn, void* hess, int64_t n_rows);
+
 /* ---- training objective (next after the predict path: SURVEY.md 8f rank 2) -------------------
  * For each of n_sets hyper-parameter vectors theta [n_sets][n_inputs+2]: what
  * GaussianProcess.loglikelihood + partial_devs compute (gp_emulator/GaussianProcess.py:52-125):
