@@ -2,7 +2,7 @@
 
     python -m gp_emulator_amd.build [--force] [--jobs N]
 
-One object per (compute dtype, kernel size) translation unit + the C-ABI object, linked into
+One object per (compute dtype, kernel size) translation unit + the host units of the C ABI, linked into
 ``gp_emulator_amd/libgp_predict_hip.so`` (in-tree, git-ignored, shipped to the GPU box by
 gpurun).  hipcc cross-compiles without a GPU.  Replaces the reference's CMake/CUDA build
 (CMakeLists.txt, gp_emulator/gpu/CMakeLists.txt, setup.py:16-35), which picks ONE precision
@@ -113,40 +113,23 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
             if name.endswith(".o.digest"):
                 os.remove(os.path.join(OBJ, name))
     jobs = jobs or min(8, os.cpu_count() or 1)
-    tasks = []
+    # (source, object base name, extra flags); a per-dtype unit keeps f32 / f64 in its object's name
+    units = []
     for tname, ctype in (("f64", "double"), ("f32", "float")):
-        for nk in kernel_sizes("NK"):
-            obj = os.path.join(OBJ, "kern_%s_%d.o" % (tname, nk))
-            tasks.append([HIPCC] + FLAGS + defines + ["-DGP_T=" + ctype, "-DGP_TNAME=" + tname,
-                                            "-DGP_NK=%d" % nk, "-c",
-                                            os.path.join(CSRC, "gp_kernels_tu.hip"), "-o", obj])
-        for nb in kernel_sizes("NB"):
-            obj = os.path.join(OBJ, "hessm_%s_%d.o" % (tname, nb))
-            tasks.append([HIPCC] + FLAGS + defines + ["-DGP_T=" + ctype, "-DGP_TNAME=" + tname,
-                                            "-DGP_NB=%d" % nb, "-c",
-                                            os.path.join(CSRC, "gp_hessian_win_tu.hip"), "-o", obj])
-        obj = os.path.join(OBJ, "generic_%s.o" % tname)
-        tasks.append([HIPCC] + FLAGS + defines + ["-DGP_T=" + ctype, "-DGP_TNAME=" + tname, "-c",
-                                        os.path.join(CSRC, "gp_generic_tu.hip"), "-o", obj])
-        obj = os.path.join(OBJ, "few_%s.o" % tname)
-        tasks.append([HIPCC] + FLAGS + defines + ["-DGP_T=" + ctype, "-DGP_TNAME=" + tname, "-c",
-                                        os.path.join(CSRC, "gp_few_tu.hip"), "-o", obj])
-        obj = os.path.join(OBJ, "hess_%s.o" % tname)
-        tasks.append([HIPCC] + FLAGS + defines + ["-DGP_T=" + ctype, "-DGP_TNAME=" + tname, "-c",
-                                        os.path.join(CSRC, "gp_hessian_tu.hip"), "-o", obj])
-    tasks.append([HIPCC] + FLAGS + defines + ["-c", os.path.join(CSRC, "gp_reconstruct_tu.hip"),
-                                           "-o", os.path.join(OBJ, "reconstruct.o")])
-    tasks.append([HIPCC] + FLAGS + defines + ["-c", os.path.join(CSRC, "gp_misfit_tu.hip"),
-                                           "-o", os.path.join(OBJ, "misfit.o")])
-    tasks.append([HIPCC] + FLAGS + defines + ["-c", os.path.join(CSRC, "gp_band_misfit_tu.hip"),
-                                           "-o", os.path.join(OBJ, "band_misfit.o")])
-    tasks.append([HIPCC] + FLAGS + defines + ["-c", os.path.join(CSRC, "gp_train_tu.hip"),
-                                           "-o", os.path.join(OBJ, "train.o")])
+        t = ["-DGP_T=" + ctype]
+        units += [("gp_kernels_tu.hip", "kern_%s_%d" % (tname, nk), t + ["-DGP_NK=%d" % nk]) for nk in kernel_sizes("NK")]
+        units += [("gp_hessian_win_tu.hip", "hessm_%s_%d" % (tname, nb), t + ["-DGP_NB=%d" % nb]) for nb in kernel_sizes("NB")]
+        units += [("gp_generic_tu.hip", "generic_" + tname, t), ("gp_few_tu.hip", "few_" + tname, t),
+                  ("gp_hessian_tu.hip", "hess_" + tname, t)]
+    units += [("gp_reconstruct_tu.hip", "reconstruct", []), ("gp_misfit_tu.hip", "misfit", []),
+              ("gp_band_misfit_tu.hip", "band_misfit", []), ("gp_train_tu.hip", "train", [])]
+    # the host units (gp_host.hpp lists them)
+    units += [("gp_%s.hip" % u, "gp_" + u, []) for u in ("ctx", "model", "device", "host_path", "folds", "mv")]
+    tasks = [[HIPCC] + FLAGS + defines + extra + ["-c", os.path.join(CSRC, src), "-o", os.path.join(OBJ, name + ".o")]
+             for src, name, extra in units]
     # plain host C++ (no device pass): the content digest with its per-ISA clones
     tasks.append([HIPCC, "-O3", "-std=c++17", "-fPIC", "-x", "c++", "-c", os.path.join(CSRC, "gp_host_digest.cpp"),
                   "-o", os.path.join(OBJ, "host_digest.o")])
-    abi_obj = os.path.join(OBJ, "gp_abi.o")
-    tasks.append([HIPCC] + FLAGS + defines + ["-c", os.path.join(CSRC, "gp_abi.hip"), "-o", abi_obj])
     # biggest kernels first so the pool drains evenly
     def weight(c):
         for a in c:

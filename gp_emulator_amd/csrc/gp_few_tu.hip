@@ -1,21 +1,19 @@
 // predict_few_kernel<T, D, kVar> launchers (every compiled D; NB is a run-time argument); build.py
-// compiles this with -DGP_T / -DGP_TNAME.
+// compiles this with -DGP_T.
 #include "gp_dispatch.hpp"
+#include "gp_launchers.hpp"
 #include "gp_predict_few_kernel.hpp"
-
-#define GP_CAT2(a, b) a##b
-#define GP_CAT(a, b) GP_CAT2(a, b)
 
 namespace gpk {
 
 // var = false: the mean+gradient instances (no phase B)
-hipError_t GP_CAT(launch_few_, GP_TNAME)(int kd, const PredictArgs<GP_T>& a, int nb, int grid, bool var,
-                                        hipStream_t stream) {
+template <typename T>
+hipError_t launch_few(int kd, const PredictArgs<T>& a, int nb, int grid, bool var, hipStream_t stream) {
   switch (kd) {
 #define GP_CASE(d)                                                                                         \
   case d:                                                                                                  \
-    if (var) hipLaunchKernelGGL((predict_few_kernel<GP_T, d, true>), dim3(grid), dim3(fkThreads), 0, stream, a, nb); \
-    else hipLaunchKernelGGL((predict_few_kernel<GP_T, d, false>), dim3(grid), dim3(fkThreads), 0, stream, a, nb); \
+    if (var) hipLaunchKernelGGL((predict_few_kernel<T, d, true>), dim3(grid), dim3(fkThreads), 0, stream, a, nb); \
+    else hipLaunchKernelGGL((predict_few_kernel<T, d, false>), dim3(grid), dim3(fkThreads), 0, stream, a, nb); \
     break;
     GP_FOR_EACH_KERNEL_D(GP_CASE)
 #undef GP_CASE
@@ -24,5 +22,7 @@ hipError_t GP_CAT(launch_few_, GP_TNAME)(int kd, const PredictArgs<GP_T>& a, int
   }
   return hipGetLastError();
 }
+
+template hipError_t launch_few<GP_T>(int, const PredictArgs<GP_T>&, int, int, bool, hipStream_t);
 
 }  // namespace gpk

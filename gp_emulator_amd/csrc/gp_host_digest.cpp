@@ -1,5 +1,5 @@
 // 64-bit digest of host memory blocks: what a device-resident copy of an emulator was made from
-// (gp_content_digest, gp_mv_predict_host_checked in gp_abi.hip).  Plain host C++ -- no HIP -- so the hot loop can be
+// (gp_content_digest, gp_mv_predict_host_checked in gp_mv.hip).  Plain host C++ -- no HIP -- so the hot loop can be
 // compiled in per-ISA clones picked at load time.  Every byte counts: 32 interleaved rotate-add lanes over the
 // 8-byte words (h = rotl(h, 5) + w: every step is a bijection of its lane, so a change of any one word changes
 // the result), folded with multiplies at the end.  It runs at cache / memory speed; the checked calls run it

@@ -1,5 +1,5 @@
 // Persistent helper threads for the host side of the host-pointer predict path
-// (gp_abi.hip, predict_host): copying slabs of the caller's pageable arrays into and out of
+// (gp_host_path.hip, predict_host): copying slabs of the caller's pageable arrays into and out of
 // the pinned staging buffers, converting float64 <-> float32 on the way.
 //
 // One pool per gp_ctx (a context is driven by one thread at a time), created on the first

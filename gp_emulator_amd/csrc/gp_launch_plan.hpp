@@ -1,5 +1,5 @@
 // How a call is cut into work items and workgroups: host arithmetic only, shared by the launch
-// path (gp_abi.hip and the *_tu.hip launchers) and by gp_launch_plan, which reports it, so that the
+// path (gp_device.hip and the *_tu.hip launchers) and by gp_launch_plan, which reports it, so that the
 // report cannot drift from the launch.  Every hot kernel is persistent: a launch takes
 // min(cap, items) workgroups, cap = compute units x workgroups per CU, and a workgroup walks the
 // items it is dealt (grid-stride, or a ticket counter in hessian_win_kernel).  One ROUND of a

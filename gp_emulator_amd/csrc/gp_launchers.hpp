@@ -1,0 +1,38 @@
+// Every kernel launcher of the library, declared once.  The *_tu.hip units, which define and explicitly
+// instantiate them, and the host units, which call them, both include this header: a launcher whose
+// two sides disagree fails to compile, not to link.  T is the compute dtype (float or double); the
+// per-size units instantiate <GP_T, GP_NK> or <GP_T, GP_NB> only, the others the float and double pair.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace gpk {
+
+template <typename T> struct PredictArgs;
+template <typename T> struct GenericArgs;
+template <typename T> struct HessianArgs;
+template <typename T> struct HessMfmaArgs;
+template <typename T> struct HessCombineArgs;
+template <typename T> struct BandMisfitArgs;
+template <typename T> struct ReconArgs;
+template <typename T> struct MisfitArgs;
+struct TrainArgs;
+
+#pragma GCC visibility push(hidden)      // (the launchers are the library's own)
+// predict_kernel<T, D, NK, var> (var = false: the mean+gradient instance) for the compiled kernel_d
+template <typename T, int NK> hipError_t launch_predict(int kernel_d, const PredictArgs<T>&, int grid, bool var, hipStream_t);
+template <typename T> hipError_t launch_few(int kernel_d, const PredictArgs<T>&, int nb, int grid, bool var, hipStream_t);
+template <typename T> hipError_t launch_generic(const GenericArgs<T>&, int grid, hipStream_t);
+
+template <typename T> hipError_t launch_hessian(int kernel_d, const HessianArgs<T>&, int grid, hipStream_t);      // the VALU kernel
+template <typename T, int NB> hipError_t launch_hessm(int kernel_d, const HessMfmaArgs<T>&, int grid, hipStream_t);
+template <typename T> hipError_t launch_hess_combine(const HessCombineArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_band_misfit_fold(const BandMisfitArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_band_misfit_add(const T* gn, T* hess, long long n, hipStream_t);
+template <typename T> hipError_t launch_reconstruct(const ReconArgs<T>&, int wide, int cus, hipStream_t);
+template <typename T> hipError_t launch_misfit(const MisfitArgs<T>&, int cus, hipStream_t);
+template <typename T> hipError_t launch_gauss_newton(const T* deriv, const T* A, T* gn, long long M, int P, int D, int cus, hipStream_t);
+
+hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);      // fp64 only
+#pragma GCC visibility pop
+
+}  // namespace gpk

@@ -1,11 +1,12 @@
 // misfit_kernel<T, PS> (PS = ceil(n_pcs / 4) in 1..4) and gauss_newton_kernel<T> launchers; both dtypes in one unit.
 #include "gp_misfit_kernel.hpp"
 #include "gp_launch_plan.hpp"
+#include "gp_launchers.hpp"
 
 namespace gpk {
 
 template <typename T>
-static hipError_t launch_misfit(const MisfitArgs<T>& a, int cus, hipStream_t stream) {
+hipError_t launch_misfit(const MisfitArgs<T>& a, int cus, hipStream_t stream) {
   // items, and the balanced persistent grid over them: plan_misfit (gp_launch_plan.hpp)
   const int grid = plan_misfit(a.M, mkRows, misfit_cap(cus)).workgroups;
   if (a.P <= 4) hipLaunchKernelGGL((misfit_kernel<T, 1>), dim3(grid), dim3(mkThreads), 0, stream, a);
@@ -17,22 +18,16 @@ static hipError_t launch_misfit(const MisfitArgs<T>& a, int cus, hipStream_t str
 }
 
 template <typename T>
-static hipError_t launch_gn(const T* deriv, const T* A, T* gn, long long M, int P, int D, int cus, hipStream_t stream) {
+hipError_t launch_gauss_newton(const T* deriv, const T* A, T* gn, long long M, int P, int D, int cus, hipStream_t stream) {
   const long long blocks = (M * D + gnThreads - 1) / gnThreads, cap = (long long)cus * 8;
   hipLaunchKernelGGL((gauss_newton_kernel<T>), dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(gnThreads), 0, stream,
                      deriv, A, gn, M, P, D);
   return hipGetLastError();
 }
 
-hipError_t launch_misfit_f32(const MisfitArgs<float>& a, int cus, hipStream_t s) { return launch_misfit<float>(a, cus, s); }
-hipError_t launch_misfit_f64(const MisfitArgs<double>& a, int cus, hipStream_t s) { return launch_misfit<double>(a, cus, s); }
-hipError_t launch_gauss_newton_f32(const float* deriv, const float* A, float* gn, long long M, int P, int D, int cus,
-                                   hipStream_t s) {
-  return launch_gn<float>(deriv, A, gn, M, P, D, cus, s);
-}
-hipError_t launch_gauss_newton_f64(const double* deriv, const double* A, double* gn, long long M, int P, int D, int cus,
-                                   hipStream_t s) {
-  return launch_gn<double>(deriv, A, gn, M, P, D, cus, s);
-}
+template hipError_t launch_misfit<float>(const MisfitArgs<float>&, int, hipStream_t);
+template hipError_t launch_misfit<double>(const MisfitArgs<double>&, int, hipStream_t);
+template hipError_t launch_gauss_newton<float>(const float*, const float*, float*, long long, int, int, int, hipStream_t);
+template hipError_t launch_gauss_newton<double>(const double*, const double*, double*, long long, int, int, int, hipStream_t);
 
 }  // namespace gpk

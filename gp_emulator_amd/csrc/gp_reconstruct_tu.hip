@@ -2,6 +2,7 @@
 // both dtypes in one unit.
 #include "gp_reconstruct_kernel.hpp"
 #include "gp_launch_plan.hpp"
+#include "gp_launchers.hpp"
 
 namespace gpk {
 
@@ -17,14 +18,14 @@ static hipError_t launch_geo(const ReconArgs<T>& a, int grid, hipStream_t stream
 
 // wide = 1: the (512, 3) geometry; returns the bands one workgroup covers through *bw
 template <typename T>
-static hipError_t launch_recon(const ReconArgs<T>& a, int wide, int cus, hipStream_t stream) {
+hipError_t launch_reconstruct(const ReconArgs<T>& a, int wide, int cus, hipStream_t stream) {
   const long long bw = wide ? recon_bands_per_wg<T, 512, 3>() : recon_bands_per_wg<T, 256, 2>();
   // items, and the balanced grid over them: plan_recon (gp_launch_plan.hpp)
   const int grid = plan_recon(a.R, rkRows, a.B, bw, recon_cap(cus, wide != 0)).workgroups;
   return wide ? launch_geo<T, 512, 3>(a, grid, stream) : launch_geo<T, 256, 2>(a, grid, stream);
 }
 
-hipError_t launch_reconstruct_f32(const ReconArgs<float>& a, int wide, int cus, hipStream_t s) { return launch_recon<float>(a, wide, cus, s); }
-hipError_t launch_reconstruct_f64(const ReconArgs<double>& a, int wide, int cus, hipStream_t s) { return launch_recon<double>(a, wide, cus, s); }
+template hipError_t launch_reconstruct<float>(const ReconArgs<float>&, int, int, hipStream_t);
+template hipError_t launch_reconstruct<double>(const ReconArgs<double>&, int, int, hipStream_t);
 
 }  // namespace gpk

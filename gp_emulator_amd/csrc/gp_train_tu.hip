@@ -1,6 +1,7 @@
 // likelihood kernels' launcher (fp64 only).
 #include <cstdlib>
 
+#include "gp_launchers.hpp"
 #include "gp_train_kernel.hpp"
 #include "gp_train_mfma_kernel.hpp"
 
