@@ -18,6 +18,8 @@ LIB_PATH = os.environ.get("GP_PREDICT_LIB") or os.path.join(HERE, "libgp_predict
 
 GP_F32, GP_F64 = 0, 1
 GP_DERIV_DMAJOR, GP_DERIV_ROWMAJOR = 0, 1
+GP_DAMP_DIAGONAL, GP_DAMP_IDENTITY = 0, 1
+_DAMPING = {"diagonal": GP_DAMP_DIAGONAL, "identity": GP_DAMP_IDENTITY}
 
 c_int, c_i64, c_void_p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
 c_dp = ctypes.POINTER(ctypes.c_double)
@@ -67,6 +69,8 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_band_misfit_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
+    "gp_newton_step_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 7 + [c_i64, c_int]),
+    "gp_lm_update_device": (c_int, [c_void_p, c_int] + [c_void_p] * 14 + [ctypes.c_double] * 6 + [c_i64, c_int]),
     "gp_hessian_f64": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_hessian_f32": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_reconstruct_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
@@ -284,6 +288,63 @@ class OutputPool:
         return base.view(dtype).reshape(shape)
 
 
+def newton_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=None):
+    """The damped Newton step of ``gp_newton_step_device`` in float64 numpy, vectorised over the rows and written out
+    in the kernel's summation order (ascending index in the factorisation, in both substitutions and in the prior's
+    chain): ``(step (M, D), trial (M, D), status (M,) int32)``.  The explicit CPU branch of ``Context.newton_step``
+    and of ``perband.retrieve_bands``, and the reference of the CPU tests; never a fallback.
+
+        A' = A (+ P),  g' = grad (+ P (x - x0)),  A'_dd += lam * (A'_dd | 1),  L L^T = A' (lower triangle read),
+        step = -L^-T L^-1 g',  trial = clip(x + step, lo, hi);  status = k + 1 when pivot k is not > 0 or not finite,
+        then step = 0 and trial = x.
+
+    ``prior=(x0 (D,), P (D, D))``, ``bounds=(lo (D,), hi (D,))``, ``lam`` (M,) or a scalar."""
+    if damping not in _DAMPING:
+        raise ValueError("damping must be 'diagonal' or 'identity'")
+    x = np.array(x, dtype=np.float64, ndmin=2)
+    M, D = x.shape
+    g = np.array(grad, dtype=np.float64).reshape(M, D)
+    L = np.array(A, dtype=np.float64).reshape(M, D, D)
+    lam = np.broadcast_to(np.asarray(lam, dtype=np.float64), (M,))
+    if prior is not None:
+        x0, P = np.asarray(prior[0], dtype=np.float64).reshape(D), np.asarray(prior[1], dtype=np.float64).reshape(D, D)
+        L = L + P
+        for c in range(D):
+            g += P[:, c] * (x[:, c] - x0[c])[:, None]
+    idx = np.arange(D)
+    diag = L[:, idx, idx]
+    L[:, idx, idx] = diag + lam[:, None] * (diag if damping == "diagonal" else 1.0)
+    status = np.zeros(M, np.int32)
+    with np.errstate(all="ignore"):
+        for k in range(D):
+            s = L[:, k:, k].copy()                                   # rows j >= k of column k
+            for q in range(k):
+                s -= L[:, k:, q] * L[:, k, q][:, None]
+            piv = s[:, 0]
+            bad = ~(piv > 0.0) | ~np.isfinite(piv)
+            status[(status == 0) & bad] = k + 1
+            dk = np.sqrt(piv)
+            L[:, k, k] = dk
+            L[:, k + 1:, k] = s[:, 1:] / dk[:, None]
+        y = g                                                       # y = L^-1 g'
+        for k in range(D):
+            y[:, k] = y[:, k] / L[:, k, k]
+            y[:, k + 1:] -= L[:, k + 1:, k] * y[:, k][:, None]
+        z = np.zeros((M, D))                                        # z = L^-T y
+        for i in range(D - 1, -1, -1):
+            a = y[:, i].copy()
+            for k in range(i + 1, D):
+                a -= L[:, k, i] * z[:, k]
+            z[:, i] = a / L[:, i, i]
+    ok = (status == 0)[:, None]
+    step = np.where(ok, -z, 0.0)
+    trial = x + step
+    if bounds is not None:
+        trial = np.minimum(np.maximum(trial, np.asarray(bounds[0], dtype=np.float64)), np.asarray(bounds[1], dtype=np.float64))
+    trial = np.where(ok, trial, x)
+    return step, trial, status
+
+
 class Context:
     """One device + one HIP stream (gp_ctx).  Use one per thread / per GPU."""
 
@@ -391,6 +452,67 @@ class Context:
         code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
         check(self.lib.gp_mv_gauss_newton_device(self.h, code, d_deriv, d_A, d_gn, int(n_rows), int(n_pcs),
                                                  int(n_inputs)), "gp_mv_gauss_newton_device")
+
+    def newton_step_device(self, dtype, d_x, d_grad, d_A, d_lambda, d_step, d_trial, d_status, n_rows, n_inputs,
+                           damping="diagonal", d_prior_mean=None, d_prior_prec=None, d_lo=None, d_hi=None):
+        """Asynchronous damped Newton step of ``n_rows`` systems on the device (``gp_newton_step_device``): solves
+        ``(A + damping) step = -grad`` row by row by Cholesky, ``trial = clamp(x + step)``, ``status`` int32 (0, or
+        the 1-based index of the failed pivot: then step = 0, trial = x).  Device pointers of ``dtype``; the prior
+        pair, the bounds pair and one of ``d_step`` / ``d_trial`` may be None."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_newton_step_device(self.h, code, d_x, d_grad, d_A, d_lambda, _DAMPING[damping], d_prior_mean,
+                                             d_prior_prec, d_lo, d_hi, d_step, d_trial, d_status, int(n_rows),
+                                             int(n_inputs)), "gp_newton_step_device")
+
+    def lm_update_device(self, dtype, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A, d_A_trial, d_lambda,
+                         d_status, d_state, d_accepted, n_rows, n_inputs, d_prior_mean=None, d_prior_prec=None,
+                         down=1.0 / 3.0, up=4.0, lambda_min=1e-12, lambda_max=1e12, ftol=1e-10, xtol=0.0):
+        """Asynchronous Levenberg-Marquardt accept / reject of the trial rows on the device (``gp_lm_update_device``):
+        rows with ``state == 0`` whose trial lowers ``cost (+ prior term)`` take the trial's x, cost, grad and A and
+        ``lambda * down``, the others keep theirs and take ``lambda * up``; ``state`` becomes 1 on convergence
+        (``ftol``, ``xtol``).  The grad pair, the A pair, ``d_accepted`` and the prior pair may be None."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_lm_update_device(self.h, code, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A,
+                                           d_A_trial, d_lambda, d_status, d_state, d_accepted, d_prior_mean, d_prior_prec,
+                                           float(down), float(up), float(lambda_min), float(lambda_max), float(ftol),
+                                           float(xtol), int(n_rows), int(n_inputs)), "gp_lm_update_device")
+
+    def newton_step(self, x, grad, A, lam, damping="diagonal", prior=None, bounds=None, precision=None, is_gpu=True):
+        """``(step, trial, status)`` of the damped Newton step for host arrays ``x`` (M, D), ``grad`` (M, D), ``A``
+        (M, D, D) and ``lam`` (M,) or a scalar: uploads, launches ``gp_newton_step_device``, downloads.
+        ``prior=(x0, P)``, ``bounds=(lo, hi)``.  ``precision`` is the device dtype (default: float32 when ``x`` is
+        float32, else float64).  ``is_gpu=False`` is the explicit numpy branch (``newton_step_numpy``: the same
+        algorithm in float64); never a fallback."""
+        if not is_gpu:
+            return newton_step_numpy(x, grad, A, lam, damping, prior, bounds)
+        if damping not in _DAMPING:
+            raise ValueError("damping must be 'diagonal' or 'identity'")
+        x = np.asarray(x)
+        if x.ndim != 2:
+            raise ValueError("x must be (n_rows, n_inputs)")
+        dt = np.dtype(precision if precision is not None else (np.float32 if x.dtype == np.float32 else np.float64))
+        M, D = x.shape
+        host = [np.ascontiguousarray(x, dtype=dt), np.ascontiguousarray(grad, dtype=dt).reshape(M, D),
+                np.ascontiguousarray(A, dtype=dt).reshape(M, D, D),
+                np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=dt), (M,)))]
+        host += [np.ascontiguousarray(prior[0], dtype=dt).reshape(D), np.ascontiguousarray(prior[1], dtype=dt).reshape(D, D)] \
+            if prior is not None else [None, None]
+        host += [np.ascontiguousarray(bounds[0], dtype=dt).reshape(D), np.ascontiguousarray(bounds[1], dtype=dt).reshape(D)] \
+            if bounds is not None else [None, None]
+        ptrs = []
+        try:
+            for a in host:
+                ptrs.append(self.to_device(a) if a is not None else None)
+            d_step, d_trial, d_status = self.malloc(M * D * dt.itemsize), self.malloc(M * D * dt.itemsize), self.malloc(M * 4)
+            ptrs += [d_step, d_trial, d_status]
+            self.newton_step_device(dt, ptrs[0], ptrs[1], ptrs[2], ptrs[3], d_step, d_trial, d_status, M, D, damping,
+                                    ptrs[4], ptrs[5], ptrs[6], ptrs[7])
+            return (np.array(self.to_host(d_step, (M, D), dt)), np.array(self.to_host(d_trial, (M, D), dt)),
+                    np.array(self.to_host(d_status, (M,), np.int32)))
+        finally:
+            for p in ptrs:
+                if p is not None:
+                    self.free(p)
 
     def likelihood_batch(self, thetas, inputs, targets, want_inverse=False):
         """cost (E,), grad (E, D+2) [and invQ (E, N, N), invQt (E, N)] of the training

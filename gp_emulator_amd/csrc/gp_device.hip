@@ -1,4 +1,4 @@
-// Launch sizing, and predict and Hessian on device buffers.
+// Launch sizing, and predict, Hessian, Newton step and LM update on device buffers.
 #include "gp_host.hpp"
 
 #include "gp_generic_kernel.hpp"
@@ -7,6 +7,7 @@
 #include "gp_launch_plan.hpp"
 #include "gp_launchers.hpp"
 #include "gp_misfit_kernel.hpp"
+#include "gp_newton_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
 
 // The per-size launchers by their run-time size: one switch over the compiled NK, one over the compiled NB.
@@ -343,6 +344,99 @@ int gp_hessian_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
   return guarded([&] { return for_dtype(model->dtype, [&](auto t) {
     return hessian_device<GP_TAG_TYPE(t)>(ctx, model, d_testing, d_hess, n_predict);
   }); });
+}
+
+// ---- damped Newton step and LM update: device arrays in, device arrays out, no model ------------------
+static int newton_sizes(int dtype, int64_t n_rows, int n_inputs) {
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_rows <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_inputs > gpk::kNewtonMaxD)
+    return fail(GP_ERR_UNSUPPORTED, "the Newton step kernels serve n_inputs <= %d", gpk::kNewtonMaxD);
+  // (16 or 8 rows per workgroup, 4 per workgroup in the update: the grids are numbered in 31 bits)
+  if (n_rows > (int64_t)0x7fffffff * 4) return fail(GP_ERR_INVALID, "n_rows too large for one launch");
+  return GP_OK;
+}
+
+int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
+                          const void* d_lambda, int damping, const void* d_prior_mean, const void* d_prior_prec,
+                          const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
+                          int64_t n_rows, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_x || !d_grad || !d_A || !d_lambda || !d_status || (!d_step && !d_trial))
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (damping != GP_DAMP_DIAGONAL && damping != GP_DAMP_IDENTITY) return fail(GP_ERR_INVALID, "bad damping %d", damping);
+  if ((d_prior_mean != nullptr) != (d_prior_prec != nullptr))
+    return fail(GP_ERR_INVALID, "prior mean and prior precision go together");
+  if ((d_lo != nullptr) != (d_hi != nullptr)) return fail(GP_ERR_INVALID, "lower and upper bounds go together");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::NewtonArgs<T> a;
+    a.x = as<T>(d_x);
+    a.grad = as<T>(d_grad);
+    a.A = as<T>(d_A);
+    a.lambda = as<T>(d_lambda);
+    a.prior_mean = as<T>(d_prior_mean);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.lo = as<T>(d_lo);
+    a.hi = as<T>(d_hi);
+    a.step = as<T>(d_step);
+    a.trial = as<T>(d_trial);
+    a.status = d_status;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    a.diagonal = damping == GP_DAMP_DIAGONAL ? 1 : 0;
+    hipError_t e = gpk::launch_newton_step<T>(a, ctx->stream);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "newton step kernel launch: %s", hipGetErrorString(e));
+    return (int)GP_OK;
+  });
+}
+
+int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost, const void* d_cost_trial,
+                        void* d_grad, const void* d_grad_trial, void* d_A, const void* d_A_trial,
+                        void* d_lambda, const int32_t* d_status, int32_t* d_state, int32_t* d_accepted,
+                        const void* d_prior_mean, const void* d_prior_prec, double down, double up,
+                        double lambda_min, double lambda_max, double ftol, double xtol,
+                        int64_t n_rows, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_x || !d_trial || !d_cost || !d_cost_trial || !d_lambda || !d_status || !d_state)
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if ((d_grad != nullptr) != (d_grad_trial != nullptr) || (d_A != nullptr) != (d_A_trial != nullptr))
+    return fail(GP_ERR_INVALID, "grad / grad_trial and A / A_trial are given or left out as pairs");
+  if ((d_prior_mean != nullptr) != (d_prior_prec != nullptr))
+    return fail(GP_ERR_INVALID, "prior mean and prior precision go together");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::LmUpdateArgs<T> a;
+    a.x = as<T>(d_x);
+    a.trial = as<T>(d_trial);
+    a.cost = as<T>(d_cost);
+    a.cost_trial = as<T>(d_cost_trial);
+    a.grad = as<T>(d_grad);
+    a.grad_trial = as<T>(d_grad_trial);
+    a.A = as<T>(d_A);
+    a.A_trial = as<T>(d_A_trial);
+    a.lambda = as<T>(d_lambda);
+    a.status = d_status;
+    a.state = d_state;
+    a.accepted = d_accepted;
+    a.prior_mean = as<T>(d_prior_mean);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.down = down;
+    a.up = up;
+    a.lambda_min = lambda_min;
+    a.lambda_max = lambda_max;
+    a.ftol = ftol;
+    a.xtol = xtol;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    hipError_t e = gpk::launch_lm_update<T>(a, ctx->stream);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "lm update kernel launch: %s", hipGetErrorString(e));
+    return (int)GP_OK;
+  });
 }
 
 }  // extern "C"

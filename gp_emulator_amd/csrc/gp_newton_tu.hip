@@ -1,0 +1,36 @@
+// newton_step_kernel<T> and lm_update_kernel<T> launchers; both dtypes in one unit.
+#include "gp_newton_kernel.hpp"
+#include "gp_launchers.hpp"
+
+namespace gpk {
+
+// plain grids sized by the work, as the band misfit's: 16 or 8 rows per workgroup (a sub-group of lanes per row)
+template <typename T>
+hipError_t launch_newton_step(const NewtonArgs<T>& a, hipStream_t stream) {
+  if (a.rows <= 0) return hipSuccess;
+  if (a.d < 1 || a.d > kNewtonMaxD) return hipErrorInvalidValue;
+  const int per_wg = newton_rows_per_wg(a.d);
+  const long long blocks = (a.rows + per_wg - 1) / per_wg;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((newton_step_kernel<T>), dim3((unsigned)blocks), dim3(kNewtonThreads), newton_lds_bytes(a.d), stream, a);
+  return hipGetLastError();
+}
+
+// a wave per row
+template <typename T>
+hipError_t launch_lm_update(const LmUpdateArgs<T>& a, hipStream_t stream) {
+  if (a.rows <= 0) return hipSuccess;
+  if (a.d < 1 || a.d > kNewtonMaxD) return hipErrorInvalidValue;
+  const int per_wg = kNewtonThreads / 64;
+  const long long blocks = (a.rows + per_wg - 1) / per_wg;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((lm_update_kernel<T>), dim3((unsigned)blocks), dim3(kNewtonThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+template hipError_t launch_newton_step<float>(const NewtonArgs<float>&, hipStream_t);
+template hipError_t launch_newton_step<double>(const NewtonArgs<double>&, hipStream_t);
+template hipError_t launch_lm_update<float>(const LmUpdateArgs<float>&, hipStream_t);
+template hipError_t launch_lm_update<double>(const LmUpdateArgs<double>&, hipStream_t);
+
+}  // namespace gpk

@@ -324,6 +324,162 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
     return tuple(total)
 
 
+def _prior_term(X, prior):
+    """1/2 (x - x0)^T P (x - x0) per row, outer and inner index ascending as lm_update_kernel sums it."""
+    if prior is None:
+        return 0.0
+    x0, P = prior
+    d = X - x0
+    D = d.shape[1]
+    q = np.zeros(d.shape[0])
+    for i in range(D):
+        ri = np.zeros(d.shape[0])
+        for c in range(D):
+            ri += P[i, c] * d[:, c]
+        q += d[:, i] * ri
+    return 0.5 * q
+
+
+def _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, status, state, prior, down, up, lam_min, lam_max,
+                     ftol, xtol):
+    """``gp_lm_update_device`` in float64 numpy, in place on X, cost, grad, A, lam, state; returns accepted (M,) int32."""
+    active = state == 0
+    F, Ft = cost + _prior_term(X, prior), cost_t + _prior_term(trial, prior)
+    with np.errstate(invalid="ignore"):
+        accept = active & (status == 0) & np.isfinite(Ft) & (Ft < F)
+        conv = ((F - Ft) <= ftol * F) | (np.max(np.abs(trial - X), axis=1) <= xtol)
+    reject = active & ~accept
+    X[accept], cost[accept], grad[accept], A[accept] = trial[accept], cost_t[accept], grad_t[accept], A_t[accept]
+    lam[accept] = np.maximum(lam[accept] * down, lam_min)
+    lam[reject] = np.minimum(lam[reject] * up, lam_max)
+    state[accept & conv] = 1
+    return accept.astype(np.int32)
+
+
+LAMBDA_MIN, LAMBDA_MAX = 1e-12, 1e12     # the clamps of retrieve_bands' damping
+
+
+def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prior=None, bounds=None, lam0=1e-2,
+                   max_iter=20, down=1.0 / 3.0, up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64,
+                   device=None, step_fn=None):
+    """Levenberg-Marquardt retrieval of M state vectors at once on E per-band emulators: minimises, row by row,
+
+        F(x) = 1/2 sum_e w (mu_e(x) - obs[e])^2  (+ 1/2 (x - x0)^T P (x - x0) with ``prior=(x0 (D,), P (D, D))``)
+
+    from ``X0`` (M, D), inside ``bounds=(lo (D,), hi (D,))`` when given.  ``obs`` and ``weights`` as in
+    ``misfit_bands``; ``second_order`` is "gauss_newton" or "full" (the matrix A of the step).  An iteration is: the
+    misfit at the trial rows, the accept / reject update (a trial that lowers F is taken and lambda multiplied by
+    ``down``, any other is dropped and lambda multiplied by ``up``, between ``LAMBDA_MIN`` and ``LAMBDA_MAX``; a row
+    whose accepted step gains no more than ``ftol * F`` or moves no more than ``xtol`` is converged and frozen), then
+    the damped Newton step ``(A + P + lambda diag(A + P)) step = -(grad + P (x - x0))``, ``trial = clip(x + step)``.
+    At most ``max_iter`` trials per row.
+
+    Returns ``(X (M, D), cost (M,), state (M,) int32, n_accepted (M,) int32, lam (M,))``: ``cost`` is the DATA term
+    at ``X`` (the prior term is not included), ``state`` 1 for converged rows, ``n_accepted`` the trials taken.
+
+    On the GPU one ``BatchModel`` is built and ``X0``, ``obs`` and ``weights`` go up once; every iteration is
+    ``misfit_device``, ``lm_update_device``, ``newton_step_device`` on the context's stream, and nothing comes back
+    inside the loop but ``state``, every fourth iteration, to stop when every row has converged.  ``is_gpu=False`` is
+    the explicit numpy branch, the same loop from ``_misfit_numpy`` and ``_lib.newton_step_numpy``; never a fallback.
+    ``step_fn(x, grad, A, lam) -> (step, trial, status)`` replaces the Newton step in the CPU tests of the loop's
+    logic: the loop then runs on the host whatever ``is_gpu`` says."""
+    if second_order not in ("gauss_newton", "full"):
+        raise ValueError("second_order must be 'gauss_newton' or 'full'")
+    X0 = np.asarray(X0)
+    if X0.ndim != 2:
+        raise ValueError("X0 must be (n_rows, n_inputs)")
+    inputs = _check_shared_inputs(gps)
+    E, (M, D) = len(gps), X0.shape
+    if D != inputs.shape[1]:
+        raise ValueError("X0 has %d columns, the emulators have %d inputs" % (D, inputs.shape[1]))
+    obs = _em_broadcast(obs, E, M, "obs")
+    if weights is not None:
+        weights = _em_broadcast(weights, E, M, "weights")
+    if prior is not None:
+        prior = (np.asarray(prior[0], dtype=np.float64).reshape(D), np.asarray(prior[1], dtype=np.float64).reshape(D, D))
+    if bounds is not None:
+        bounds = (np.asarray(bounds[0], dtype=np.float64).reshape(D), np.asarray(bounds[1], dtype=np.float64).reshape(D))
+    max_iter = int(max_iter)
+
+    if step_fn is not None or not is_gpu:
+        step = step_fn if step_fn is not None else (
+            lambda x, g, A, lam: _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds))
+        X = np.array(X0, dtype=np.float64)
+        lam = np.full(M, float(lam0))
+        state, n_acc = np.zeros(M, np.int32), np.zeros(M, np.int32)
+        cost, grad, A = (np.array(a) for a in _misfit_numpy(gps, X, obs, weights, second_order, False))
+        for it in range(max_iter):
+            _, trial, status = step(X, grad, A, lam)
+            trial = np.asarray(trial, dtype=np.float64)
+            cost_t, grad_t, A_t = _misfit_numpy(gps, trial, obs, weights, second_order, False)
+            n_acc += _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, np.asarray(status), state, prior,
+                                      down, up, LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
+            if it % 4 == 3 and np.all(state == 1):
+                break
+        return X, cost, state, n_acc, lam
+
+    ctx = _lib.default_context(device)
+    dt = np.dtype(precision)
+    isz = dt.itemsize
+    batch = _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in gps]), inputs,
+                            np.stack([np.asarray(gp.invQt) for gp in gps]), None, precision)
+    held = []
+
+    def up_(a):
+        held.append(ctx.to_device(np.ascontiguousarray(a, dtype=dt)))
+        return held[-1]
+
+    def alloc(nbytes):
+        held.append(ctx.malloc(max(1, nbytes)))
+        return held[-1]
+
+    def strides(a):
+        return (1, 0) if a.shape[1] == 1 and M != 1 else (M, 1)
+    try:
+        d_x, d_obs = up_(X0), up_(obs)
+        d_w = up_(weights) if weights is not None else None
+        d_lam = up_(np.full(M, float(lam0)))
+        d_x0, d_P = (up_(prior[0]), up_(prior[1])) if prior is not None else (None, None)
+        d_lo, d_hi = (up_(bounds[0]), up_(bounds[1])) if bounds is not None else (None, None)
+        d_cost, d_grad, d_A = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
+        d_cost_t, d_grad_t, d_A_t = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
+        d_trial, d_status, d_state = alloc(M * D * isz), alloc(M * 4), alloc(M * 4)
+        d_acc = alloc(max_iter * M * 4)            # one (M,) slice per iteration, summed after the loop
+        _lib.check(ctx.lib.gp_memset(ctx.h, d_state, 0, M * 4), "gp_memset")
+        os_, ws = strides(obs), strides(weights) if weights is not None else (0, 0)
+
+        def misfit(d_rows, c, g, a):
+            batch.misfit_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a if second_order == "gauss_newton" else None,
+                                d_hess=a if second_order == "full" else None)
+
+        def newton():
+            ctx.newton_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0, d_P,
+                                   d_lo, d_hi)
+        misfit(d_x, d_cost, d_grad, d_A)
+        newton()
+        done = 0
+        for it in range(max_iter):
+            misfit(d_trial, d_cost_t, d_grad_t, d_A_t)
+            ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status,
+                                 d_state, _lib.c_void_p(d_acc.value + it * M * 4), M, D, d_x0, d_P, down, up,
+                                 LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
+            newton()
+            done = it + 1
+            if it % 4 == 3:                       # (the copy synchronises the stream first)
+                ctx.synchronize()
+                if np.all(np.asarray(ctx.to_host(d_state, (M,), np.int32)) == 1):
+                    break
+        ctx.synchronize()
+        X, cost, lam = (np.array(ctx.to_host(p, s, dt)) for p, s in ((d_x, (M, D)), (d_cost, (M,)), (d_lam, (M,))))
+        state = np.array(ctx.to_host(d_state, (M,), np.int32))
+        n_acc = np.array(ctx.to_host(d_acc, (done, M), np.int32)).sum(axis=0, dtype=np.int32) if done else np.zeros(M, np.int32)
+        return X, cost, state, n_acc, lam
+    finally:
+        for p in held:
+            ctx.free(p)
+        batch.close()
+
+
 # ---------------------------------------------------------------------------------------------
 # Training many per-band emulators at once
 # ---------------------------------------------------------------------------------------------

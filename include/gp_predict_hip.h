@@ -352,6 +352,47 @@ int gp_band_misfit_host(gp_ctx* ctx, const gp_model* batch, int host_dtype, cons
                         int64_t obs_estride, int64_t obs_mstride, const void* weights, int64_t w_estride,
                         int64_t w_mstride, void* cost, void* grad, void* wr, void* gn, void* hess, int64_t n_rows);
 
+/* ---- damped Newton step and Levenberg-Marquardt update ----------------------------------------------
+ * What consumes cost, grad and gn / hess of the misfit entries above without their leaving the device; the two
+ * entries do not know where d_grad and d_A came from.  For each of n_rows rows, D = n_inputs,
+ *   A' = A[m] (+ P)                      d_A [n_rows][D][D];  d_prior_prec P [D][D] and d_prior_mean x0 [D], shared
+ *   g' = grad[m] (+ P (x_m - x0))        by all rows: both or neither
+ *   A'_dd += lambda[m] s_d               damping = GP_DAMP_DIAGONAL: s_d = A'_dd (before damping); GP_DAMP_IDENTITY: 1
+ *   L L^T = A'                           Cholesky: the lower triangle of A' is read, the upper is never touched
+ *   step[m]  = -L^-T L^-1 g'             d_step  [n_rows][D]
+ *   trial[m] = clamp(x_m + step[m], lo, hi)   d_trial [n_rows][D]; d_lo / d_hi [D], shared, both or neither (without
+ *                                        them trial = x + step)
+ *   status[m] = 0, or k + 1 when pivot k (0-based) is not > 0 or not finite; then step[m] = 0 and trial[m] = x_m
+ * Either of d_step and d_trial may be NULL, not both.  Everything runs in double in both precisions, step and
+ * trial each rounded to `dtype` once on store; every sum runs in ascending index (the factorisation, both
+ * substitutions, the prior's chain over the column index).  No atomics: a row's result does not depend on the
+ * other rows, on its place in the call or on the grid, and two calls agree bit for bit.
+ * gp_lm_update_device decides on the trial rows.  For each row with state[m] == 0,
+ *   F   = cost[m]       + 1/2 (x - x0)^T P (x - x0)       (the prior term only when P is given; in double,
+ *   F_t = cost_trial[m] + 1/2 (t - x0)^T P (t - x0)        outer index ascending, inner index ascending)
+ *   accept = status[m] == 0 && isfinite(F_t) && F_t < F
+ *   accept:  x, cost, grad, A  <-  trial, cost_trial, grad_trial, A_trial        (copies, bit for bit)
+ *            lambda <- max(lambda * down, lambda_min)
+ *            state  <- 1 if (F - F_t) <= ftol * F  or  max_d |t_d - x_d| <= xtol, else 0
+ *   reject:  lambda <- min(lambda * up, lambda_max);  x, cost, grad, A unchanged
+ * and d_accepted[m] (nullable) is 1 or 0.  Rows with state[m] == 1 are left untouched (d_accepted[m] = 0).
+ * d_grad / d_grad_trial and d_A / d_A_trial may each be NULL as a pair; lambda is an array of `dtype`, updated in
+ * double and rounded on store.
+ * Both: device pointers of `dtype` (d_status, d_state, d_accepted int32), asynchronous on the context's stream;
+ * n_rows > 0, 1 <= n_inputs <= 32 (GP_ERR_UNSUPPORTED beyond). */
+#define GP_DAMP_DIAGONAL 0
+#define GP_DAMP_IDENTITY 1
+int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
+                          const void* d_lambda, int damping, const void* d_prior_mean, const void* d_prior_prec,
+                          const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
+                          int64_t n_rows, int n_inputs);
+int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost, const void* d_cost_trial,
+                        void* d_grad, const void* d_grad_trial, void* d_A, const void* d_A_trial,
+                        void* d_lambda, const int32_t* d_status, int32_t* d_state, int32_t* d_accepted,
+                        const void* d_prior_mean, const void* d_prior_prec, double down, double up,
+                        double lambda_min, double lambda_max, double ftol, double xtol,
+                        int64_t n_rows, int n_inputs);
+
 /* ---- training objective (next after the predict path: SURVEY.md 8f rank 2) -------------------
  * For each of n_sets hyper-parameter vectors theta [n_sets][n_inputs+2]: what
  * GaussianProcess.loglikelihood + partial_devs compute (gp_emulator/GaussianProcess.py:52-125):

@@ -1,0 +1,238 @@
+#!/usr/bin/env python
+"""Damped Newton step on the device (gp_newton_step_device) against what a caller did before it, and one
+retrieve_bands iteration against its misfit_device alone.  Prints one JSON line per measurement and appends them to
+--out when one is given (profiles/r09_newton_step.txt quotes such a run's lines).
+
+    python tools/newton_step_timing.py [--legs device,host,iteration] [--out FILE] [--reps 20] [--warmup 5]
+    python tools/newton_step_timing.py --legs registers        # no GPU: compiles csrc/gp_newton_tu.hip once
+
+device     gp_newton_step_device at M = 1e5 rows, D in {11, 16}, both dtypes, trial and status out: the median of
+           --reps event-timed calls after --warmup.  Bytes are the algorithmic M (D^2 + 3 D + 1) sizeof(T) (A, x, grad
+           and trial, lambda; status not counted), as a fraction of the 6.3 TB/s achievable HBM rate of BASELINE.md's
+           metric table (8.0 TB/s is the specification).  gp_lm_update_device on the same rows with every row
+           accepting (so every row copies x, cost, grad and A) is timed beside it.
+host       in the same process, what the kernel replaces: the download of A and grad, numpy.linalg.solve of
+           (A + lambda diag A) step = -grad, and the upload of x + step (wall clock, median of 5).
+iteration  one retrieve_bands iteration at E = 12 (N = 250, D = 11, 1e5 rows, Gauss-Newton): misfit_device at the
+           trial rows + lm_update_device + newton_step_device, against the same misfit_device alone.
+
+Every leg that touches the GPU runs under the caller's time limit, e.g.
+    timeout -k 10 300 python tools/newton_step_timing.py --legs device,host,iteration --out profiles/r09_newton_step.txt
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from gp_emulator_amd import _lib  # noqa: E402
+from gp_emulator_amd import build as gp_build  # noqa: E402
+
+M = 100_000
+HBM_ACHIEVABLE = 6.3e12      # BASELINE.md, metric table: "6.3 TB/s (achievable)"
+
+
+def emit(a, **kw):
+    line = json.dumps(kw)
+    print(line, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as fh:
+            fh.write(line + "\n")
+
+
+def median_ms(ctx, fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ctx.synchronize()
+    e0, e1 = ctx.event(), ctx.event()
+    t = []
+    for _ in range(reps):
+        ctx.record(e0)
+        fn()
+        ctx.record(e1)
+        ctx.synchronize()
+        t.append(ctx.elapsed_ms(e0, e1))
+    ctx.event_destroy(e0)
+    ctx.event_destroy(e1)
+    return float(np.median(t))
+
+
+def wall_ms(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(t))
+
+
+def systems(D, dt, seed=0):
+    """x, grad, A = J^T J of D + 8 terms, lambda = 1e-2 for M rows."""
+    rs = np.random.RandomState(seed + D)
+    J = rs.standard_normal((M, D + 8, D)).astype(np.float32)
+    A = np.einsum("med,mef->mdf", J, J).astype(dt)
+    return rs.random_sample((M, D)).astype(dt), rs.standard_normal((M, D)).astype(dt), A, np.full(M, 1e-2, dt)
+
+
+def legs_device_host(a, legs):
+    ctx = _lib.default_context(0)
+    for D in (11, 16):
+        for prec in (np.float64, np.float32):
+            dt = np.dtype(prec)
+            isz = dt.itemsize
+            x, g, A, lam = systems(D, dt)
+            d_x, d_g, d_A, d_lam = (ctx.to_device(v) for v in (x, g, A, lam))
+            d_trial, d_status = ctx.malloc(M * D * isz), ctx.malloc(M * 4)
+            if "device" in legs:
+                ms = median_ms(ctx, lambda: ctx.newton_step_device(dt, d_x, d_g, d_A, d_lam, None, d_trial, d_status, M, D),
+                               a.reps, a.warmup)
+                nbytes = M * (D * D + 3 * D + 1) * isz
+                failed = int(np.count_nonzero(ctx.to_host(d_status, (M,), np.int32)))
+                emit(a, leg="newton_step_device", dtype=dt.name, rows=M, D=D, ms=round(ms, 4), MB=round(nbytes / 1e6, 1),
+                     GB_per_s=round(nbytes / (ms * 1e-3) / 1e9, 1), of_hbm_achievable=round(nbytes / (ms * 1e-3) / HBM_ACHIEVABLE, 3),
+                     rows_failed=failed)
+                # the update with every row accepting: trial costs below the costs
+                d_cost, d_cost_t = ctx.to_device(np.full(M, 2.0, dt)), ctx.to_device(np.full(M, 1.0, dt))
+                d_g2, d_A2 = ctx.to_device(g), ctx.to_device(A)
+                d_state = ctx.malloc(M * 4)
+                zero = np.zeros(M, np.int32)
+
+                def update():
+                    ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_g, d_g2, d_A, d_A2, d_lam, d_status, d_state,
+                                         None, M, D, ftol=0.0, xtol=-1.0)
+                two, e0, e1, t = np.full(M, 2.0, dt), ctx.event(), ctx.event(), []
+                ctx.h2d(d_state, zero)
+                for i in range(a.warmup + a.reps):       # (ftol = 0, xtol < 0: no row ever converges)
+                    ctx.h2d(d_cost, two)                  # every call accepts again
+                    ctx.record(e0)
+                    update()
+                    ctx.record(e1)
+                    ctx.synchronize()
+                    if i >= a.warmup:
+                        t.append(ctx.elapsed_ms(e0, e1))
+                ctx.event_destroy(e0)
+                ctx.event_destroy(e1)
+                ms_u = float(np.median(t))
+                ubytes = M * (2 * (D * D + 2 * D + 1) + 2) * isz
+                emit(a, leg="lm_update_device_all_accept", dtype=dt.name, rows=M, D=D, ms=round(ms_u, 4), MB=round(ubytes / 1e6, 1),
+                     GB_per_s=round(ubytes / (ms_u * 1e-3) / 1e9, 1))
+                for p in (d_cost, d_cost_t, d_g2, d_A2, d_state):
+                    ctx.free(p)
+                ctx.h2d(d_x, x), ctx.h2d(d_g, g), ctx.h2d(d_A, A), ctx.h2d(d_lam, lam)
+            if "host" in legs:
+                idx = np.arange(D)
+
+                def old():
+                    Ah, gh = np.array(ctx.to_host(d_A, (M, D, D), dt)), np.array(ctx.to_host(d_g, (M, D), dt))
+                    t0 = time.perf_counter()
+                    Ah[:, idx, idx] *= 1.0 + 1e-2
+                    step = -np.linalg.solve(Ah, gh[:, :, None])[:, :, 0]
+                    old.solve_ms.append((time.perf_counter() - t0) * 1e3)
+                    ctx.h2d(d_trial, (x + step).astype(dt))
+                old.solve_ms = []
+                ms_old = wall_ms(old, 5, 1)
+                emit(a, leg="download_solve_upload", dtype=dt.name, rows=M, D=D, ms=round(ms_old, 2),
+                     numpy_linalg_solve_ms=round(float(np.median(old.solve_ms[1:])), 2))
+            for p in (d_x, d_g, d_A, d_lam, d_trial, d_status):
+                ctx.free(p)
+
+
+def leg_iteration(a):
+    N, D, E = 250, 11, 12
+    ctx = _lib.default_context(0)
+    rs = np.random.RandomState(5)
+    inputs, thetas, invQts = rs.random_sample((N, D)), rs.random_sample((E, D + 2)), rs.random_sample((E, N))
+    for prec in (np.float64, np.float32):
+        dt = np.dtype(prec)
+        isz = dt.itemsize
+        batch = _lib.BatchModel(ctx, np.exp(thetas), inputs, invQts, None, prec)
+        d_x = ctx.to_device(rs.random_sample((M, D)).astype(dt))
+        d_obs = ctx.to_device(rs.standard_normal(E).astype(dt))
+        d_lam = ctx.to_device(np.full(M, 1e-2, dt))
+        d_state = ctx.to_device(np.zeros(M, np.int32))
+        bufs = [ctx.malloc(n * isz) for n in (M, M * D, M * D * D, M, M * D, M * D * D, M * D)]
+        d_cost, d_grad, d_A, d_cost_t, d_grad_t, d_A_t, d_trial = bufs
+        d_status = ctx.malloc(M * 4)
+
+        def misfit(rows, c, g, A):
+            batch.misfit_device(rows, d_obs, (1, 0), None, (0, 0), c, g, M, d_gn=A)
+
+        def newton():
+            ctx.newton_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D)
+
+        def iteration():
+            misfit(d_trial, d_cost_t, d_grad_t, d_A_t)
+            ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status, d_state,
+                                 None, M, D, ftol=0.0, xtol=-1.0)
+            newton()
+        misfit(d_x, d_cost, d_grad, d_A)
+        newton()
+        ms_m = median_ms(ctx, lambda: misfit(d_trial, d_cost_t, d_grad_t, d_A_t), a.reps, a.warmup)
+        ms_i = median_ms(ctx, iteration, a.reps, a.warmup)
+        emit(a, leg="retrieve_bands_iteration", dtype=dt.name, emulators=E, rows=M, D=D, n_train=N, second_order="gauss_newton",
+             misfit_device_ms=round(ms_m, 3), iteration_ms=round(ms_i, 3), update_plus_step_ms=round(ms_i - ms_m, 3),
+             iteration_over_misfit=round(ms_i / ms_m, 3))
+        for p in bufs + [d_x, d_obs, d_lam, d_state, d_status]:
+            ctx.free(p)
+        batch.close()
+
+
+def leg_registers(a):
+    """What the compiler reports for every instance in csrc/gp_newton_tu.hip, with build.py's flags."""
+    src = os.path.join(gp_build.CSRC, "gp_newton_tu.hip")
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [gp_build.HIPCC] + gp_build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", src,
+                                                   "-o", os.path.join(tmp, "newton.o")]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("command failed: %s\n%s" % (" ".join(cmd), r.stdout))
+    fmt = "%-30s %5s  %18s  %10s  %11s  %16s"
+    print(fmt % ("instance", "VGPRs", "scratch bytes/lane", "VGPR spill", "waves/SIMD", "static LDS bytes"))
+    name, row = None, {}
+
+    def flush():
+        if name:
+            print(fmt % (name, row["VGPRs"], row["ScratchSize [bytes/lane]"], row["VGPRs Spill"],
+                         row["Occupancy [waves/SIMD]"], row["LDS Size [bytes/block]"]))
+    for line in r.stdout.splitlines():
+        m = re.search(r"remark: +([^:]+): (\S+) \[-Rpass-analysis", line)
+        if not m:
+            continue
+        if m.group(1) == "Function Name":
+            flush()
+            t = re.search(r"\d+(newton_step_kernel|lm_update_kernel)I([fd])E", m.group(2))
+            name = "%s<%s>" % (t.group(1), {"f": "float", "d": "double"}[t.group(2)]) if t else m.group(2)
+            row = {}
+        else:
+            row[m.group(1)] = m.group(2)
+    flush()
+    for D in (11, 16, 32):          # gp_newton_kernel.hpp: newton_rows_per_wg, newton_pitch
+        rows, tri = (16 if D <= 16 else 8), D * (D + 1) // 2
+        pitch = tri + (16 - tri % 32) % 32
+        print("dynamic LDS of newton_step_kernel at D = %d: %d rows x %d doubles = %d bytes per workgroup" % (D, rows, pitch, rows * pitch * 8))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="device,host,iteration")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    legs = a.legs.split(",")
+    if "registers" in legs:
+        leg_registers(a)
+    if "device" in legs or "host" in legs:
+        legs_device_host(a, legs)
+    if "iteration" in legs:
+        leg_iteration(a)
