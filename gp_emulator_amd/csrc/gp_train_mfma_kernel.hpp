@@ -377,7 +377,10 @@ __global__ __launch_bounds__(tmThreads, 2) void likelihood_mfma_kernel(TrainArgs
 
   __syncthreads();                     // the last pass's readers of the panels are done
   // ---- the inverse -> global memory: the lower triangle in 128-byte runs (the gradient sums below read
-  // it back from L2); the mirror image (8-byte stores, a row apart) only when the caller wants the matrix
+  // it back from L2); the mirror image (8-byte stores, a row apart) only when the caller wants the matrix.  A diagonal
+  // tile holds both triangles, each with its own roundings (the panel steps compute both halves of a pivot block, the
+  // update forms C[k][i] W[k][j] and C[k][j] W[k][i]): its upper half is stored from the lower half's registers too,
+  // so the matrix the caller gets is bitwise symmetric and is the one the gradient sums below read
   const bool full = p.full_inverse != 0;
   static_for<tmTiles>([&](auto tc) __attribute__((always_inline)) {
     constexpr int t = decltype(tc)::value;
@@ -387,8 +390,8 @@ __global__ __launch_bounds__(tmThreads, 2) void likelihood_mfma_kernel(TrainArgs
     for (int r = 0; r < 4; ++r) {
       const int i = 16 * R + g + 4 * r;
       if (i < N && j < N) {
-        if (R != C || j <= i || full) A[(long long)i * N + j] = tl[t][r];
-        if (R != C && full) A[(long long)j * N + i] = tl[t][r];
+        if (R != C || j <= i) A[(long long)i * N + j] = tl[t][r];
+        if (full && (R != C || j < i)) A[(long long)j * N + i] = tl[t][r];
       }
     }
   });
