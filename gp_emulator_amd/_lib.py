@@ -71,6 +71,7 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_newton_step_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 7 + [c_i64, c_int]),
     "gp_lm_update_device": (c_int, [c_void_p, c_int] + [c_void_p] * 14 + [ctypes.c_double] * 6 + [c_i64, c_int]),
+    "gp_posterior_cov_device": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_i64, c_int]),
     "gp_hessian_f64": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_hessian_f32": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_reconstruct_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
@@ -345,6 +346,52 @@ def newton_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=No
     return step, trial, status
 
 
+def posterior_cov_numpy(A, prior_prec=None):
+    """The posterior covariance of ``gp_posterior_cov_device`` in float64 numpy, vectorised over the rows and written
+    out in the kernel's summation order (ascending index in the factorisation and in both substitutions):
+    ``(cov (M, D, D), sigma (M, D), status (M,) int32)``.  The explicit CPU branch of ``Context.posterior_cov`` and of
+    ``perband.retrieve_bands(return_cov=True)``, and the reference of the CPU tests; never a fallback.
+
+        A' = A (+ P), no damping,  L L^T = A' (lower triangle read),  C[:, j] = L^-T L^-1 e_j,
+        cov = C with the elements i >= j from column j's solve and the upper triangle mirrored from them,
+        sigma = sqrt(diag C);  status = k + 1 when pivot k is not > 0 or not finite, then cov and sigma are NaN."""
+    L = np.array(A, dtype=np.float64)
+    if L.ndim != 3 or L.shape[1] != L.shape[2]:
+        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+    M, D = L.shape[:2]
+    if prior_prec is not None:
+        L = L + np.asarray(prior_prec, dtype=np.float64).reshape(D, D)
+    status = np.zeros(M, np.int32)
+    W = np.zeros((M, D, D))                                         # W[:, i, j]: y_i, then z_i, of column j
+    with np.errstate(all="ignore"):
+        for k in range(D):
+            s = L[:, k:, k].copy()                                   # rows j >= k of column k
+            for q in range(k):
+                s -= L[:, k:, q] * L[:, k, q][:, None]
+            piv = s[:, 0]
+            bad = ~(piv > 0.0) | ~np.isfinite(piv)
+            status[(status == 0) & bad] = k + 1
+            dk = np.sqrt(piv)
+            L[:, k, k] = dk
+            L[:, k + 1:, k] = s[:, 1:] / dk[:, None]
+        for i in range(D):                                           # y = L^-1 e_j, the columns j <= i side by side
+            s = np.zeros((M, i + 1))
+            s[:, i] = 1.0
+            for k in range(i):                                       # (column j takes the terms k >= j)
+                s[:, :k + 1] -= L[:, i, k][:, None] * W[:, k, :k + 1]
+            W[:, i, :i + 1] = s / L[:, i, i][:, None]
+        for i in range(D - 1, -1, -1):                               # z = L^-T y, down to row j
+            a = W[:, i, :i + 1].copy()
+            for k in range(i + 1, D):
+                a -= L[:, k, i][:, None] * W[:, k, :i + 1]
+            W[:, i, :i + 1] = a / L[:, i, i][:, None]
+        W[status != 0] = np.nan
+        cov = np.tril(W) + np.transpose(np.tril(W, -1), (0, 2, 1))
+        idx = np.arange(D)
+        sigma = np.sqrt(W[:, idx, idx])
+    return cov, sigma, status
+
+
 class Context:
     """One device + one HIP stream (gp_ctx).  Use one per thread / per GPU."""
 
@@ -476,6 +523,42 @@ class Context:
                                            d_A_trial, d_lambda, d_status, d_state, d_accepted, d_prior_mean, d_prior_prec,
                                            float(down), float(up), float(lambda_min), float(lambda_max), float(ftol),
                                            float(xtol), int(n_rows), int(n_inputs)), "gp_lm_update_device")
+
+    def posterior_cov_device(self, dtype, d_A, d_prior_prec, d_cov, d_sigma, d_status, n_rows, n_inputs):
+        """Asynchronous posterior covariance of ``n_rows`` systems on the device (``gp_posterior_cov_device``):
+        ``cov = (A + P)^-1`` row by row by Cholesky and unit-vector solves, symmetric bit for bit, ``sigma`` the square
+        roots of its diagonal, ``status`` int32 (0, or the 1-based index of the failed pivot: then cov and sigma are
+        NaN).  Device pointers of ``dtype``; ``d_prior_prec`` and one of ``d_cov`` / ``d_sigma`` may be None."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_posterior_cov_device(self.h, code, d_A, d_prior_prec, d_cov, d_sigma, d_status, int(n_rows),
+                                               int(n_inputs)), "gp_posterior_cov_device")
+
+    def posterior_cov(self, A, prior_prec=None, precision=None, is_gpu=True):
+        """``(cov (M, D, D), sigma (M, D), status (M,) int32)`` of the posterior covariance ``(A + P)^-1`` for the host
+        array ``A`` (M, D, D) and ``prior_prec`` (D, D) or None: uploads, launches ``gp_posterior_cov_device``,
+        downloads.  ``precision`` is the device dtype (default: float32 when ``A`` is float32, else float64).
+        ``is_gpu=False`` is the explicit numpy branch (``posterior_cov_numpy``: the same algorithm in float64); never a
+        fallback."""
+        if not is_gpu:
+            return posterior_cov_numpy(A, prior_prec)
+        A = np.asarray(A)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+        dt = np.dtype(precision if precision is not None else (np.float32 if A.dtype == np.float32 else np.float64))
+        M, D = A.shape[:2]
+        ptrs = []
+        try:
+            ptrs.append(self.to_device(np.ascontiguousarray(A, dtype=dt)))
+            ptrs.append(self.to_device(np.ascontiguousarray(prior_prec, dtype=dt).reshape(D, D)) if prior_prec is not None else None)
+            d_cov, d_sigma, d_status = self.malloc(M * D * D * dt.itemsize), self.malloc(M * D * dt.itemsize), self.malloc(M * 4)
+            ptrs += [d_cov, d_sigma, d_status]
+            self.posterior_cov_device(dt, ptrs[0], ptrs[1], d_cov, d_sigma, d_status, M, D)
+            return (np.array(self.to_host(d_cov, (M, D, D), dt)), np.array(self.to_host(d_sigma, (M, D), dt)),
+                    np.array(self.to_host(d_status, (M,), np.int32)))
+        finally:
+            for p in ptrs:
+                if p is not None:
+                    self.free(p)
 
     def newton_step(self, x, grad, A, lam, damping="diagonal", prior=None, bounds=None, precision=None, is_gpu=True):
         """``(step, trial, status)`` of the damped Newton step for host arrays ``x`` (M, D), ``grad`` (M, D), ``A``

@@ -1,4 +1,4 @@
-// Launch sizing, and predict, Hessian, Newton step and LM update on device buffers.
+// Launch sizing, and predict, Hessian, Newton step, LM update and posterior covariance on device buffers.
 #include "gp_host.hpp"
 
 #include "gp_generic_kernel.hpp"
@@ -8,6 +8,7 @@
 #include "gp_launchers.hpp"
 #include "gp_misfit_kernel.hpp"
 #include "gp_newton_kernel.hpp"
+#include "gp_posterior_cov_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
 
 // The per-size launchers by their run-time size: one switch over the compiled NK, one over the compiled NB.
@@ -435,6 +436,28 @@ int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, 
     a.d = n_inputs;
     hipError_t e = gpk::launch_lm_update<T>(a, ctx->stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "lm update kernel launch: %s", hipGetErrorString(e));
+    return (int)GP_OK;
+  });
+}
+
+int gp_posterior_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, void* d_cov, void* d_sigma,
+                            int32_t* d_status, int64_t n_rows, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_A || !d_status || (!d_cov && !d_sigma)) return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::PosteriorCovArgs<T> a;
+    a.A = as<T>(d_A);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.cov = as<T>(d_cov);
+    a.sigma = as<T>(d_sigma);
+    a.status = d_status;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    hipError_t e = gpk::launch_posterior_cov<T>(a, ctx->stream);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "posterior covariance kernel launch: %s", hipGetErrorString(e));
     return (int)GP_OK;
   });
 }

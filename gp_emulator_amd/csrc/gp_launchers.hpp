@@ -15,6 +15,7 @@ template <typename T> struct HessCombineArgs;
 template <typename T> struct BandMisfitArgs;
 template <typename T> struct NewtonArgs;
 template <typename T> struct LmUpdateArgs;
+template <typename T> struct PosteriorCovArgs;
 template <typename T> struct ReconArgs;
 template <typename T> struct MisfitArgs;
 struct TrainArgs;
@@ -32,6 +33,7 @@ template <typename T> hipError_t launch_band_misfit_fold(const BandMisfitArgs<T>
 template <typename T> hipError_t launch_band_misfit_add(const T* gn, T* hess, long long n, hipStream_t);
 template <typename T> hipError_t launch_newton_step(const NewtonArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_lm_update(const LmUpdateArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_posterior_cov(const PosteriorCovArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_reconstruct(const ReconArgs<T>&, int wide, int cus, hipStream_t);
 template <typename T> hipError_t launch_misfit(const MisfitArgs<T>&, int cus, hipStream_t);
 template <typename T> hipError_t launch_gauss_newton(const T* deriv, const T* A, T* gn, long long M, int P, int D, int cus, hipStream_t);

@@ -361,7 +361,7 @@ LAMBDA_MIN, LAMBDA_MAX = 1e-12, 1e12     # the clamps of retrieve_bands' damping
 
 def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prior=None, bounds=None, lam0=1e-2,
                    max_iter=20, down=1.0 / 3.0, up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64,
-                   device=None, step_fn=None):
+                   device=None, step_fn=None, return_cov=False):
     """Levenberg-Marquardt retrieval of M state vectors at once on E per-band emulators: minimises, row by row,
 
         F(x) = 1/2 sum_e w (mu_e(x) - obs[e])^2  (+ 1/2 (x - x0)^T P (x - x0) with ``prior=(x0 (D,), P (D, D))``)
@@ -382,7 +382,18 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     inside the loop but ``state``, every fourth iteration, to stop when every row has converged.  ``is_gpu=False`` is
     the explicit numpy branch, the same loop from ``_misfit_numpy`` and ``_lib.newton_step_numpy``; never a fallback.
     ``step_fn(x, grad, A, lam) -> (step, trial, status)`` replaces the Newton step in the CPU tests of the loop's
-    logic: the loop then runs on the host whatever ``is_gpu`` says."""
+    logic: the loop then runs on the host whatever ``is_gpu`` says.
+
+    ``return_cov=True`` appends ``cov (M, D, D)``, ``sigma (M, D)`` and ``cov_status (M,) int32`` to the five: the
+    posterior covariance ``C = (A + P)^-1`` of every row, the square roots of its diagonal (the ``x +- sigma`` of the
+    retrieval) and 0, or the 1-based index of the pivot at which ``A + P`` failed to factor, in which case the row's
+    ``cov`` and ``sigma`` are NaN.  ``A`` is the matrix of the row's last accepted step (the one at the returned
+    ``X``), WITHOUT the damping: the Gauss-Newton term by default; with ``second_order="full"`` the full
+    second-order term, which may be indefinite away from a minimum -- ``cov_status`` then says so.  Active bounds are
+    ignored: a component held at its bound gets the unconstrained variance.  ``C`` is a covariance only when
+    ``weights`` are the inverse variances of the observations (and ``P`` that of the prior).  On the GPU this is one
+    ``posterior_cov_device`` call on the loop's own device arrays after the loop, and only the three results come
+    back; on the numpy branch ``_lib.posterior_cov_numpy`` on the loop's ``A``.  With ``False`` nothing changes."""
     if second_order not in ("gauss_newton", "full"):
         raise ValueError("second_order must be 'gauss_newton' or 'full'")
     X0 = np.asarray(X0)
@@ -416,6 +427,8 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
                                       down, up, LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
             if it % 4 == 3 and np.all(state == 1):
                 break
+        if return_cov:
+            return (X, cost, state, n_acc, lam) + _lib.posterior_cov_numpy(A, prior[1] if prior is not None else None)
         return X, cost, state, n_acc, lam
 
     ctx = _lib.default_context(device)
@@ -473,6 +486,12 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
         X, cost, lam = (np.array(ctx.to_host(p, s, dt)) for p, s in ((d_x, (M, D)), (d_cost, (M,)), (d_lam, (M,))))
         state = np.array(ctx.to_host(d_state, (M,), np.int32))
         n_acc = np.array(ctx.to_host(d_acc, (done, M), np.int32)).sum(axis=0, dtype=np.int32) if done else np.zeros(M, np.int32)
+        if return_cov:
+            d_cov, d_sigma, d_cstat = alloc(M * D * D * isz), alloc(M * D * isz), alloc(M * 4)
+            ctx.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D)
+            ctx.synchronize()
+            return (X, cost, state, n_acc, lam, np.array(ctx.to_host(d_cov, (M, D, D), dt)),
+                    np.array(ctx.to_host(d_sigma, (M, D), dt)), np.array(ctx.to_host(d_cstat, (M,), np.int32)))
         return X, cost, state, n_acc, lam
     finally:
         for p in held:

@@ -393,6 +393,31 @@ int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, 
                         double lambda_min, double lambda_max, double ftol, double xtol,
                         int64_t n_rows, int n_inputs);
 
+/* ---- posterior covariance ----------------------------------------------------------------------------
+ * The inverse of the matrix the Newton step factors, without the damping: what a retrieval reports beside its
+ * state as x +- sigma, from the d_A (and prior precision) that the loop above leaves on the device.  For each of
+ * n_rows rows, D = n_inputs,
+ *   A' = A[m] (+ P)                      d_A [n_rows][D][D];  d_prior_prec P [D][D], shared by all rows, or NULL;
+ *                                        NO damping
+ *   L L^T = A'                           the factorisation of gp_newton_step_device: the lower triangle of A' is
+ *                                        read, the upper is never touched; same order, same pivot test
+ *   C[:, j] = L^-T L^-1 e_j              every column a Cholesky solve of a unit vector
+ *   cov[m]   = C                         d_cov [n_rows][D][D]: elements i >= j from column j's solve, the upper
+ *                                        triangle mirrored from them, so cov[m] is symmetric bit for bit
+ *   sigma[m] = sqrt(C_dd)                d_sigma [n_rows][D], from the unrounded diagonal
+ *   status[m] = 0, or k + 1 when pivot k (0-based) is not > 0 or not finite; then every element of cov[m] and of
+ *                                        sigma[m] is a quiet NaN (a failed row does not read as "no uncertainty")
+ * Either of d_cov and d_sigma may be NULL, not both; d_status is required.  Everything runs in double in both
+ * precisions, cov and sigma each rounded to `dtype` once on store; every sum is one fma chain in ascending index
+ * (the factorisation, the forward substitution from e_j, the backward substitution down to row j).  No atomics: a
+ * row's result does not depend on the other rows, on its place in the call or on the grid, and two calls agree bit
+ * for bit.  C is a covariance when A is a sum of inverse-variance weighted terms; an indefinite A (a full
+ * second-order term away from the minimum) shows in status.
+ * Device pointers of `dtype` (d_status int32), asynchronous on the context's stream; n_rows > 0,
+ * 1 <= n_inputs <= 32 (GP_ERR_UNSUPPORTED beyond). */
+int gp_posterior_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec,
+                            void* d_cov, void* d_sigma, int32_t* d_status, int64_t n_rows, int n_inputs);
+
 /* ---- training objective (next after the predict path: SURVEY.md 8f rank 2) -------------------
  * For each of n_sets hyper-parameter vectors theta [n_sets][n_inputs+2]: what
  * GaussianProcess.loglikelihood + partial_devs compute (gp_emulator/GaussianProcess.py:52-125):

@@ -4,6 +4,7 @@ retrieve_bands iteration against its misfit_device alone.  Prints one JSON line 
 --out when one is given (profiles/r09_newton_step.txt quotes such a run's lines).
 
     python tools/newton_step_timing.py [--legs device,host,iteration] [--out FILE] [--reps 20] [--warmup 5]
+    python tools/newton_step_timing.py --legs posterior [--out FILE] [--reps 50] [--warmup 5]
     python tools/newton_step_timing.py --legs registers        # no GPU: compiles csrc/gp_newton_tu.hip once
 
 device     gp_newton_step_device at M = 1e5 rows, D in {11, 16}, both dtypes, trial and status out: the median of
@@ -15,6 +16,11 @@ host       in the same process, what the kernel replaces: the download of A and 
            (A + lambda diag A) step = -grad, and the upload of x + step (wall clock, median of 5).
 iteration  one retrieve_bands iteration at E = 12 (N = 250, D = 11, 1e5 rows, Gauss-Newton): misfit_device at the
            trial rows + lm_update_device + newton_step_device, against the same misfit_device alone.
+posterior  gp_posterior_cov_device (cov, sigma and status out) beside gp_newton_step_device (trial and status out) on the
+           same resident rows: M = 1e5, D in {11, 16}, both dtypes, the device leg's matrices.  The two calls alternate
+           inside one loop, each between its own pair of events, so that both see the same machine; per entry the
+           median, the minimum and the maximum of --reps calls after --warmup of each, and the ratio of the medians
+           (profiles/r10_posterior_cov.txt quotes such a run's lines).
 
 Every leg that touches the GPU runs under the caller's time limit, e.g.
     timeout -k 10 300 python tools/newton_step_timing.py --legs device,host,iteration --out profiles/r09_newton_step.txt
@@ -147,6 +153,42 @@ def legs_device_host(a, legs):
                 ctx.free(p)
 
 
+def leg_posterior(a):
+    ctx = _lib.default_context(0)
+    for D in (11, 16):
+        for prec in (np.float64, np.float32):
+            dt = np.dtype(prec)
+            isz = dt.itemsize
+            x, g, A, lam = systems(D, dt)
+            d_x, d_g, d_A, d_lam = (ctx.to_device(v) for v in (x, g, A, lam))
+            d_trial, d_status = ctx.malloc(M * D * isz), ctx.malloc(M * 4)
+            d_cov, d_sigma, d_cstat = ctx.malloc(M * D * D * isz), ctx.malloc(M * D * isz), ctx.malloc(M * 4)
+            calls = dict(step=lambda: ctx.newton_step_device(dt, d_x, d_g, d_A, d_lam, None, d_trial, d_status, M, D),
+                         cov=lambda: ctx.posterior_cov_device(dt, d_A, None, d_cov, d_sigma, d_cstat, M, D))
+            t = dict(step=[], cov=[])
+            e0, e1 = ctx.event(), ctx.event()
+            for i in range(a.warmup + a.reps):
+                for name in ("step", "cov"):                  # alternating: both see the same machine
+                    ctx.record(e0)
+                    calls[name]()
+                    ctx.record(e1)
+                    ctx.synchronize()
+                    if i >= a.warmup:
+                        t[name].append(ctx.elapsed_ms(e0, e1))
+            ctx.event_destroy(e0)
+            ctx.event_destroy(e1)
+            failed = int(np.count_nonzero(ctx.to_host(d_cstat, (M,), np.int32)))
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            nbytes = M * (2 * D * D + D) * isz                 # A in, cov and sigma out (status not counted)
+            emit(a, leg="posterior_cov_device", dtype=dt.name, rows=M, D=D, reps=a.reps, ms=round(med["cov"], 4),
+                 ms_min=round(min(t["cov"]), 4), ms_max=round(max(t["cov"]), 4), MB=round(nbytes / 1e6, 1),
+                 GB_per_s=round(nbytes / (med["cov"] * 1e-3) / 1e9, 1), rows_failed=failed,
+                 newton_step_ms=round(med["step"], 4), newton_step_ms_min=round(min(t["step"]), 4),
+                 newton_step_ms_max=round(max(t["step"]), 4), cov_over_step=round(med["cov"] / med["step"], 2))
+            for p in (d_x, d_g, d_A, d_lam, d_trial, d_status, d_cov, d_sigma, d_cstat):
+                ctx.free(p)
+
+
 def leg_iteration(a):
     N, D, E = 250, 11, 12
     ctx = _lib.default_context(0)
@@ -210,7 +252,7 @@ def leg_registers(a):
             continue
         if m.group(1) == "Function Name":
             flush()
-            t = re.search(r"\d+(newton_step_kernel|lm_update_kernel)I([fd])E", m.group(2))
+            t = re.search(r"\d+(newton_step_kernel|lm_update_kernel|posterior_cov_kernel)I([fd])E", m.group(2))
             name = "%s<%s>" % (t.group(1), {"f": "float", "d": "double"}[t.group(2)]) if t else m.group(2)
             row = {}
         else:
@@ -220,6 +262,10 @@ def leg_registers(a):
         rows, tri = (16 if D <= 16 else 8), D * (D + 1) // 2
         pitch = tri + (16 - tri % 32) % 32
         print("dynamic LDS of newton_step_kernel at D = %d: %d rows x %d doubles = %d bytes per workgroup" % (D, rows, pitch, rows * pitch * 8))
+    for D in (11, 16, 32):          # gp_posterior_cov_kernel.hpp: post_cov_rows_per_wg, two triangles per row
+        rows, tri = (8 if D <= 16 else 4), D * (D + 1) // 2
+        pitch = tri + (16 - tri % 32) % 32
+        print("dynamic LDS of posterior_cov_kernel at D = %d: %d rows x 2 x %d doubles = %d bytes per workgroup" % (D, rows, pitch, rows * 2 * pitch * 8))
 
 
 if __name__ == "__main__":
@@ -236,3 +282,5 @@ if __name__ == "__main__":
         legs_device_host(a, legs)
     if "iteration" in legs:
         leg_iteration(a)
+    if "posterior" in legs:
+        leg_posterior(a)
