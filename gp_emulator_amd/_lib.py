@@ -83,6 +83,8 @@ SIGNATURES = {
     "gp_mv_misfit_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64,
                                     c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int]),
     "gp_mv_gauss_newton_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
+    "gp_mv_weight_gram_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int]),
+    "gp_mv_gauss_newton_rows_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int]),
     "gp_mv_misfit_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                   c_void_p, c_i64, c_int, c_void_p]),
     "gp_mv_misfit_host_checked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
@@ -499,6 +501,22 @@ class Context:
         code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
         check(self.lib.gp_mv_gauss_newton_device(self.h, code, d_deriv, d_A, d_gn, int(n_rows), int(n_pcs),
                                                  int(n_inputs)), "gp_mv_gauss_newton_device")
+
+    def mv_weight_gram_device(self, dtype, d_basis, d_weights, weights_stride, d_gram, n_rows, n_pcs, n_bands):
+        """gram[m] = basis @ diag(w[m]) @ basis.T, [M][P][P], symmetric bit for bit, on the device (asynchronous;
+        ``gp_mv_weight_gram_device``).  Row m of the weights is ``weights_stride`` elements behind row m - 1; 0 = one
+        vector for all rows."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_mv_weight_gram_device(self.h, code, d_basis, d_weights, int(weights_stride), d_gram,
+                                                int(n_rows), int(n_pcs), int(n_bands)), "gp_mv_weight_gram_device")
+
+    def mv_gauss_newton_rows_device(self, dtype, d_deriv, d_gram, gram_stride, d_gn, n_rows, n_pcs, n_inputs):
+        """gn[m] = deriv[:, m].T @ gram[m] @ deriv[:, m] on the device, exactly symmetric (asynchronous;
+        ``gp_mv_gauss_newton_rows_device``).  Row m's matrix is at ``d_gram + m * gram_stride`` elements; 0 = one
+        matrix for all rows, which is ``mv_gauss_newton_device``."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_mv_gauss_newton_rows_device(self.h, code, d_deriv, d_gram, int(gram_stride), d_gn, int(n_rows),
+                                                      int(n_pcs), int(n_inputs)), "gp_mv_gauss_newton_rows_device")
 
     def newton_step_device(self, dtype, d_x, d_grad, d_A, d_lambda, d_step, d_trial, d_status, n_rows, n_inputs,
                            damping="diagonal", d_prior_mean=None, d_prior_prec=None, d_lo=None, d_hi=None):
@@ -936,25 +954,25 @@ class BatchModel(Model):
         return out
 
 
-GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT = 0, 1, 2, 3, 4
+GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM = 0, 1, 2, 3, 4, 5
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
                 6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
-                10: "misfit"}
+                10: "misfit", 11: "mv_gram"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
-             "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT}
+             "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM}
 
 
 def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_pcs=0, n_bands=0,
                 compute_units=256, aligned16=True):
-    """How the device call ``op`` ("predict", "mean_grad", "hessian", "reconstruct", "misfit") on ``n_rows`` rows would be
+    """How the device call ``op`` ("predict", "mean_grad", "hessian", "reconstruct", "misfit", "mv_gram") on ``n_rows`` rows would be
     launched on a device of ``compute_units`` (``gp_launch_plan``: host arithmetic shared with the launch path, no
     GPU needed).  Returns dict(kernel, rows_per_item, items, workgroups, rest_items, rest_workgroups): the
     kernel family and instance (a ``PLAN_KERNELS`` name), the rows of one work item, and the work items and
     workgroups of the launch (``rest_*``: the windowed Hessian's second launch for the rows behind the last whole
     64-row group).  ``items > workgroups``: workgroups run several items.  ``aligned16``: a Hessian call's row and
-    output pointers are 16-byte aligned.  reconstruct and misfit take ``n_pcs`` and ``n_bands``."""
+    output pointers are 16-byte aligned.  reconstruct, misfit and mv_gram take ``n_pcs`` and ``n_bands``."""
     code = _PLAN_OPS[op]
-    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT)
+    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM)
     k, wg, rwg, rpi = c_int(0), c_int(0), c_int(0), c_int(0)
     items, ritems = c_i64(0), c_i64(0)
     check(load().gp_launch_plan(

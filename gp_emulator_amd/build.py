@@ -122,6 +122,7 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
         units += [("gp_generic_tu.hip", "generic_" + tname, t), ("gp_few_tu.hip", "few_" + tname, t),
                   ("gp_hessian_tu.hip", "hess_" + tname, t)]
     units += [("gp_reconstruct_tu.hip", "reconstruct", []), ("gp_misfit_tu.hip", "misfit", []),
+              ("gp_gram_tu.hip", "gram", []),
               ("gp_band_misfit_tu.hip", "band_misfit", []), ("gp_newton_tu.hip", "newton", []),
               ("gp_train_tu.hip", "train", [])]
     # the host units (gp_host.hpp lists them)

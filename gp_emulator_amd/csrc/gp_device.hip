@@ -256,6 +256,13 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     k = GP_PLAN_MISFIT;
     rpi = gpk::mkRows;
     g = gpk::plan_misfit(n_rows, gpk::mkRows, gpk::misfit_cap(compute_units));
+  } else if (op == GP_OP_MV_GRAM) {
+    // (n_inputs = n_pcs here; aux = n_bands)
+    if (n_inputs <= 0 || aux <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    if (n_inputs > gpk::mkMaxPcs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels are compiled for n_pcs <= %d", gpk::mkMaxPcs);
+    k = GP_PLAN_MV_GRAM;
+    rpi = gpk::mkRows;
+    g = gpk::plan_misfit(n_rows, gpk::mkRows, gpk::gram_cap(compute_units, n_inputs, f64 ? 8 : 4));
   } else if (op == GP_OP_PREDICT || op == GP_OP_MEAN_GRAD || op == GP_OP_HESSIAN) {
     int kd, knb;
     int rc = pick_kernel(n_train, n_inputs, &kd, &knb);

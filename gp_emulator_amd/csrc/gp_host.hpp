@@ -5,7 +5,7 @@
 //   gp_device.hip     launch sizing; predict, Hessian, Newton step, LM update, posterior covariance on device buffers
 //   gp_host_path.hip  predict and Hessian on host arrays: the slab pipeline, the pinned-array path
 //   gp_folds.hip      folds over the emulators of a batch: the weighted Hessian, the per-band misfit
-//   gp_mv.hip         the multivariate emulator: reconstruction, misfit, content digest
+//   gp_mv.hip         the multivariate emulator: reconstruction, misfit, per-row Gram matrices, content digest
 // A template over the compute type T that another unit uses is explicitly instantiated in the unit that defines it.
 #pragma once
 #include "gp_predict_hip.h"

@@ -93,4 +93,15 @@ inline GridPlan plan_misfit(long long n_rows, int rows_per_item, long long cap) 
   return p;
 }
 
+// weight_gram_kernel: items and rounds as misfit_kernel's (plan_misfit).  The instance is the number of 16-pair
+// blocks of the n_pcs (n_pcs + 1) / 2 pairs p <= q; its accumulators (8 reals per block and lane, 16 registers in
+// fp64) decide how many 4-wave workgroups a CU holds, which is also what the kernel is compiled for.
+constexpr int gram_blocks(int n_pcs) { return (n_pcs * (n_pcs + 1) / 2 + 15) / 16; }
+constexpr int gram_wgs_per_cu(int blocks, int elem_bytes) {
+  return elem_bytes == 8 ? (blocks <= 2 ? 4 : blocks <= 3 ? 3 : blocks <= 7 ? 2 : 1) : (blocks <= 4 ? 4 : blocks <= 7 ? 3 : 2);
+}
+inline long long gram_cap(int compute_units, int n_pcs, int elem_bytes) {
+  return (long long)compute_units * gram_wgs_per_cu(gram_blocks(n_pcs), elem_bytes);
+}
+
 }  // namespace gpk

@@ -18,6 +18,7 @@ template <typename T> struct LmUpdateArgs;
 template <typename T> struct PosteriorCovArgs;
 template <typename T> struct ReconArgs;
 template <typename T> struct MisfitArgs;
+template <typename T> struct GramArgs;
 struct TrainArgs;
 
 #pragma GCC visibility push(hidden)      // (the launchers are the library's own)
@@ -37,6 +38,8 @@ template <typename T> hipError_t launch_posterior_cov(const PosteriorCovArgs<T>&
 template <typename T> hipError_t launch_reconstruct(const ReconArgs<T>&, int wide, int cus, hipStream_t);
 template <typename T> hipError_t launch_misfit(const MisfitArgs<T>&, int cus, hipStream_t);
 template <typename T> hipError_t launch_gauss_newton(const T* deriv, const T* A, T* gn, long long M, int P, int D, int cus, hipStream_t);
+template <typename T> hipError_t launch_gauss_newton_rows(const T* deriv, const T* A, long long a_stride, T* gn, long long M, int P, int D, int cus, hipStream_t);
+template <typename T> hipError_t launch_weight_gram(const GramArgs<T>&, int cus, hipStream_t);
 
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);      // fp64 only
 #pragma GCC visibility pop

@@ -211,16 +211,19 @@ __global__ __launch_bounds__(mkThreads, 4) void misfit_kernel(MisfitArgs<T> p) {
 // Gauss-Newton term gn[m][d][e] = sum_pq deriv[p][m][d] A[p][q] deriv[q][m][e] for a P x P matrix A
 // (basis diag(w) basis^T for weights shared by all rows).  A thread per (m, d): t[q] = sum_p deriv[p][m][d] A[p][q],
 // then the entries e >= d, each written to [d][e] and [e][d]: exactly symmetric, as the Hessians are.
+// PER_ROW: row m has a matrix of its own at A + m * a_stride (weight_gram_kernel's, for weights that differ from
+// row to row), read from global memory where the shared form reads its LDS copy; the chains are the same, so rows
+// whose matrices all equal A give the shared form's bits.
 constexpr int gnThreads = 256;
-template <typename T>
+template <typename T, bool PER_ROW = false>
 __global__ __launch_bounds__(gnThreads) void gauss_newton_kernel(const T* deriv, const T* A, T* gn, long long M, int P,
-                                                                int D) {
-  __shared__ T s_A[mkMaxPcs][mkMaxPcs];
-  {
+                                                                int D, long long a_stride = 0) {
+  __shared__ T s_A[PER_ROW ? 1 : mkMaxPcs][PER_ROW ? 1 : mkMaxPcs];
+  if constexpr (!PER_ROW) {
     const int q0 = threadIdx.x / mkMaxPcs, q1 = threadIdx.x % mkMaxPcs;
     s_A[q0][q1] = (q0 < P && q1 < P) ? A[q0 * P + q1] : T(0);
+    __syncthreads();
   }
-  __syncthreads();
   const long long n = M * D;
   for (long long idx = (long long)blockIdx.x * gnThreads + threadIdx.x; idx < n; idx += (long long)gridDim.x * gnThreads) {
     const long long m = idx / D;
@@ -230,8 +233,14 @@ __global__ __launch_bounds__(gnThreads) void gauss_newton_kernel(const T* deriv,
     for (int q = 0; q < mkMaxPcs; ++q) t[q] = T(0);
     for (int q0 = 0; q0 < P; ++q0) {
       const T dv = deriv[((long long)q0 * M + m) * D + d];
+      if constexpr (PER_ROW) {
+        const T* Am = A + m * a_stride + q0 * P;
 #pragma unroll
-      for (int q = 0; q < mkMaxPcs; ++q) t[q] = fma(dv, s_A[q0][q], t[q]);
+        for (int q = 0; q < mkMaxPcs; ++q) t[q] = fma(dv, q < P ? Am[q] : T(0), t[q]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < mkMaxPcs; ++q) t[q] = fma(dv, s_A[q0][q], t[q]);
+      }
     }
     for (int e = d; e < D; ++e) {
       T v = T(0);

@@ -1,6 +1,7 @@
 // The multivariate emulator: reconstruction, observation misfit and the content digest of its host data.
 #include "gp_host.hpp"
 
+#include "gp_gram_kernel.hpp"
 #include "gp_launchers.hpp"
 #include "gp_misfit_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
@@ -140,6 +141,33 @@ static int gauss_newton_on(gp_ctx* ctx, int dtype, const void* d_deriv, const vo
   });
 }
 
+// ---- per-row weights: the Gram matrix of every row and the Gauss-Newton contraction with it (gp_gram_kernel.hpp) --
+// Everything but the launch is checked before the device is touched: the entries below call these first.
+static int weight_gram_args(const gp_ctx* ctx, int dtype, const void* d_basis, const void* d_weights, int64_t weights_stride,
+                            const void* d_gram, int64_t n_rows, int n_pcs, int n_bands) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_basis || !d_weights || !d_gram) return fail(GP_ERR_INVALID, "null device pointer");
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_rows <= 0 || n_pcs <= 0 || n_bands <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (weights_stride < 0 || (weights_stride != 0 && weights_stride < n_bands))
+    return fail(GP_ERR_INVALID, "weights_stride is 0 (one vector for all rows) or >= n_bands");
+  if (n_pcs > gpk::mkMaxPcs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels are compiled for n_pcs <= %d", gpk::mkMaxPcs);
+  return GP_OK;
+}
+
+static int gauss_newton_rows_args(const gp_ctx* ctx, int dtype, const void* d_deriv, const void* d_gram, int64_t gram_stride,
+                                  const void* d_gn, int64_t n_rows, int n_pcs, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_deriv || !d_gram || !d_gn) return fail(GP_ERR_INVALID, "null device pointer");
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_rows <= 0 || n_pcs <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_pcs > gpk::mkMaxPcs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels are compiled for n_pcs <= %d", gpk::mkMaxPcs);
+  if (n_inputs > gpk::mkMaxInputs) return fail(GP_ERR_UNSUPPORTED, "misfit kernels serve n_inputs <= %d", gpk::mkMaxInputs);
+  if (gram_stride < 0 || (gram_stride != 0 && gram_stride < (int64_t)n_pcs * n_pcs))
+    return fail(GP_ERR_INVALID, "gram_stride is 0 (one matrix for all rows) or >= n_pcs^2");
+  return GP_OK;
+}
+
 // rows of `width` reals, `stride` reals apart on the host, packed on the device
 template <typename T>
 static hipError_t upload_rows(T* dst, const T* src, int64_t stride, int64_t rows, int64_t width, hipStream_t st) {
@@ -267,6 +295,34 @@ int gp_mv_gauss_newton_device(gp_ctx* ctx, int dtype, const void* d_deriv, const
   if (!ctx) return fail(GP_ERR_INVALID, "null context");
   HIP_TRY(hipSetDevice(ctx->device));
   return gauss_newton_on(ctx, dtype, d_deriv, d_A, d_gn, n_rows, n_pcs, n_inputs, ctx->stream);
+}
+
+int gp_mv_weight_gram_device(gp_ctx* ctx, int dtype, const void* d_basis, const void* d_weights, int64_t weights_stride,
+                             void* d_gram, int64_t n_rows, int n_pcs, int n_bands) {
+  if (int rc = weight_gram_args(ctx, dtype, d_basis, d_weights, weights_stride, d_gram, n_rows, n_pcs, n_bands)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) -> int {
+    using T = GP_TAG_TYPE(t);
+    gpk::GramArgs<T> a{as<T>(d_basis), as<T>(d_weights), as<T>(d_gram), n_rows, weights_stride, n_pcs, n_bands};
+    const hipError_t e = gpk::launch_weight_gram<T>(a, ctx->compute_units, ctx->stream);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "weight gram kernel launch: %s", hipGetErrorString(e));
+    return GP_OK;
+  });
+}
+
+int gp_mv_gauss_newton_rows_device(gp_ctx* ctx, int dtype, const void* d_deriv, const void* d_gram, int64_t gram_stride,
+                                   void* d_gn, int64_t n_rows, int n_pcs, int n_inputs) {
+  if (int rc = gauss_newton_rows_args(ctx, dtype, d_deriv, d_gram, gram_stride, d_gn, n_rows, n_pcs, n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  // stride 0 IS the shared form: its kernel instance, its bits
+  if (gram_stride == 0) return gauss_newton_on(ctx, dtype, d_deriv, d_gram, d_gn, n_rows, n_pcs, n_inputs, ctx->stream);
+  return for_dtype(dtype, [&](auto t) -> int {
+    using T = GP_TAG_TYPE(t);
+    const hipError_t e = gpk::launch_gauss_newton_rows<T>(as<T>(d_deriv), as<T>(d_gram), gram_stride, as<T>(d_gn), n_rows,
+                                                          n_pcs, n_inputs, ctx->compute_units, ctx->stream);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "gauss-newton kernel launch: %s", hipGetErrorString(e));
+    return GP_OK;
+  });
 }
 
 int gp_mv_misfit_host(gp_ctx* ctx, const gp_model* model, const void* d_basis, const void* y, int64_t y_stride,

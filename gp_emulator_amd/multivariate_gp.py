@@ -381,6 +381,261 @@ class MultivariateEmulator(object):
             res.append(coef)
         return tuple(res) if len(res) > 1 else cost
 
+    # ---- per-row weights and the retrieval ---------------------------------------------------------
+    def _fresh_gpu_state(self, dt):
+        """``_gpu_state`` under the staleness contract of ``hessian_many``: the host arrays are digested before use
+        and the resident copy rebuilt when they were edited in place."""
+        from . import _lib
+        st = self._gpu_state(dt)
+        if not st["blocks"].unchanged():
+            self._release(st)
+            del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
+            st = self._gpu_state(dt)
+        return st
+
+    def weight_gram(self, weights, is_gpu=True, precision=np.float64):
+        """``G[m] = basis diag(weights[m]) basis^T``, ``(M, n_pcs, n_pcs)`` for weights ``(M, N_full)``: the matrix of
+        the Gauss-Newton term of row m when the weights (per-pixel uncertainties, masks) differ from row to row.  It
+        depends on the weights and the basis only, not on the state.  The numpy branch is, row by row,
+        ``(basis * weights[m]) @ basis.T`` in float64 -- row by row for the reason ``hessian_many`` gives: a row's
+        result must not depend on M.  On the GPU it is ``weight_gram_kernel`` on the device-resident basis (weights
+        up, matrices down), every ``G[m]`` symmetric bit for bit."""
+        weights = np.asarray(weights)
+        P, B = self.n_pcs, self.basis_functions.shape[1]
+        if weights.ndim != 2 or weights.shape[1] != B:
+            raise ValueError("weights must be (n_rows, %d), got %s" % (B, weights.shape))
+        M = weights.shape[0]
+        if not is_gpu:
+            b64 = np.ascontiguousarray(self.basis_functions, dtype=np.float64)
+            w64 = np.asarray(weights, dtype=np.float64)
+            return np.stack([(b64 * w64[m]) @ b64.T for m in range(M)]) if M else np.zeros((0, P, P))
+        dt = np.dtype(precision)
+        isz = dt.itemsize
+        st = self._fresh_gpu_state(dt)
+        ctx = st["ctx"]
+        out = np.empty((M, P, P), dt)
+        step = max(1, (1 << 30) // (B * isz))                  # at most 1 GiB of weights on the device
+        d_w = ctx.malloc(max(1, min(M, step) * B * isz))
+        d_g = ctx.malloc(max(1, min(M, step) * P * P * isz))
+        try:
+            for r0 in range(0, M, step):
+                n = min(M, r0 + step) - r0
+                ctx.h2d(d_w, np.ascontiguousarray(weights[r0:r0 + n], dtype=dt))
+                ctx.mv_weight_gram_device(dt, st["d_basis"], d_w, B, d_g, n, P, B)
+                out[r0:r0 + n] = ctx.to_host(d_g, (n, P, P), dt)
+        finally:
+            ctx.free(d_w)
+            ctx.free(d_g)
+        return out
+
+    @staticmethod
+    def _contract_numpy(grads, G):
+        """``gn[m] = grads[:, m].T @ G[m] @ grads[:, m]`` for ``G`` (M, P, P), upper triangle mirrored."""
+        gn = np.triu(np.einsum("pmd,mpq,qme->mde", grads, G, grads))
+        return gn + np.swapaxes(np.triu(gn, 1), 1, 2)
+
+    def gauss_newton_many(self, Y, weights=None, is_gpu=True, precision=np.float64):
+        """The Gauss-Newton term ``gn (M, N_params, N_params) = Jac diag(w) Jac^T`` of the observation misfit for M
+        input rows, exactly symmetric; ``weights`` None (all 1), ``(N_full,)`` or ``(M, N_full)``.  For None and shared
+        weights it is ``misfit_many(..., gauss_newton=True)``'s ``gn``, bit for bit, on both branches.  For per-row
+        weights, which ``misfit_many`` does not take, ``gn[m] = dmu[:, m].T @ G[m] @ dmu[:, m]`` with ``G =
+        weight_gram(weights)``: on the GPU rows and weights up, the mean+gradient predict, the Gram kernel, the
+        strided contraction (``gp_mv_gauss_newton_rows_device``), ``gn`` down, on the device-resident emulator under
+        the staleness contract of ``hessian_many``; the numpy branch is ``einsum("pmd,mpq,qme->mde")`` on the per-PC
+        ``gp.predict`` gradients and ``weight_gram``'s numpy result, the upper triangle mirrored."""
+        Y = np.atleast_2d(Y)
+        M, D = Y.shape
+        P, B = self.n_pcs, self.basis_functions.shape[1]
+        if weights is None or np.ndim(weights) == 1:
+            return self.misfit_many(Y, np.zeros(B), weights=weights, is_gpu=is_gpu, precision=precision,
+                                    do_deriv=False, gauss_newton=True)[1]
+        weights = np.asarray(weights)
+        if weights.shape != (M, B):
+            raise ValueError("weights must be (%d,) or (%d, %d), got %s" % (B, M, B, weights.shape))
+        if not is_gpu:
+            grads = np.stack([gp.predict(Y)[2] for gp in self.emulators])      # (P, M, D)
+            return self._contract_numpy(grads, self.weight_gram(weights, is_gpu=False))
+        dt = np.dtype(precision)
+        isz = dt.itemsize
+        st = self._fresh_gpu_state(dt)
+        ctx, batch = st["ctx"], st["batch"]
+        Yc = np.ascontiguousarray(Y, dtype=dt)
+        out = np.empty((M, D, D), dt)
+        step = max(1, (1 << 30) // (max(B, P * D, D * D) * isz))      # at most 1 GiB per device array
+        n0 = min(M, step)
+        held = [ctx.malloc(max(1, n0 * k * isz)) for k in (D, B, P, P * D, P * P, D * D)]
+        d_y, d_w, d_mu, d_der, d_g, d_gn = held
+        try:
+            for r0 in range(0, M, step):
+                n = min(M, r0 + step) - r0
+                ctx.h2d(d_y, Yc[r0:r0 + n])
+                ctx.h2d(d_w, np.ascontiguousarray(weights[r0:r0 + n], dtype=dt))
+                batch.predict_mean_grad_device(d_y, d_mu, d_der, n)
+                ctx.mv_weight_gram_device(dt, st["d_basis"], d_w, B, d_g, n, P, B)
+                ctx.mv_gauss_newton_rows_device(dt, d_der, d_g, P * P, d_gn, n, P, D)
+                out[r0:r0 + n] = ctx.to_host(d_gn, (n, D, D), dt)
+        finally:
+            for p_ in held:
+                ctx.free(p_)
+        return out
+
+    def _data_term_numpy(self, Y, obs, weights, G):
+        """cost, grad and gn of the numpy branches above from ONE pass over the per-PC emulators; ``G`` is the (P, P)
+        matrix of shared weights or ``weight_gram``'s (M, P, P)."""
+        basis = np.asarray(self.basis_functions, dtype=np.float64)
+        out = [gp.predict(Y) for gp in self.emulators]
+        mu = np.stack([o[0] for o in out])                      # (P, M)
+        grads = np.stack([o[2] for o in out])                   # (P, M, D)
+        r = mu.T @ basis - obs
+        wr = r if weights is None else weights * r
+        cost = 0.5 * np.sum(wr * r, axis=1)
+        grad = np.einsum("mp,pmd->md", wr @ basis.T, grads)
+        if G.ndim == 3:
+            return cost, grad, self._contract_numpy(grads, G)
+        gn = np.triu(np.einsum("pmd,pq,qme->mde", grads, G, grads))
+        return cost, grad, gn + np.swapaxes(np.triu(gn, 1), 1, 2)
+
+    def retrieve_many(self, Y0, obs, weights=None, prior=None, bounds=None, lam0=1e-2, max_iter=20, down=1.0 / 3.0,
+                      up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False):
+        """Levenberg-Marquardt retrieval of M state vectors at once on this emulator: minimises, row by row,
+
+            F(y) = 1/2 sum_b w_b (f_b(y) - obs_b)^2  (+ 1/2 (y - y0)^T P (y - y0) with ``prior=(y0 (D,), P (D, D))``)
+
+        from ``Y0`` (M, D), inside ``bounds=(lo (D,), hi (D,))`` when given.  ``obs`` is ``(N_full,)`` or
+        ``(M, N_full)``; ``weights`` None (all 1), ``(N_full,)`` or ``(M, N_full)`` -- per-row weights are per-pixel
+        uncertainties and masks: weight 0 marks a missing or contaminated band.  The loop, its arguments and what it
+        returns are ``perband.retrieve_bands``': an iteration is the misfit at the trial rows, the accept / reject
+        update (a trial that lowers F is taken and lambda multiplied by ``down``, any other is dropped and lambda
+        multiplied by ``up``, between ``perband.LAMBDA_MIN`` and ``LAMBDA_MAX``; a row whose accepted step gains no
+        more than ``ftol * F`` or moves no more than ``xtol`` is converged and frozen), then the damped Newton step
+        ``(A + P + lambda diag(A + P)) step = -(grad + P (y - y0))``, ``trial = clip(y + step)``.  At most ``max_iter``
+        trials per row.  ``A`` is the Gauss-Newton term ``Jac diag(w) Jac^T`` (``gauss_newton_many``) ONLY: the full
+        second-order matrix (``hessian_many(coef=)`` added to it) is not offered here.
+
+        Returns ``(Y (M, D), cost (M,), state (M,) int32, n_accepted (M,) int32, lam (M,))``: ``cost`` is the DATA term
+        at ``Y`` (the prior term is not included), ``state`` 1 for converged rows, ``n_accepted`` the trials taken.
+        ``return_cov=True`` appends ``cov (M, D, D)``, ``sigma (M, D)`` and ``cov_status (M,) int32``, the posterior
+        covariance ``(A + P)^-1`` at the returned rows exactly as ``retrieve_bands`` defines it; the five are
+        unchanged by it.
+
+        On the GPU ``Y0``, ``obs`` and ``weights`` go up once to the device-resident emulator; with per-row weights one
+        launch of the Gram kernel forms every row's ``basis diag(w) basis^T`` before the loop (it does not depend on
+        the state).  Every iteration is ``predict_mean_grad_device``, ``mv_misfit_device``, the Gauss-Newton
+        contraction (``mv_gauss_newton_device`` with the host's matrix, or ``mv_gauss_newton_rows_device`` with the
+        per-row ones), ``lm_update_device`` and ``newton_step_device`` on the one stream, and nothing comes back
+        inside the loop but ``state``, every fourth iteration, to stop when every row has converged; after it,
+        ``posterior_cov_device`` on the loop's own arrays.  ``is_gpu=False`` is the explicit numpy branch, the same loop
+        from the numpy forms of ``misfit_many`` / ``gauss_newton_many`` and ``_lib.newton_step_numpy``; never a
+        fallback."""
+        from . import _lib
+        from .perband import LAMBDA_MAX, LAMBDA_MIN, _lm_update_numpy
+        Y0 = np.asarray(Y0)
+        if Y0.ndim != 2:
+            raise ValueError("Y0 must be (n_rows, n_inputs)")
+        M, D = Y0.shape
+        P, B = self.n_pcs, self.basis_functions.shape[1]
+        if D != self.emulators[0].inputs.shape[1]:
+            raise ValueError("Y0 has %d columns, the emulators have %d inputs" % (D, self.emulators[0].inputs.shape[1]))
+        _, obs, weights = self._misfit_args(Y0, obs, weights, False)
+        if prior is not None:
+            prior = (np.asarray(prior[0], dtype=np.float64).reshape(D), np.asarray(prior[1], dtype=np.float64).reshape(D, D))
+        if bounds is not None:
+            bounds = (np.asarray(bounds[0], dtype=np.float64).reshape(D), np.asarray(bounds[1], dtype=np.float64).reshape(D))
+        max_iter = int(max_iter)
+        per_row = weights is not None and weights.ndim == 2
+
+        if not is_gpu:
+            obs64 = np.asarray(obs, dtype=np.float64)
+            w64 = None if weights is None else np.asarray(weights, dtype=np.float64)
+            G = self.weight_gram(w64, is_gpu=False) if per_row else self._gauss_newton_matrix(w64)
+            X = np.array(Y0, dtype=np.float64)
+            lam = np.full(M, float(lam0))
+            state, n_acc = np.zeros(M, np.int32), np.zeros(M, np.int32)
+            cost, grad, A = (np.array(a) for a in self._data_term_numpy(X, obs64, w64, G))
+            for it in range(max_iter):
+                _, trial, status = _lib.newton_step_numpy(X, grad, A, lam, "diagonal", prior, bounds)
+                cost_t, grad_t, A_t = self._data_term_numpy(trial, obs64, w64, G)
+                n_acc += _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, np.asarray(status), state,
+                                          prior, down, up, LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
+                if it % 4 == 3 and np.all(state == 1):
+                    break
+            if return_cov:
+                return (X, cost, state, n_acc, lam) + _lib.posterior_cov_numpy(A, prior[1] if prior is not None else None)
+            return X, cost, state, n_acc, lam
+
+        dt = np.dtype(precision)
+        isz = dt.itemsize
+        st = self._fresh_gpu_state(dt)
+        ctx, batch, d_basis = st["ctx"], st["batch"], st["d_basis"]
+        held = []
+
+        def up_(a):
+            held.append(ctx.to_device(np.ascontiguousarray(a, dtype=dt)))
+            return held[-1]
+
+        def alloc(nbytes):
+            held.append(ctx.malloc(max(1, nbytes)))
+            return held[-1]
+        try:
+            d_x, d_obs = up_(Y0), up_(obs)
+            d_w = up_(weights) if weights is not None else None
+            d_lam = up_(np.full(M, float(lam0)))
+            d_x0, d_P = (up_(prior[0]), up_(prior[1])) if prior is not None else (None, None)
+            d_lo, d_hi = (up_(bounds[0]), up_(bounds[1])) if bounds is not None else (None, None)
+            d_mu, d_der = alloc(P * M * isz), alloc(P * M * D * isz)
+            d_cost, d_grad, d_A = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
+            d_cost_t, d_grad_t, d_A_t = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
+            d_trial, d_status, d_state = alloc(M * D * isz), alloc(M * 4), alloc(M * 4)
+            d_acc = alloc(max_iter * M * 4)            # one (M,) slice per iteration, summed after the loop
+            _lib.check(ctx.lib.gp_memset(ctx.h, d_state, 0, M * 4), "gp_memset")
+            os_, ws = B if obs.ndim == 2 else 0, B if per_row else 0
+            if per_row:                                # every row's matrix, once: it does not depend on the state
+                d_G = alloc(M * P * P * isz)
+                ctx.mv_weight_gram_device(dt, d_basis, d_w, B, d_G, M, P, B)
+            else:
+                d_G = up_(self._gauss_newton_matrix(weights))
+
+            def misfit(d_rows, c, g, a):
+                batch.predict_mean_grad_device(d_rows, d_mu, d_der, M)
+                ctx.mv_misfit_device(dt, d_basis, d_mu, d_der, d_obs, os_, d_w, ws, c, None, g, M, P, B, D)
+                if per_row:
+                    ctx.mv_gauss_newton_rows_device(dt, d_der, d_G, P * P, a, M, P, D)
+                else:
+                    ctx.mv_gauss_newton_device(dt, d_der, d_G, a, M, P, D)
+
+            def newton():
+                ctx.newton_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0, d_P,
+                                       d_lo, d_hi)
+            misfit(d_x, d_cost, d_grad, d_A)
+            newton()
+            done = 0
+            for it in range(max_iter):
+                misfit(d_trial, d_cost_t, d_grad_t, d_A_t)
+                ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status,
+                                     d_state, _lib.c_void_p(d_acc.value + it * M * 4), M, D, d_x0, d_P, down, up,
+                                     LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
+                newton()
+                done = it + 1
+                if it % 4 == 3:                       # (the copy synchronises the stream first)
+                    ctx.synchronize()
+                    if np.all(np.asarray(ctx.to_host(d_state, (M,), np.int32)) == 1):
+                        break
+            ctx.synchronize()
+            X, cost, lam = (np.array(ctx.to_host(p, s, dt)) for p, s in ((d_x, (M, D)), (d_cost, (M,)), (d_lam, (M,))))
+            state = np.array(ctx.to_host(d_state, (M,), np.int32))
+            n_acc = (np.array(ctx.to_host(d_acc, (done, M), np.int32)).sum(axis=0, dtype=np.int32) if done
+                     else np.zeros(M, np.int32))
+            if return_cov:
+                d_cov, d_sigma, d_cstat = alloc(M * D * D * isz), alloc(M * D * isz), alloc(M * 4)
+                ctx.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D)
+                ctx.synchronize()
+                return (X, cost, state, n_acc, lam, np.array(ctx.to_host(d_cov, (M, D, D), dt)),
+                        np.array(ctx.to_host(d_sigma, (M, D), dt)), np.array(ctx.to_host(d_cstat, (M,), np.int32)))
+            return X, cost, state, n_acc, lam
+        finally:
+            for p_ in held:
+                ctx.free(p_)
+
     # ---- second derivatives ---------------------------------------------------------------------
     def hessian(self, y, is_gpu=False, weights=None):
         """Hessian of the reconstructed output at ONE input vector ``y``: ``(N_params, N_params, N_full)`` (axes

@@ -301,6 +301,29 @@ int gp_mv_misfit_device(gp_ctx* ctx, int dtype, const void* d_basis, const void*
  * triangle is computed and mirrored, so the result is exactly symmetric. */
 int gp_mv_gauss_newton_device(gp_ctx* ctx, int dtype, const void* d_deriv, const void* d_A, void* d_gn, int64_t n_rows,
                               int n_pcs, int n_inputs);
+/* Per-row weights (per-pixel uncertainties, masks: weight 0 marks a missing band).  The matrix of the Gauss-Newton
+ * term is then one per row,
+ *   G[m][p][q] = sum_b basis[p][b] w[m][b] basis[q][b]       d_gram [n_rows][n_pcs][n_pcs]
+ * It depends on the weights and the basis only, not on the state: a retrieval forms it once before its loop.
+ * d_weights: row m at d_weights + m * weights_stride (elements; 0 = one vector for all rows, every row then gets
+ * the same bits; else >= n_bands).  Rows start on a multiple of the element size only and nothing between the rows
+ * is read.  Only the pairs p <= q are computed, on the matrix core in `dtype`, and each value is stored once to
+ * [p][q] and [q][p]: G[m] is symmetric bit for bit.  The sum over the bands runs in chunks of 128: a chunk's share
+ * is summed from zero and then added to the total.  No atomics: a row's matrix depends on its own weights only, not
+ * on the number of rows, the row's place in the call or the grid, and two calls agree bit for bit; padded pairs,
+ * bands and rows are zeros that are selected, never multiplied in, so a NaN or Inf in one row's weights stays in
+ * that row's matrix.
+ * gp_mv_gauss_newton_rows_device is gp_mv_gauss_newton_device with the matrix of row m read at d_gram + m *
+ * gram_stride (elements; >= n_pcs^2, or 0 = one matrix for all rows, which IS gp_mv_gauss_newton_device):
+ *   gn[m][d][e] = sum_pq deriv[p][m][d] G[m][p][q] deriv[q][m][e]      d_gn [n_rows][n_inputs][n_inputs]
+ * by the same chains (t[q] over p ascending, then the sum over q ascending; the upper triangle computed and
+ * mirrored): exactly symmetric, and bit for bit gp_mv_gauss_newton_device(..., A) when every row's matrix is A.
+ * Both: device pointers of `dtype`, asynchronous on the context's stream; n_rows > 0; n_pcs <= 16, n_inputs <= 64
+ * (GP_ERR_UNSUPPORTED beyond).  Every argument is checked before the device is touched. */
+int gp_mv_weight_gram_device(gp_ctx* ctx, int dtype, const void* d_basis, const void* d_weights, int64_t weights_stride,
+                             void* d_gram, int64_t n_rows, int n_pcs, int n_bands);
+int gp_mv_gauss_newton_rows_device(gp_ctx* ctx, int dtype, const void* d_deriv, const void* d_gram, int64_t gram_stride,
+                                   void* d_gn, int64_t n_rows, int n_pcs, int n_inputs);
 /* The whole data term in one call, the counterpart of gp_mv_predict_host[_checked]: `model` is the batch of the
  * n_pcs per-PC emulators, d_basis their basis on the device, y / obs / weights host rows of the model's dtype with
  * row strides in elements (y_stride >= n_inputs; obs_stride and weights_stride 0 or >= n_bands; weights may be
@@ -455,6 +478,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_HESSIAN 2
 #define GP_OP_RECONSTRUCT 3
 #define GP_OP_MISFIT 4             /* n_inputs is n_pcs and aux n_bands, as for GP_OP_RECONSTRUCT */
+#define GP_OP_MV_GRAM 5            /* gp_mv_weight_gram_device: n_inputs is n_pcs and aux n_bands */
 #define GP_PLAN_PREDICT_FEW 1      /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
@@ -465,6 +489,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_RECON_NARROW 8     /* reconstruct_kernel, 256 threads x 2 vectors */
 #define GP_PLAN_RECON_WIDE 9       /* reconstruct_kernel, 512 threads x 3 vectors */
 #define GP_PLAN_MISFIT 10          /* misfit_kernel: an item is 64 rows over all bands */
+#define GP_PLAN_MV_GRAM 11         /* weight_gram_kernel: an item is 64 rows over all bands; workgroups per CU by instance */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
