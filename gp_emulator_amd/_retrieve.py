@@ -1,0 +1,143 @@
+"""The Levenberg-Marquardt loop of ``perband.retrieve_bands`` and ``MultivariateEmulator.retrieve_many``: what belongs
+to the loop and to neither emulator type.  The callers keep their argument checks, their uploads and the data term
+(a callable); the accept / reject update, the damping, the convergence read-back, the results and the posterior
+covariance are stated here once, for the host (``lm_numpy``) and for the device (``lm_device``)."""
+import numpy as np
+
+from . import _lib
+
+LAMBDA_MIN, LAMBDA_MAX = 1e-12, 1e12     # the clamps of the loop's damping
+
+
+def _prior_term(X, prior):
+    """1/2 (x - x0)^T P (x - x0) per row, outer and inner index ascending as lm_update_kernel sums it."""
+    if prior is None:
+        return 0.0
+    x0, P = prior
+    d = X - x0
+    D = d.shape[1]
+    q = np.zeros(d.shape[0])
+    for i in range(D):
+        ri = np.zeros(d.shape[0])
+        for c in range(D):
+            ri += P[i, c] * d[:, c]
+        q += d[:, i] * ri
+    return 0.5 * q
+
+
+def _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, status, state, prior, down, up, lam_min, lam_max,
+                     ftol, xtol):
+    """``gp_lm_update_device`` in float64 numpy, in place on X, cost, grad, A, lam, state; returns accepted (M,) int32."""
+    active = state == 0
+    F, Ft = cost + _prior_term(X, prior), cost_t + _prior_term(trial, prior)
+    with np.errstate(invalid="ignore"):
+        accept = active & (status == 0) & np.isfinite(Ft) & (Ft < F)
+        conv = ((F - Ft) <= ftol * F) | (np.max(np.abs(trial - X), axis=1) <= xtol)
+    reject = active & ~accept
+    X[accept], cost[accept], grad[accept], A[accept] = trial[accept], cost_t[accept], grad_t[accept], A_t[accept]
+    lam[accept] = np.maximum(lam[accept] * down, lam_min)
+    lam[reject] = np.minimum(lam[reject] * up, lam_max)
+    state[accept & conv] = 1
+    return accept.astype(np.int32)
+
+
+def prior_and_bounds(prior, bounds, D):
+    """``prior`` as float64 ``(x0 (D,), P (D, D))`` and ``bounds`` as float64 ``(lo (D,), hi (D,))``; None stays None."""
+    if prior is not None:
+        prior = (np.asarray(prior[0], dtype=np.float64).reshape(D), np.asarray(prior[1], dtype=np.float64).reshape(D, D))
+    if bounds is not None:
+        bounds = (np.asarray(bounds[0], dtype=np.float64).reshape(D), np.asarray(bounds[1], dtype=np.float64).reshape(D))
+    return prior, bounds
+
+
+def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov):
+    """The loop on the host in float64: ``data_term(X) -> (cost, grad, A)``, ``step(x, grad, A, lam) -> (step, trial,
+    status)``.  Returns ``(X, cost, state, n_accepted, lam)`` and with ``return_cov`` ``_lib.posterior_cov_numpy``'s
+    three of the loop's ``A``."""
+    M = X0.shape[0]
+    X = np.array(X0, dtype=np.float64)
+    lam = np.full(M, float(lam0))
+    state, n_acc = np.zeros(M, np.int32), np.zeros(M, np.int32)
+    cost, grad, A = (np.array(a) for a in data_term(X))
+    for it in range(max_iter):
+        _, trial, status = step(X, grad, A, lam)
+        trial = np.asarray(trial, dtype=np.float64)
+        cost_t, grad_t, A_t = data_term(trial)
+        n_acc += _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, np.asarray(status), state, prior,
+                                  down, up, LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
+        if it % 4 == 3 and np.all(state == 1):
+            break
+    if return_cov:
+        return (X, cost, state, n_acc, lam) + _lib.posterior_cov_numpy(A, prior[1] if prior is not None else None)
+    return X, cost, state, n_acc, lam
+
+
+class Scratch(object):
+    """Device arrays of one call, freed together on exit -- also when the call raises half way: ``up(array)`` uploads
+    in the call's precision, ``alloc(nbytes)`` reserves."""
+
+    def __init__(self, ctx, dt):
+        self.ctx, self.dt, self.held = ctx, dt, []
+
+    def up(self, a):
+        self.held.append(self.ctx.to_device(np.ascontiguousarray(a, dtype=self.dt)))
+        return self.held[-1]
+
+    def alloc(self, nbytes):
+        self.held.append(self.ctx.malloc(max(1, nbytes)))
+        return self.held[-1]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        held, self.held = self.held, []
+        for p in held:
+            self.ctx.free(p)
+
+
+def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov, misfit):
+    """The loop on the device from the host rows ``X0``, in the precision and on the context of ``scratch`` (the
+    caller's ``Scratch``, which also holds whatever ``misfit`` reads).  ``misfit(d_rows, d_cost, d_grad, d_A)`` enqueues
+    the data term at ``d_rows`` on the context's stream.  Every iteration is that, ``lm_update_device`` and
+    ``newton_step_device``; nothing comes back inside the loop but ``state``, every fourth iteration, to stop when every
+    row has converged.  Returns what ``lm_numpy`` returns, in the scratch's precision."""
+    ctx, dt = scratch.ctx, scratch.dt
+    up_, alloc, isz = scratch.up, scratch.alloc, dt.itemsize
+    d_x, d_lam = up_(X0), up_(np.full(M, float(lam0)))
+    d_x0, d_P = (up_(prior[0]), up_(prior[1])) if prior is not None else (None, None)
+    d_lo, d_hi = (up_(bounds[0]), up_(bounds[1])) if bounds is not None else (None, None)
+    d_cost, d_grad, d_A = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
+    d_cost_t, d_grad_t, d_A_t = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
+    d_trial, d_status, d_state = alloc(M * D * isz), alloc(M * 4), alloc(M * 4)
+    d_acc = alloc(max_iter * M * 4)            # one (M,) slice per iteration, summed after the loop
+    _lib.check(ctx.lib.gp_memset(ctx.h, d_state, 0, M * 4), "gp_memset")
+
+    def newton():
+        ctx.newton_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0, d_P,
+                               d_lo, d_hi)
+    misfit(d_x, d_cost, d_grad, d_A)
+    newton()
+    done = 0
+    for it in range(max_iter):
+        misfit(d_trial, d_cost_t, d_grad_t, d_A_t)
+        ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status,
+                             d_state, _lib.c_void_p(d_acc.value + it * M * 4), M, D, d_x0, d_P, down, up,
+                             LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
+        newton()
+        done = it + 1
+        if it % 4 == 3:                       # (the copy synchronises the stream first)
+            ctx.synchronize()
+            if np.all(np.asarray(ctx.to_host(d_state, (M,), np.int32)) == 1):
+                break
+    ctx.synchronize()
+    X, cost, lam = (np.array(ctx.to_host(p, s, dt)) for p, s in ((d_x, (M, D)), (d_cost, (M,)), (d_lam, (M,))))
+    state = np.array(ctx.to_host(d_state, (M,), np.int32))
+    n_acc = np.array(ctx.to_host(d_acc, (done, M), np.int32)).sum(axis=0, dtype=np.int32) if done else np.zeros(M, np.int32)
+    if return_cov:
+        d_cov, d_sigma, d_cstat = alloc(M * D * D * isz), alloc(M * D * isz), alloc(M * 4)
+        ctx.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D)
+        ctx.synchronize()
+        return (X, cost, state, n_acc, lam, np.array(ctx.to_host(d_cov, (M, D, D), dt)),
+                np.array(ctx.to_host(d_sigma, (M, D), dt)), np.array(ctx.to_host(d_cstat, (M,), np.int32)))
+    return X, cost, state, n_acc, lam

@@ -35,6 +35,27 @@ def row_shards(n_rows, n_shards):
     return out
 
 
+def run_shards(devices, shards, work):
+    """``work(k, device, start, end)`` for the k-th ``(device, shard)`` pair, one thread each; empty shards are skipped.
+    Every thread is joined, then the first exception one of them recorded is raised in the caller."""
+    errors = []
+
+    def guarded(*args):
+        try:
+            work(*args)
+        except BaseException as exc:   # surfaced to the caller below
+            errors.append(exc)
+
+    threads = [threading.Thread(target=guarded, args=(k, device, s, e))
+               for k, (device, (s, e)) in enumerate(zip(devices, shards)) if e > s]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        raise errors[0]
+
+
 _device_ctx = {}
 _device_ctx_lock = threading.Lock()
 
@@ -98,10 +119,11 @@ def predict_sharded(gp, testing, devices, precision=np.float64, predict_fn=None,
         mu, var, deriv = np.empty(M), np.empty(M), np.empty((M, D))
     else:
         mu, var, deriv = out
-    shards = row_shards(M, len(devices))
-    errors = []
 
-    def hip_shard(device, s, e):
+    def work(k, device, s, e):
+        if predict_fn is not None:
+            mu[s:e], var[s:e], deriv[s:e] = predict_fn(device, testing[s:e])
+            return
         ctx, lock = _device_context(device)
         with lock:
             model = _shard_model(ctx, device, gp, precision)
@@ -110,24 +132,7 @@ def predict_sharded(gp, testing, devices, precision=np.float64, predict_fn=None,
                 rows = rows.astype(np.float64)
             model.predict(rows, out=(mu[s:e], var[s:e], deriv[s:e]))
 
-    def work(device, s, e):
-        try:
-            if e > s:
-                if predict_fn is None:
-                    hip_shard(device, s, e)
-                else:
-                    mu[s:e], var[s:e], deriv[s:e] = predict_fn(device, testing[s:e])
-        except BaseException as exc:   # surfaced to the caller below
-            errors.append((device, exc))
-
-    threads = [threading.Thread(target=work, args=(dev, s, e))
-               for dev, (s, e) in zip(devices, shards)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    if errors:
-        raise errors[0][1]
+    run_shards(devices, row_shards(M, len(devices)), work)
     return mu, var, deriv
 
 

@@ -184,6 +184,14 @@ class MultivariateEmulator(object):
         st["ctx"].free(st["d_basis"])
         st["batch"].close()
 
+    def _rebuilt_gpu_state(self, dt, st):
+        """The host arrays were edited in place since the resident copy ``st`` was made: discard it and build the
+        state again from what they hold now."""
+        from . import _lib
+        self._release(st)
+        del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
+        return self._gpu_state(dt)
+
     def release_gpu(self):
         """Free the device-resident copy (packed emulators, basis); the next
         ``is_gpu=True`` call rebuilds it."""
@@ -239,11 +247,7 @@ class MultivariateEmulator(object):
                                                     _lib._ptr(fwd[r0:r1]), _lib._ptr(jac[r0:r1]) if do_deriv else None,
                                                     blocks.ptrs, blocks.lens, blocks.n, blocks.expected)
             if rc == _lib.GP_STALE:
-                # the host arrays were edited in place since the resident copy was made: rebuild it from what
-                # they hold now and run the same rows again (nothing of the stale call is kept)
-                self._release(st)
-                del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
-                st = self._gpu_state(dt)
+                st = self._rebuilt_gpu_state(dt, st)      # and run the same rows again: nothing of the stale call is kept
                 ctx = st["ctx"]
                 continue
             _lib.check(rc, "gp_mv_predict_host_checked")
@@ -308,22 +312,8 @@ class MultivariateEmulator(object):
         P, B = self.n_pcs, self.basis_functions.shape[1]
         A = self._gauss_newton_matrix(weights) if gauss_newton else None
         if not is_gpu:
-            basis = np.asarray(self.basis_functions, dtype=np.float64)
-            out = [gp.predict(Y) for gp in self.emulators]
-            mu = np.stack([o[0] for o in out])                      # (P, M)
-            grads = np.stack([o[2] for o in out])                   # (P, M, D)
-            r = mu.T @ basis - obs
-            wr = r if weights is None else weights * r
-            cost = 0.5 * np.sum(wr * r, axis=1)
-            coef = wr @ basis.T                                      # (M, P)
-            res = [cost]
-            if do_deriv:
-                res.append(np.einsum("mp,pmd->md", coef, grads))
-            if gauss_newton:
-                gn = np.triu(np.einsum("pmd,pq,qme->mde", grads, A, grads))
-                res.append(gn + np.swapaxes(np.triu(gn, 1), 1, 2))   # upper triangle mirrored: exactly symmetric
-            if return_coef:
-                res.append(coef)
+            cost, coef, _, grad, gn = self._data_term_numpy(Y, obs, weights, do_deriv, A)
+            res = [cost] + [a for a, asked in ((grad, do_deriv), (gn, gauss_newton), (coef, return_coef)) if asked]
             return tuple(res) if len(res) > 1 else cost
         from . import _lib
         dt = np.dtype(precision)
@@ -358,11 +348,7 @@ class MultivariateEmulator(object):
                 None if A_c is None else _lib._ptr(A_c), n, B, _lib._ptr(buf),
                 blocks.ptrs, blocks.lens, blocks.n, blocks.expected)
             if rc == _lib.GP_STALE:
-                # the host arrays were edited in place since the resident copy was made: rebuild it and run the
-                # same rows again (the staleness contract of predict_many)
-                self._release(st)
-                del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
-                st = self._gpu_state(dt)
+                st = self._rebuilt_gpu_state(dt, st)      # and run the same rows again (as predict_many)
                 ctx = st["ctx"]
                 continue
             _lib.check(rc, "gp_mv_misfit_host_checked")
@@ -385,13 +371,8 @@ class MultivariateEmulator(object):
     def _fresh_gpu_state(self, dt):
         """``_gpu_state`` under the staleness contract of ``hessian_many``: the host arrays are digested before use
         and the resident copy rebuilt when they were edited in place."""
-        from . import _lib
         st = self._gpu_state(dt)
-        if not st["blocks"].unchanged():
-            self._release(st)
-            del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
-            st = self._gpu_state(dt)
-        return st
+        return st if st["blocks"].unchanged() else self._rebuilt_gpu_state(dt, st)
 
     def weight_gram(self, weights, is_gpu=True, precision=np.float64):
         """``G[m] = basis diag(weights[m]) basis^T``, ``(M, n_pcs, n_pcs)`` for weights ``(M, N_full)``: the matrix of
@@ -430,8 +411,9 @@ class MultivariateEmulator(object):
 
     @staticmethod
     def _contract_numpy(grads, G):
-        """``gn[m] = grads[:, m].T @ G[m] @ grads[:, m]`` for ``G`` (M, P, P), upper triangle mirrored."""
-        gn = np.triu(np.einsum("pmd,mpq,qme->mde", grads, G, grads))
+        """``gn[m] = grads[:, m].T @ G[m] @ grads[:, m]`` for ``G`` (M, P, P), or (P, P) shared by the rows; the upper
+        triangle mirrored: exactly symmetric."""
+        gn = np.triu(np.einsum("pmd,mpq,qme->mde" if G.ndim == 3 else "pmd,pq,qme->mde", grads, G, grads))
         return gn + np.swapaxes(np.triu(gn, 1), 1, 2)
 
     def gauss_newton_many(self, Y, weights=None, is_gpu=True, precision=np.float64):
@@ -479,9 +461,10 @@ class MultivariateEmulator(object):
                 ctx.free(p_)
         return out
 
-    def _data_term_numpy(self, Y, obs, weights, G):
-        """cost, grad and gn of the numpy branches above from ONE pass over the per-PC emulators; ``G`` is the (P, P)
-        matrix of shared weights or ``weight_gram``'s (M, P, P)."""
+    def _data_term_numpy(self, Y, obs, weights, do_deriv=True, G=None):
+        """The numpy branches' data term from ONE pass over the per-PC emulators' ``gp.predict``: ``cost (M,)``, ``coef
+        (M, P)``, the per-PC gradients ``grads (P, M, D)``, then ``grad (M, D)`` with ``do_deriv`` and ``gn (M, D, D)``
+        with ``G`` -- the (P, P) matrix of shared weights or ``weight_gram``'s (M, P, P) -- else None."""
         basis = np.asarray(self.basis_functions, dtype=np.float64)
         out = [gp.predict(Y) for gp in self.emulators]
         mu = np.stack([o[0] for o in out])                      # (P, M)
@@ -489,11 +472,9 @@ class MultivariateEmulator(object):
         r = mu.T @ basis - obs
         wr = r if weights is None else weights * r
         cost = 0.5 * np.sum(wr * r, axis=1)
-        grad = np.einsum("mp,pmd->md", wr @ basis.T, grads)
-        if G.ndim == 3:
-            return cost, grad, self._contract_numpy(grads, G)
-        gn = np.triu(np.einsum("pmd,pq,qme->mde", grads, G, grads))
-        return cost, grad, gn + np.swapaxes(np.triu(gn, 1), 1, 2)
+        coef = wr @ basis.T                                      # (M, P)
+        grad = np.einsum("mp,pmd->md", coef, grads) if do_deriv else None
+        return cost, coef, grads, grad, None if G is None else self._contract_numpy(grads, G)
 
     def retrieve_many(self, Y0, obs, weights=None, prior=None, bounds=None, lam0=1e-2, max_iter=20, down=1.0 / 3.0,
                       up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False):
@@ -527,8 +508,7 @@ class MultivariateEmulator(object):
         ``posterior_cov_device`` on the loop's own arrays.  ``is_gpu=False`` is the explicit numpy branch, the same loop
         from the numpy forms of ``misfit_many`` / ``gauss_newton_many`` and ``_lib.newton_step_numpy``; never a
         fallback."""
-        from . import _lib
-        from .perband import LAMBDA_MAX, LAMBDA_MIN, _lm_update_numpy
+        from . import _lib, _retrieve
         Y0 = np.asarray(Y0)
         if Y0.ndim != 2:
             raise ValueError("Y0 must be (n_rows, n_inputs)")
@@ -537,10 +517,7 @@ class MultivariateEmulator(object):
         if D != self.emulators[0].inputs.shape[1]:
             raise ValueError("Y0 has %d columns, the emulators have %d inputs" % (D, self.emulators[0].inputs.shape[1]))
         _, obs, weights = self._misfit_args(Y0, obs, weights, False)
-        if prior is not None:
-            prior = (np.asarray(prior[0], dtype=np.float64).reshape(D), np.asarray(prior[1], dtype=np.float64).reshape(D, D))
-        if bounds is not None:
-            bounds = (np.asarray(bounds[0], dtype=np.float64).reshape(D), np.asarray(bounds[1], dtype=np.float64).reshape(D))
+        prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D)
         max_iter = int(max_iter)
         per_row = weights is not None and weights.ndim == 2
 
@@ -548,52 +525,29 @@ class MultivariateEmulator(object):
             obs64 = np.asarray(obs, dtype=np.float64)
             w64 = None if weights is None else np.asarray(weights, dtype=np.float64)
             G = self.weight_gram(w64, is_gpu=False) if per_row else self._gauss_newton_matrix(w64)
-            X = np.array(Y0, dtype=np.float64)
-            lam = np.full(M, float(lam0))
-            state, n_acc = np.zeros(M, np.int32), np.zeros(M, np.int32)
-            cost, grad, A = (np.array(a) for a in self._data_term_numpy(X, obs64, w64, G))
-            for it in range(max_iter):
-                _, trial, status = _lib.newton_step_numpy(X, grad, A, lam, "diagonal", prior, bounds)
-                cost_t, grad_t, A_t = self._data_term_numpy(trial, obs64, w64, G)
-                n_acc += _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, np.asarray(status), state,
-                                          prior, down, up, LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
-                if it % 4 == 3 and np.all(state == 1):
-                    break
-            if return_cov:
-                return (X, cost, state, n_acc, lam) + _lib.posterior_cov_numpy(A, prior[1] if prior is not None else None)
-            return X, cost, state, n_acc, lam
+
+            def data_term(X):
+                cost, _, _, grad, gn = self._data_term_numpy(X, obs64, w64, True, G)
+                return cost, grad, gn
+
+            def step(x, g, A, lam):
+                return _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds)
+            return _retrieve.lm_numpy(data_term, step, Y0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov)
 
         dt = np.dtype(precision)
         isz = dt.itemsize
         st = self._fresh_gpu_state(dt)
         ctx, batch, d_basis = st["ctx"], st["batch"], st["d_basis"]
-        held = []
-
-        def up_(a):
-            held.append(ctx.to_device(np.ascontiguousarray(a, dtype=dt)))
-            return held[-1]
-
-        def alloc(nbytes):
-            held.append(ctx.malloc(max(1, nbytes)))
-            return held[-1]
-        try:
-            d_x, d_obs = up_(Y0), up_(obs)
-            d_w = up_(weights) if weights is not None else None
-            d_lam = up_(np.full(M, float(lam0)))
-            d_x0, d_P = (up_(prior[0]), up_(prior[1])) if prior is not None else (None, None)
-            d_lo, d_hi = (up_(bounds[0]), up_(bounds[1])) if bounds is not None else (None, None)
-            d_mu, d_der = alloc(P * M * isz), alloc(P * M * D * isz)
-            d_cost, d_grad, d_A = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
-            d_cost_t, d_grad_t, d_A_t = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
-            d_trial, d_status, d_state = alloc(M * D * isz), alloc(M * 4), alloc(M * 4)
-            d_acc = alloc(max_iter * M * 4)            # one (M,) slice per iteration, summed after the loop
-            _lib.check(ctx.lib.gp_memset(ctx.h, d_state, 0, M * 4), "gp_memset")
+        with _retrieve.Scratch(ctx, dt) as scratch:
+            d_obs = scratch.up(obs)
+            d_w = scratch.up(weights) if weights is not None else None
+            d_mu, d_der = scratch.alloc(P * M * isz), scratch.alloc(P * M * D * isz)
             os_, ws = B if obs.ndim == 2 else 0, B if per_row else 0
             if per_row:                                # every row's matrix, once: it does not depend on the state
-                d_G = alloc(M * P * P * isz)
+                d_G = scratch.alloc(M * P * P * isz)
                 ctx.mv_weight_gram_device(dt, d_basis, d_w, B, d_G, M, P, B)
             else:
-                d_G = up_(self._gauss_newton_matrix(weights))
+                d_G = scratch.up(self._gauss_newton_matrix(weights))
 
             def misfit(d_rows, c, g, a):
                 batch.predict_mean_grad_device(d_rows, d_mu, d_der, M)
@@ -602,39 +556,8 @@ class MultivariateEmulator(object):
                     ctx.mv_gauss_newton_rows_device(dt, d_der, d_G, P * P, a, M, P, D)
                 else:
                     ctx.mv_gauss_newton_device(dt, d_der, d_G, a, M, P, D)
-
-            def newton():
-                ctx.newton_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0, d_P,
-                                       d_lo, d_hi)
-            misfit(d_x, d_cost, d_grad, d_A)
-            newton()
-            done = 0
-            for it in range(max_iter):
-                misfit(d_trial, d_cost_t, d_grad_t, d_A_t)
-                ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status,
-                                     d_state, _lib.c_void_p(d_acc.value + it * M * 4), M, D, d_x0, d_P, down, up,
-                                     LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
-                newton()
-                done = it + 1
-                if it % 4 == 3:                       # (the copy synchronises the stream first)
-                    ctx.synchronize()
-                    if np.all(np.asarray(ctx.to_host(d_state, (M,), np.int32)) == 1):
-                        break
-            ctx.synchronize()
-            X, cost, lam = (np.array(ctx.to_host(p, s, dt)) for p, s in ((d_x, (M, D)), (d_cost, (M,)), (d_lam, (M,))))
-            state = np.array(ctx.to_host(d_state, (M,), np.int32))
-            n_acc = (np.array(ctx.to_host(d_acc, (done, M), np.int32)).sum(axis=0, dtype=np.int32) if done
-                     else np.zeros(M, np.int32))
-            if return_cov:
-                d_cov, d_sigma, d_cstat = alloc(M * D * D * isz), alloc(M * D * isz), alloc(M * 4)
-                ctx.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D)
-                ctx.synchronize()
-                return (X, cost, state, n_acc, lam, np.array(ctx.to_host(d_cov, (M, D, D), dt)),
-                        np.array(ctx.to_host(d_sigma, (M, D), dt)), np.array(ctx.to_host(d_cstat, (M,), np.int32)))
-            return X, cost, state, n_acc, lam
-        finally:
-            for p_ in held:
-                ctx.free(p_)
+            return _retrieve.lm_device(scratch, M, D, Y0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
+                                       misfit)
 
     # ---- second derivatives ---------------------------------------------------------------------
     def hessian(self, y, is_gpu=False, weights=None):
@@ -687,13 +610,7 @@ class MultivariateEmulator(object):
             return np.einsum("pmde,pm->mde", hp, coef)
         from . import _lib
         dt = np.dtype(precision)
-        st = self._gpu_state(dt)
-        if not st["blocks"].unchanged():
-            # the host arrays were edited in place since the resident copy was made: rebuild it from what they
-            # hold now (the staleness contract of predict_many)
-            self._release(st)
-            del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
-            st = self._gpu_state(dt)
+        st = self._fresh_gpu_state(dt)
         ctx, batch = st["ctx"], st["batch"]
         Yc = np.ascontiguousarray(Y, dtype=dt)
         if coef is not None:

@@ -8,13 +8,11 @@ of the fused kernel (BASELINE config 3: 2101 bands x N_train=250 x D=11, shared 
 """
 import numpy as np
 
-from . import _lib
+from . import _lib, _retrieve
+from ._retrieve import LAMBDA_MAX, LAMBDA_MIN, _lm_update_numpy, _prior_term     # noqa: F401  (their names here)
 
 
-def make_batch(gps, precision=np.float64, device=None, do_unc=True):
-    """Pack a list of GaussianProcess objects sharing ``inputs`` into one BatchModel.  ``do_unc=False``:
-    no invQ is stacked or uploaded (2101 bands x 250^2 x 8 B = 1.05 GB); the batch then serves
-    ``predict_mean_grad`` only."""
+def _check_shared_inputs(gps):
     if not gps:
         raise ValueError("need at least one GaussianProcess")
     inputs = np.asarray(gps[0].inputs)
@@ -22,10 +20,22 @@ def make_batch(gps, precision=np.float64, device=None, do_unc=True):
         other = np.asarray(gp.inputs)
         if other.shape != inputs.shape or not np.array_equal(other, inputs):
             raise ValueError("per-band emulators must share the same training inputs")
-    expX = np.stack([np.exp(gp.theta) for gp in gps])
-    invQt = np.stack([np.asarray(gp.invQt) for gp in gps])
-    invQ = np.stack([np.asarray(gp.invQ) for gp in gps]) if do_unc else None
-    return _lib.BatchModel(_lib.default_context(device), expX, inputs, invQt, invQ, precision)
+    return inputs
+
+
+def _batch_model(ctx, gps, inputs, precision, do_unc):
+    """The BatchModel of a block of emulators on ``inputs``; ``do_unc=False`` stacks and uploads no invQ."""
+    return _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in gps]), inputs,
+                           np.stack([np.asarray(gp.invQt) for gp in gps]),
+                           np.stack([np.asarray(gp.invQ) for gp in gps]) if do_unc else None, precision)
+
+
+def make_batch(gps, precision=np.float64, device=None, do_unc=True):
+    """Pack a list of GaussianProcess objects sharing ``inputs`` into one BatchModel.  ``do_unc=False``:
+    no invQ is stacked or uploaded (2101 bands x 250^2 x 8 B = 1.05 GB); the batch then serves
+    ``predict_mean_grad`` only."""
+    inputs = _check_shared_inputs(gps)
+    return _batch_model(_lib.default_context(device), gps, inputs, precision, do_unc)
 
 
 def predict_bands(gps, testing, precision=np.float64, device=None, devices=None, predict_fn=None, do_unc=True):
@@ -49,7 +59,6 @@ def predict_bands(gps, testing, precision=np.float64, device=None, devices=None,
             return batch.predict(testing) if do_unc else batch.predict_mean_grad(testing)
         finally:
             batch.close()
-    import threading
     from . import multi_gpu
     if not gps:
         raise ValueError("need at least one GaussianProcess")
@@ -58,57 +67,28 @@ def predict_bands(gps, testing, precision=np.float64, device=None, devices=None,
     mu, deriv = np.empty((E, M), dt), np.empty((E, M, D), dt)
     var = np.empty((E, M), dt) if do_unc else None
     blocks = multi_gpu.row_shards(E, len(devices))       # contiguous blocks of emulators
-    errors = []
+    inputs = _check_shared_inputs(gps)
 
-    def work(dev, e0, e1):
-        try:
-            if e1 <= e0:
-                return
-            if predict_fn is not None:
+    def work(k, dev, e0, e1):
+        if predict_fn is not None:
+            if do_unc:
+                mu[e0:e1], var[e0:e1], deriv[e0:e1] = predict_fn(dev, gps[e0:e1], testing)
+            else:
+                mu[e0:e1], deriv[e0:e1] = predict_fn(dev, gps[e0:e1], testing)
+            return
+        ctx, lock = multi_gpu._device_context(dev)
+        with lock:
+            batch = _batch_model(ctx, gps[e0:e1], inputs, precision, do_unc)
+            try:
                 if do_unc:
-                    mu[e0:e1], var[e0:e1], deriv[e0:e1] = predict_fn(dev, gps[e0:e1], testing)
+                    batch.predict(testing, out=(mu[e0:e1], var[e0:e1], deriv[e0:e1]))
                 else:
-                    mu[e0:e1], deriv[e0:e1] = predict_fn(dev, gps[e0:e1], testing)
-                return
-            ctx, lock = multi_gpu._device_context(dev)
-            with lock:
-                part = gps[e0:e1]
-                batch = _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in part]), np.asarray(part[0].inputs),
-                                        np.stack([np.asarray(gp.invQt) for gp in part]),
-                                        np.stack([np.asarray(gp.invQ) for gp in part]) if do_unc else None, precision)
-                try:
-                    if do_unc:
-                        batch.predict(testing, out=(mu[e0:e1], var[e0:e1], deriv[e0:e1]))
-                    else:
-                        batch.predict_mean_grad(testing, out=(mu[e0:e1], deriv[e0:e1]))
-                finally:
-                    batch.close()
-        except BaseException as exc:          # surfaced to the caller below
-            errors.append(exc)
+                    batch.predict_mean_grad(testing, out=(mu[e0:e1], deriv[e0:e1]))
+            finally:
+                batch.close()
 
-    inputs = np.asarray(gps[0].inputs)
-    for gp in gps[1:]:
-        if np.asarray(gp.inputs).shape != inputs.shape or not np.array_equal(gp.inputs, inputs):
-            raise ValueError("per-band emulators must share the same training inputs")
-    threads = [threading.Thread(target=work, args=(dev, e0, e1)) for dev, (e0, e1) in zip(devices, blocks)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    if errors:
-        raise errors[0]
+    multi_gpu.run_shards(devices, blocks, work)
     return (mu, var, deriv) if do_unc else (mu, deriv)
-
-
-def _check_shared_inputs(gps):
-    if not gps:
-        raise ValueError("need at least one GaussianProcess")
-    inputs = np.asarray(gps[0].inputs)
-    for gp in gps[1:]:
-        other = np.asarray(gp.inputs)
-        if other.shape != inputs.shape or not np.array_equal(other, inputs):
-            raise ValueError("per-band emulators must share the same training inputs")
-    return inputs
 
 
 def hessian_bands(gps, testing, precision=np.float64, weights=None, device=None, devices=None, hessian_fn=None):
@@ -142,7 +122,6 @@ def hessian_bands(gps, testing, precision=np.float64, weights=None, device=None,
             return batch.hessian(testing) if weights is None else batch.hessian_weighted(testing, weights)
         finally:
             batch.close()
-    import threading
     from . import multi_gpu
     if len(devices) < 1:
         raise ValueError("devices must name at least one device")
@@ -150,41 +129,27 @@ def hessian_bands(gps, testing, precision=np.float64, weights=None, device=None,
     blocks = multi_gpu.row_shards(E, len(devices))       # contiguous blocks of emulators
     out = np.empty((E, M, D, D), dt) if weights is None else None
     partial = [None] * len(devices)
-    errors = []
 
     def work(k, dev, e0, e1):
-        try:
-            if e1 <= e0:
-                return
-            part = gps[e0:e1]
-            if hessian_fn is not None:
+        part = gps[e0:e1]
+        if hessian_fn is not None:
+            if weights is None:
+                out[e0:e1] = hessian_fn(dev, part, testing)
+            else:
+                partial[k] = np.asarray(hessian_fn(dev, part, testing, weights[e0:e1]))
+            return
+        ctx, lock = multi_gpu._device_context(dev)
+        with lock:
+            batch = _batch_model(ctx, part, inputs, precision, False)
+            try:
                 if weights is None:
-                    out[e0:e1] = hessian_fn(dev, part, testing)
+                    batch.hessian(testing, out=out[e0:e1])
                 else:
-                    partial[k] = np.asarray(hessian_fn(dev, part, testing, weights[e0:e1]))
-                return
-            ctx, lock = multi_gpu._device_context(dev)
-            with lock:
-                batch = _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in part]), inputs,
-                                        np.stack([np.asarray(gp.invQt) for gp in part]), None, precision)
-                try:
-                    if weights is None:
-                        batch.hessian(testing, out=out[e0:e1])
-                    else:
-                        partial[k] = np.array(batch.hessian_weighted(testing, weights[e0:e1]))   # (own memory, not the pool's)
-                finally:
-                    batch.close()
-        except BaseException as exc:          # surfaced to the caller below
-            errors.append(exc)
+                    partial[k] = np.array(batch.hessian_weighted(testing, weights[e0:e1]))   # (own memory, not the pool's)
+            finally:
+                batch.close()
 
-    threads = [threading.Thread(target=work, args=(k, dev, e0, e1))
-               for k, (dev, (e0, e1)) in enumerate(zip(devices, blocks))]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    if errors:
-        raise errors[0]
+    multi_gpu.run_shards(devices, blocks, work)
     if weights is None:
         return out
     total = np.zeros((M, D, D), dt)
@@ -267,8 +232,7 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
         return a[e0:e1, 0] if a.shape[1] == 1 and M != 1 else a[e0:e1]
 
     def on_device(ctx, part, o, w):
-        batch = _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in part]), inputs,
-                                np.stack([np.asarray(gp.invQt) for gp in part]), None, precision)
+        batch = _batch_model(ctx, part, inputs, precision, False)
         try:
             return batch.misfit(X, o, w, second_order, return_residual)
         finally:
@@ -281,7 +245,6 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
         if not is_gpu:
             return _misfit_numpy(gps, np.asarray(X, dtype=np.float64), obs, weights, second_order, return_residual)
         return on_device(_lib.default_context(device), gps, o, w)
-    import threading
     from . import multi_gpu
     if len(devices) < 1:
         raise ValueError("devices must name at least one device")
@@ -289,30 +252,17 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
         raise ValueError("devices= shards the GPU path; the numpy branch runs in the calling thread")
     blocks = multi_gpu.row_shards(E, len(devices))       # contiguous blocks of emulators
     partial = [None] * len(devices)
-    errors = []
 
     def work(k, dev, e0, e1):
-        try:
-            if e1 <= e0:
-                return
-            o, w = block(obs, e0, e1), block(weights, e0, e1)
-            if misfit_fn is not None:
-                partial[k] = tuple(misfit_fn(dev, gps[e0:e1], X, o, w, second_order, return_residual))
-                return
-            ctx, lock = multi_gpu._device_context(dev)
-            with lock:
-                partial[k] = on_device(ctx, gps[e0:e1], o, w)
-        except BaseException as exc:          # surfaced to the caller below
-            errors.append(exc)
+        o, w = block(obs, e0, e1), block(weights, e0, e1)
+        if misfit_fn is not None:
+            partial[k] = tuple(misfit_fn(dev, gps[e0:e1], X, o, w, second_order, return_residual))
+            return
+        ctx, lock = multi_gpu._device_context(dev)
+        with lock:
+            partial[k] = on_device(ctx, gps[e0:e1], o, w)
 
-    threads = [threading.Thread(target=work, args=(k, dev, e0, e1))
-               for k, (dev, (e0, e1)) in enumerate(zip(devices, blocks))]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    if errors:
-        raise errors[0]
+    multi_gpu.run_shards(devices, blocks, work)
     parts = [p for p in partial if p is not None]          # device order
     n_sum = 3 if second_order else 2
     total = [np.array(a) for a in parts[0][:n_sum]]
@@ -322,41 +272,6 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
     if return_residual:
         total.append(np.concatenate([p[n_sum] for p in parts], axis=0))
     return tuple(total)
-
-
-def _prior_term(X, prior):
-    """1/2 (x - x0)^T P (x - x0) per row, outer and inner index ascending as lm_update_kernel sums it."""
-    if prior is None:
-        return 0.0
-    x0, P = prior
-    d = X - x0
-    D = d.shape[1]
-    q = np.zeros(d.shape[0])
-    for i in range(D):
-        ri = np.zeros(d.shape[0])
-        for c in range(D):
-            ri += P[i, c] * d[:, c]
-        q += d[:, i] * ri
-    return 0.5 * q
-
-
-def _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, status, state, prior, down, up, lam_min, lam_max,
-                     ftol, xtol):
-    """``gp_lm_update_device`` in float64 numpy, in place on X, cost, grad, A, lam, state; returns accepted (M,) int32."""
-    active = state == 0
-    F, Ft = cost + _prior_term(X, prior), cost_t + _prior_term(trial, prior)
-    with np.errstate(invalid="ignore"):
-        accept = active & (status == 0) & np.isfinite(Ft) & (Ft < F)
-        conv = ((F - Ft) <= ftol * F) | (np.max(np.abs(trial - X), axis=1) <= xtol)
-    reject = active & ~accept
-    X[accept], cost[accept], grad[accept], A[accept] = trial[accept], cost_t[accept], grad_t[accept], A_t[accept]
-    lam[accept] = np.maximum(lam[accept] * down, lam_min)
-    lam[reject] = np.minimum(lam[reject] * up, lam_max)
-    state[accept & conv] = 1
-    return accept.astype(np.int32)
-
-
-LAMBDA_MIN, LAMBDA_MAX = 1e-12, 1e12     # the clamps of retrieve_bands' damping
 
 
 def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prior=None, bounds=None, lam0=1e-2,
@@ -406,96 +321,32 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     obs = _em_broadcast(obs, E, M, "obs")
     if weights is not None:
         weights = _em_broadcast(weights, E, M, "weights")
-    if prior is not None:
-        prior = (np.asarray(prior[0], dtype=np.float64).reshape(D), np.asarray(prior[1], dtype=np.float64).reshape(D, D))
-    if bounds is not None:
-        bounds = (np.asarray(bounds[0], dtype=np.float64).reshape(D), np.asarray(bounds[1], dtype=np.float64).reshape(D))
+    prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D)
     max_iter = int(max_iter)
 
     if step_fn is not None or not is_gpu:
         step = step_fn if step_fn is not None else (
             lambda x, g, A, lam: _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds))
-        X = np.array(X0, dtype=np.float64)
-        lam = np.full(M, float(lam0))
-        state, n_acc = np.zeros(M, np.int32), np.zeros(M, np.int32)
-        cost, grad, A = (np.array(a) for a in _misfit_numpy(gps, X, obs, weights, second_order, False))
-        for it in range(max_iter):
-            _, trial, status = step(X, grad, A, lam)
-            trial = np.asarray(trial, dtype=np.float64)
-            cost_t, grad_t, A_t = _misfit_numpy(gps, trial, obs, weights, second_order, False)
-            n_acc += _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, np.asarray(status), state, prior,
-                                      down, up, LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
-            if it % 4 == 3 and np.all(state == 1):
-                break
-        if return_cov:
-            return (X, cost, state, n_acc, lam) + _lib.posterior_cov_numpy(A, prior[1] if prior is not None else None)
-        return X, cost, state, n_acc, lam
+        return _retrieve.lm_numpy(lambda X: _misfit_numpy(gps, X, obs, weights, second_order, False), step, X0, lam0,
+                                  max_iter, down, up, ftol, xtol, prior, return_cov)
 
     ctx = _lib.default_context(device)
-    dt = np.dtype(precision)
-    isz = dt.itemsize
-    batch = _lib.BatchModel(ctx, np.stack([np.exp(gp.theta) for gp in gps]), inputs,
-                            np.stack([np.asarray(gp.invQt) for gp in gps]), None, precision)
-    held = []
-
-    def up_(a):
-        held.append(ctx.to_device(np.ascontiguousarray(a, dtype=dt)))
-        return held[-1]
-
-    def alloc(nbytes):
-        held.append(ctx.malloc(max(1, nbytes)))
-        return held[-1]
+    batch = _batch_model(ctx, gps, inputs, precision, False)
 
     def strides(a):
         return (1, 0) if a.shape[1] == 1 and M != 1 else (M, 1)
     try:
-        d_x, d_obs = up_(X0), up_(obs)
-        d_w = up_(weights) if weights is not None else None
-        d_lam = up_(np.full(M, float(lam0)))
-        d_x0, d_P = (up_(prior[0]), up_(prior[1])) if prior is not None else (None, None)
-        d_lo, d_hi = (up_(bounds[0]), up_(bounds[1])) if bounds is not None else (None, None)
-        d_cost, d_grad, d_A = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
-        d_cost_t, d_grad_t, d_A_t = alloc(M * isz), alloc(M * D * isz), alloc(M * D * D * isz)
-        d_trial, d_status, d_state = alloc(M * D * isz), alloc(M * 4), alloc(M * 4)
-        d_acc = alloc(max_iter * M * 4)            # one (M,) slice per iteration, summed after the loop
-        _lib.check(ctx.lib.gp_memset(ctx.h, d_state, 0, M * 4), "gp_memset")
-        os_, ws = strides(obs), strides(weights) if weights is not None else (0, 0)
+        with _retrieve.Scratch(ctx, np.dtype(precision)) as scratch:
+            d_obs = scratch.up(obs)
+            d_w = scratch.up(weights) if weights is not None else None
+            os_, ws = strides(obs), strides(weights) if weights is not None else (0, 0)
 
-        def misfit(d_rows, c, g, a):
-            batch.misfit_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a if second_order == "gauss_newton" else None,
-                                d_hess=a if second_order == "full" else None)
-
-        def newton():
-            ctx.newton_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0, d_P,
-                                   d_lo, d_hi)
-        misfit(d_x, d_cost, d_grad, d_A)
-        newton()
-        done = 0
-        for it in range(max_iter):
-            misfit(d_trial, d_cost_t, d_grad_t, d_A_t)
-            ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status,
-                                 d_state, _lib.c_void_p(d_acc.value + it * M * 4), M, D, d_x0, d_P, down, up,
-                                 LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
-            newton()
-            done = it + 1
-            if it % 4 == 3:                       # (the copy synchronises the stream first)
-                ctx.synchronize()
-                if np.all(np.asarray(ctx.to_host(d_state, (M,), np.int32)) == 1):
-                    break
-        ctx.synchronize()
-        X, cost, lam = (np.array(ctx.to_host(p, s, dt)) for p, s in ((d_x, (M, D)), (d_cost, (M,)), (d_lam, (M,))))
-        state = np.array(ctx.to_host(d_state, (M,), np.int32))
-        n_acc = np.array(ctx.to_host(d_acc, (done, M), np.int32)).sum(axis=0, dtype=np.int32) if done else np.zeros(M, np.int32)
-        if return_cov:
-            d_cov, d_sigma, d_cstat = alloc(M * D * D * isz), alloc(M * D * isz), alloc(M * 4)
-            ctx.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D)
-            ctx.synchronize()
-            return (X, cost, state, n_acc, lam, np.array(ctx.to_host(d_cov, (M, D, D), dt)),
-                    np.array(ctx.to_host(d_sigma, (M, D), dt)), np.array(ctx.to_host(d_cstat, (M,), np.int32)))
-        return X, cost, state, n_acc, lam
+            def misfit(d_rows, c, g, a):
+                batch.misfit_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a if second_order == "gauss_newton" else None,
+                                    d_hess=a if second_order == "full" else None)
+            return _retrieve.lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
+                                       misfit)
     finally:
-        for p in held:
-            ctx.free(p)
         batch.close()
 
 
@@ -938,12 +789,7 @@ def learn_bands(gps, n_tries=5, concurrency=256, is_gpu=True, starts=None, batch
     import warnings
     from queue import Queue, Empty
     from scipy.optimize import fmin_l_bfgs_b
-    if not gps:
-        raise ValueError("need at least one GaussianProcess")
-    inputs = np.ascontiguousarray(gps[0].inputs, dtype=np.float64)
-    for gp in gps[1:]:
-        if np.asarray(gp.inputs).shape != inputs.shape or not np.array_equal(gp.inputs, inputs):
-            raise ValueError("per-band emulators must share the same training inputs")
+    inputs = np.ascontiguousarray(_check_shared_inputs(gps), dtype=np.float64)
     E, (N, D) = len(gps), inputs.shape
     ctx = None
     if batch_fn is None:
