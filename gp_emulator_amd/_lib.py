@@ -72,6 +72,10 @@ SIGNATURES = {
     "gp_newton_step_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 7 + [c_i64, c_int]),
     "gp_lm_update_device": (c_int, [c_void_p, c_int] + [c_void_p] * 14 + [ctypes.c_double] * 6 + [c_i64, c_int]),
     "gp_posterior_cov_device": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_i64, c_int]),
+    "gp_newton_step_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 7 + [c_i64, c_int, c_i64, c_i64]),
+    "gp_lm_update_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 14 + [ctypes.c_double] * 6 + [c_i64, c_int, c_i64, c_i64]),
+    "gp_posterior_cov_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_i64, c_int, c_i64]),
+    "gp_prior_propagate_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int]),
     "gp_hessian_f64": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_hessian_f32": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_reconstruct_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
@@ -291,6 +295,27 @@ class OutputPool:
         return base.view(dtype).reshape(shape)
 
 
+def prec_rows(P, M, D, dtype=np.float64):
+    """A prior precision (or a process noise) as a contiguous ``dtype`` array: one matrix ``(D, D)`` for all rows, or
+    ``(M, D, D)``, row m's own.  With one row the two say the same and the array is taken as shared, so a one-row call
+    goes the way it always went."""
+    P = np.asarray(P, dtype=dtype)
+    return np.ascontiguousarray(P if M > 1 and P.ndim == 3 and P.shape == (M, D, D) else P.reshape(D, D))
+
+
+def prior_rows(prior, M, D, dtype=np.float64):
+    """``prior = (x0, P)`` as contiguous ``dtype`` arrays: ``x0`` ``(D,)`` or per row ``(M, D)``, ``P`` ``(D, D)`` or
+    per row ``(M, D, D)``, independently of one another (with one row: shared, as ``prec_rows``)."""
+    x0 = np.asarray(prior[0], dtype=dtype)
+    x0 = np.ascontiguousarray(x0 if M > 1 and x0.ndim == 2 and x0.shape == (M, D) else x0.reshape(D))
+    return x0, prec_rows(prior[1], M, D, dtype)
+
+
+def row_strides(x0, P):
+    """The element strides of the ``_rows`` entries for what ``prior_rows`` / ``prec_rows`` returned: 0 = shared."""
+    return (x0.shape[1] if x0 is not None and x0.ndim == 2 else 0), (P.shape[1] * P.shape[2] if P is not None and P.ndim == 3 else 0)
+
+
 def newton_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=None):
     """The damped Newton step of ``gp_newton_step_device`` in float64 numpy, vectorised over the rows and written out
     in the kernel's summation order (ascending index in the factorisation, in both substitutions and in the prior's
@@ -301,7 +326,8 @@ def newton_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=No
         step = -L^-T L^-1 g',  trial = clip(x + step, lo, hi);  status = k + 1 when pivot k is not > 0 or not finite,
         then step = 0 and trial = x.
 
-    ``prior=(x0 (D,), P (D, D))``, ``bounds=(lo (D,), hi (D,))``, ``lam`` (M,) or a scalar."""
+    ``prior=(x0 (D,) or (M, D), P (D, D) or (M, D, D))`` (shared or row m's own, as ``gp_newton_step_rows_device``),
+    ``bounds=(lo (D,), hi (D,))``, ``lam`` (M,) or a scalar."""
     if damping not in _DAMPING:
         raise ValueError("damping must be 'diagonal' or 'identity'")
     x = np.array(x, dtype=np.float64, ndmin=2)
@@ -310,10 +336,10 @@ def newton_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=No
     L = np.array(A, dtype=np.float64).reshape(M, D, D)
     lam = np.broadcast_to(np.asarray(lam, dtype=np.float64), (M,))
     if prior is not None:
-        x0, P = np.asarray(prior[0], dtype=np.float64).reshape(D), np.asarray(prior[1], dtype=np.float64).reshape(D, D)
+        x0, P = prior_rows(prior, M, D)
         L = L + P
         for c in range(D):
-            g += P[:, c] * (x[:, c] - x0[c])[:, None]
+            g += P[..., :, c] * (x[:, c] - x0[..., c])[:, None]
     idx = np.arange(D)
     diag = L[:, idx, idx]
     L[:, idx, idx] = diag + lam[:, None] * (diag if damping == "diagonal" else 1.0)
@@ -348,21 +374,12 @@ def newton_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=No
     return step, trial, status
 
 
-def posterior_cov_numpy(A, prior_prec=None):
-    """The posterior covariance of ``gp_posterior_cov_device`` in float64 numpy, vectorised over the rows and written
-    out in the kernel's summation order (ascending index in the factorisation and in both substitutions):
-    ``(cov (M, D, D), sigma (M, D), status (M,) int32)``.  The explicit CPU branch of ``Context.posterior_cov`` and of
-    ``perband.retrieve_bands(return_cov=True)``, and the reference of the CPU tests; never a fallback.
-
-        A' = A (+ P), no damping,  L L^T = A' (lower triangle read),  C[:, j] = L^-T L^-1 e_j,
-        cov = C with the elements i >= j from column j's solve and the upper triangle mirrored from them,
-        sigma = sqrt(diag C);  status = k + 1 when pivot k is not > 0 or not finite, then cov and sigma are NaN."""
-    L = np.array(A, dtype=np.float64)
-    if L.ndim != 3 or L.shape[1] != L.shape[2]:
-        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+def _cholesky_inverse_numpy(L):
+    """``(W, status)`` for the matrices ``L`` (M, D, D), factored in place: ``W[:, i, j]``, i >= j, is element (i, j) of
+    the inverse by the kernels' chains (ascending index in the factorisation and in both substitutions of every unit
+    vector), NaN throughout where ``status`` (k + 1 for the first pivot that is not > 0 or not finite) is not 0.  Only
+    the lower triangle of ``L`` is read."""
     M, D = L.shape[:2]
-    if prior_prec is not None:
-        L = L + np.asarray(prior_prec, dtype=np.float64).reshape(D, D)
     status = np.zeros(M, np.int32)
     W = np.zeros((M, D, D))                                         # W[:, i, j]: y_i, then z_i, of column j
     with np.errstate(all="ignore"):
@@ -388,10 +405,57 @@ def posterior_cov_numpy(A, prior_prec=None):
                 a -= L[:, k, i][:, None] * W[:, k, :i + 1]
             W[:, i, :i + 1] = a / L[:, i, i][:, None]
         W[status != 0] = np.nan
+    return W, status
+
+
+def posterior_cov_numpy(A, prior_prec=None):
+    """The posterior covariance of ``gp_posterior_cov_device`` in float64 numpy, vectorised over the rows and written
+    out in the kernel's summation order (ascending index in the factorisation and in both substitutions):
+    ``(cov (M, D, D), sigma (M, D), status (M,) int32)``.  The explicit CPU branch of ``Context.posterior_cov`` and of
+    ``perband.retrieve_bands(return_cov=True)``, and the reference of the CPU tests; never a fallback.
+
+        A' = A (+ P), no damping,  L L^T = A' (lower triangle read),  C[:, j] = L^-T L^-1 e_j,
+        cov = C with the elements i >= j from column j's solve and the upper triangle mirrored from them,
+        sigma = sqrt(diag C);  status = k + 1 when pivot k is not > 0 or not finite, then cov and sigma are NaN.
+
+    ``prior_prec`` is ``(D, D)``, shared, or ``(M, D, D)``, row m's own (``gp_posterior_cov_rows_device``)."""
+    L = np.array(A, dtype=np.float64)
+    if L.ndim != 3 or L.shape[1] != L.shape[2]:
+        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+    M, D = L.shape[:2]
+    if prior_prec is not None:
+        L = L + prec_rows(prior_prec, M, D)
+    W, status = _cholesky_inverse_numpy(L)
+    with np.errstate(all="ignore"):
         cov = np.tril(W) + np.transpose(np.tril(W, -1), (0, 2, 1))
         idx = np.arange(D)
         sigma = np.sqrt(W[:, idx, idx])
     return cov, sigma, status
+
+
+def prior_propagate_numpy(A, prior_prec, noise):
+    """The prior propagation of ``gp_prior_propagate_device`` in float64 numpy, in the kernel's summation order:
+    ``(next_prec (M, D, D), status (M,) int32)``.  The explicit CPU branch of ``Context.prior_propagate`` and of the
+    retrievals' ``next_prior=``, and the reference of the CPU tests; never a fallback.
+
+        A' = A (+ P),  C = A'^-1 as ``posterior_cov_numpy``,  S = C + Q (lower triangles),  N = S^-1 the same way,
+        next_prec = N with the upper triangle mirrored;  status = k + 1 when pivot k of A' fails, D + k + 1 when pivot
+        k of S fails, then next_prec is NaN.
+
+    ``prior_prec`` is None, ``(D, D)`` or ``(M, D, D)``; ``noise`` (the process-noise covariance Q) ``(D, D)`` or
+    ``(M, D, D)``."""
+    L = np.array(A, dtype=np.float64)
+    if L.ndim != 3 or L.shape[1] != L.shape[2]:
+        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+    M, D = L.shape[:2]
+    if prior_prec is not None:
+        L = L + prec_rows(prior_prec, M, D)
+    C, first = _cholesky_inverse_numpy(L)
+    with np.errstate(all="ignore"):
+        S = C + prec_rows(noise, M, D)                               # (NaN where the first inversion failed)
+    W, second = _cholesky_inverse_numpy(S)
+    status = np.where(first != 0, first, np.where(second != 0, D + second, 0)).astype(np.int32)
+    return np.tril(W) + np.transpose(np.tril(W, -1), (0, 2, 1)), status
 
 
 class Context:
@@ -551,9 +615,85 @@ class Context:
         check(self.lib.gp_posterior_cov_device(self.h, code, d_A, d_prior_prec, d_cov, d_sigma, d_status, int(n_rows),
                                                int(n_inputs)), "gp_posterior_cov_device")
 
+    def newton_step_rows_device(self, dtype, d_x, d_grad, d_A, d_lambda, d_step, d_trial, d_status, n_rows, n_inputs,
+                                damping="diagonal", d_prior_mean=None, d_prior_prec=None, d_lo=None, d_hi=None,
+                                prior_mean_stride=0, prior_prec_stride=0):
+        """``newton_step_device`` with a prior per row (``gp_newton_step_rows_device``): row m's prior mean is at
+        ``d_prior_mean + m * prior_mean_stride`` elements and its precision at ``d_prior_prec + m * prior_prec_stride``;
+        0 = one for all rows, which is ``newton_step_device``.  The two strides are independent."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_newton_step_rows_device(self.h, code, d_x, d_grad, d_A, d_lambda, _DAMPING[damping], d_prior_mean,
+                                                  d_prior_prec, d_lo, d_hi, d_step, d_trial, d_status, int(n_rows),
+                                                  int(n_inputs), int(prior_mean_stride), int(prior_prec_stride)),
+              "gp_newton_step_rows_device")
+
+    def lm_update_rows_device(self, dtype, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A, d_A_trial,
+                              d_lambda, d_status, d_state, d_accepted, n_rows, n_inputs, d_prior_mean=None,
+                              d_prior_prec=None, down=1.0 / 3.0, up=4.0, lambda_min=1e-12, lambda_max=1e12, ftol=1e-10,
+                              xtol=0.0, prior_mean_stride=0, prior_prec_stride=0):
+        """``lm_update_device`` with a prior per row (``gp_lm_update_rows_device``); the strides as in
+        ``newton_step_rows_device``."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_lm_update_rows_device(self.h, code, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A,
+                                                d_A_trial, d_lambda, d_status, d_state, d_accepted, d_prior_mean,
+                                                d_prior_prec, float(down), float(up), float(lambda_min), float(lambda_max),
+                                                float(ftol), float(xtol), int(n_rows), int(n_inputs),
+                                                int(prior_mean_stride), int(prior_prec_stride)), "gp_lm_update_rows_device")
+
+    def posterior_cov_rows_device(self, dtype, d_A, d_prior_prec, d_cov, d_sigma, d_status, n_rows, n_inputs,
+                                  prior_prec_stride=0):
+        """``posterior_cov_device`` with a prior precision per row (``gp_posterior_cov_rows_device``): row m's is at
+        ``d_prior_prec + m * prior_prec_stride`` elements; 0 = one for all rows, which is ``posterior_cov_device``."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_posterior_cov_rows_device(self.h, code, d_A, d_prior_prec, d_cov, d_sigma, d_status, int(n_rows),
+                                                    int(n_inputs), int(prior_prec_stride)), "gp_posterior_cov_rows_device")
+
+    def prior_propagate_device(self, dtype, d_A, d_prior_prec, prior_prec_stride, d_noise, noise_stride, d_next_prec,
+                               d_status, n_rows, n_inputs):
+        """Asynchronous prior propagation of ``n_rows`` systems on the device (``gp_prior_propagate_device``):
+        ``next_prec = ((A + P)^-1 + Q)^-1`` row by row in one kernel, the covariance in between kept in double on the
+        chip; symmetric bit for bit; ``status`` int32 (0, k + 1 for a failed pivot of ``A + P``, D + k + 1 for one of
+        ``(A + P)^-1 + Q``: then next_prec is NaN).  Device pointers of ``dtype``; ``d_prior_prec`` may be None; the
+        strides are in elements, 0 = one matrix for all rows."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_prior_propagate_device(self.h, code, d_A, d_prior_prec, int(prior_prec_stride), d_noise,
+                                                 int(noise_stride), d_next_prec, d_status, int(n_rows), int(n_inputs)),
+              "gp_prior_propagate_device")
+
+    def prior_propagate(self, A, prior_prec, noise, precision=None, is_gpu=True):
+        """``(next_prec (M, D, D), status (M,) int32)`` of the prior propagation ``((A + P)^-1 + Q)^-1`` for the host
+        array ``A`` (M, D, D), ``prior_prec`` None, (D, D) or (M, D, D) and the process noise ``noise`` (D, D) or
+        (M, D, D): uploads, launches ``gp_prior_propagate_device``, downloads.  ``precision`` is the device dtype
+        (default: float32 when ``A`` is float32, else float64).  ``is_gpu=False`` is the explicit numpy branch
+        (``prior_propagate_numpy``: the same algorithm in float64); never a fallback."""
+        if not is_gpu:
+            return prior_propagate_numpy(A, prior_prec, noise)
+        A = np.asarray(A)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+        dt = np.dtype(precision if precision is not None else (np.float32 if A.dtype == np.float32 else np.float64))
+        M, D = A.shape[:2]
+        P = prec_rows(prior_prec, M, D, dt) if prior_prec is not None else None
+        Q = prec_rows(noise, M, D, dt)
+        ptrs = []
+        try:
+            ptrs.append(self.to_device(np.ascontiguousarray(A, dtype=dt)))
+            ptrs.append(self.to_device(P) if P is not None else None)
+            ptrs.append(self.to_device(Q))
+            d_next, d_status = self.malloc(M * D * D * dt.itemsize), self.malloc(M * 4)
+            ptrs += [d_next, d_status]
+            self.prior_propagate_device(dt, ptrs[0], ptrs[1], row_strides(None, P)[1], ptrs[2], row_strides(None, Q)[1],
+                                        d_next, d_status, M, D)
+            return np.array(self.to_host(d_next, (M, D, D), dt)), np.array(self.to_host(d_status, (M,), np.int32))
+        finally:
+            for p in ptrs:
+                if p is not None:
+                    self.free(p)
+
     def posterior_cov(self, A, prior_prec=None, precision=None, is_gpu=True):
         """``(cov (M, D, D), sigma (M, D), status (M,) int32)`` of the posterior covariance ``(A + P)^-1`` for the host
-        array ``A`` (M, D, D) and ``prior_prec`` (D, D) or None: uploads, launches ``gp_posterior_cov_device``,
+        array ``A`` (M, D, D) and ``prior_prec`` (D, D), per row (M, D, D) or None: uploads, launches
+        ``gp_posterior_cov_device`` (``gp_posterior_cov_rows_device`` for a per-row prior),
         downloads.  ``precision`` is the device dtype (default: float32 when ``A`` is float32, else float64).
         ``is_gpu=False`` is the explicit numpy branch (``posterior_cov_numpy``: the same algorithm in float64); never a
         fallback."""
@@ -567,10 +707,14 @@ class Context:
         ptrs = []
         try:
             ptrs.append(self.to_device(np.ascontiguousarray(A, dtype=dt)))
-            ptrs.append(self.to_device(np.ascontiguousarray(prior_prec, dtype=dt).reshape(D, D)) if prior_prec is not None else None)
+            P = prec_rows(prior_prec, M, D, dt) if prior_prec is not None else None
+            ptrs.append(self.to_device(P) if P is not None else None)
             d_cov, d_sigma, d_status = self.malloc(M * D * D * dt.itemsize), self.malloc(M * D * dt.itemsize), self.malloc(M * 4)
             ptrs += [d_cov, d_sigma, d_status]
-            self.posterior_cov_device(dt, ptrs[0], ptrs[1], d_cov, d_sigma, d_status, M, D)
+            if P is not None and P.ndim == 3:
+                self.posterior_cov_rows_device(dt, ptrs[0], ptrs[1], d_cov, d_sigma, d_status, M, D, D * D)
+            else:
+                self.posterior_cov_device(dt, ptrs[0], ptrs[1], d_cov, d_sigma, d_status, M, D)
             return (np.array(self.to_host(d_cov, (M, D, D), dt)), np.array(self.to_host(d_sigma, (M, D), dt)),
                     np.array(self.to_host(d_status, (M,), np.int32)))
         finally:
@@ -581,7 +725,8 @@ class Context:
     def newton_step(self, x, grad, A, lam, damping="diagonal", prior=None, bounds=None, precision=None, is_gpu=True):
         """``(step, trial, status)`` of the damped Newton step for host arrays ``x`` (M, D), ``grad`` (M, D), ``A``
         (M, D, D) and ``lam`` (M,) or a scalar: uploads, launches ``gp_newton_step_device``, downloads.
-        ``prior=(x0, P)``, ``bounds=(lo, hi)``.  ``precision`` is the device dtype (default: float32 when ``x`` is
+        ``prior=(x0, P)`` (each shared, or per row (M, D) / (M, D, D): then ``gp_newton_step_rows_device``),
+        ``bounds=(lo, hi)``.  ``precision`` is the device dtype (default: float32 when ``x`` is
         float32, else float64).  ``is_gpu=False`` is the explicit numpy branch (``newton_step_numpy``: the same
         algorithm in float64); never a fallback."""
         if not is_gpu:
@@ -596,8 +741,8 @@ class Context:
         host = [np.ascontiguousarray(x, dtype=dt), np.ascontiguousarray(grad, dtype=dt).reshape(M, D),
                 np.ascontiguousarray(A, dtype=dt).reshape(M, D, D),
                 np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=dt), (M,)))]
-        host += [np.ascontiguousarray(prior[0], dtype=dt).reshape(D), np.ascontiguousarray(prior[1], dtype=dt).reshape(D, D)] \
-            if prior is not None else [None, None]
+        host += list(prior_rows(prior, M, D, dt)) if prior is not None else [None, None]
+        strides = row_strides(host[4], host[5])
         host += [np.ascontiguousarray(bounds[0], dtype=dt).reshape(D), np.ascontiguousarray(bounds[1], dtype=dt).reshape(D)] \
             if bounds is not None else [None, None]
         ptrs = []
@@ -606,8 +751,12 @@ class Context:
                 ptrs.append(self.to_device(a) if a is not None else None)
             d_step, d_trial, d_status = self.malloc(M * D * dt.itemsize), self.malloc(M * D * dt.itemsize), self.malloc(M * 4)
             ptrs += [d_step, d_trial, d_status]
-            self.newton_step_device(dt, ptrs[0], ptrs[1], ptrs[2], ptrs[3], d_step, d_trial, d_status, M, D, damping,
-                                    ptrs[4], ptrs[5], ptrs[6], ptrs[7])
+            if any(strides):
+                self.newton_step_rows_device(dt, ptrs[0], ptrs[1], ptrs[2], ptrs[3], d_step, d_trial, d_status, M, D,
+                                             damping, ptrs[4], ptrs[5], ptrs[6], ptrs[7], *strides)
+            else:
+                self.newton_step_device(dt, ptrs[0], ptrs[1], ptrs[2], ptrs[3], d_step, d_trial, d_status, M, D, damping,
+                                        ptrs[4], ptrs[5], ptrs[6], ptrs[7])
             return (np.array(self.to_host(d_step, (M, D), dt)), np.array(self.to_host(d_trial, (M, D), dt)),
                     np.array(self.to_host(d_status, (M,), np.int32)))
         finally:

@@ -10,7 +10,8 @@ LAMBDA_MIN, LAMBDA_MAX = 1e-12, 1e12     # the clamps of the loop's damping
 
 
 def _prior_term(X, prior):
-    """1/2 (x - x0)^T P (x - x0) per row, outer and inner index ascending as lm_update_kernel sums it."""
+    """1/2 (x - x0)^T P (x - x0) per row, outer and inner index ascending as lm_update_kernel sums it; ``x0`` (D,) or
+    per row (M, D), ``P`` (D, D) or per row (M, D, D)."""
     if prior is None:
         return 0.0
     x0, P = prior
@@ -20,7 +21,7 @@ def _prior_term(X, prior):
     for i in range(D):
         ri = np.zeros(d.shape[0])
         for c in range(D):
-            ri += P[i, c] * d[:, c]
+            ri += P[..., i, c] * d[:, c]
         q += d[:, i] * ri
     return 0.5 * q
 
@@ -41,19 +42,21 @@ def _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, status, 
     return accept.astype(np.int32)
 
 
-def prior_and_bounds(prior, bounds, D):
-    """``prior`` as float64 ``(x0 (D,), P (D, D))`` and ``bounds`` as float64 ``(lo (D,), hi (D,))``; None stays None."""
+def prior_and_bounds(prior, bounds, D, M=1):
+    """``prior`` as float64 ``(x0, P)`` -- ``x0`` (D,) or per row (M, D), ``P`` (D, D) or per row (M, D, D) -- and
+    ``bounds`` as float64 ``(lo (D,), hi (D,))``; None stays None."""
     if prior is not None:
-        prior = (np.asarray(prior[0], dtype=np.float64).reshape(D), np.asarray(prior[1], dtype=np.float64).reshape(D, D))
+        prior = _lib.prior_rows(prior, M, D)
     if bounds is not None:
         bounds = (np.asarray(bounds[0], dtype=np.float64).reshape(D), np.asarray(bounds[1], dtype=np.float64).reshape(D))
     return prior, bounds
 
 
-def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov):
+def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov, next_prior=None):
     """The loop on the host in float64: ``data_term(X) -> (cost, grad, A)``, ``step(x, grad, A, lam) -> (step, trial,
-    status)``.  Returns ``(X, cost, state, n_accepted, lam)`` and with ``return_cov`` ``_lib.posterior_cov_numpy``'s
-    three of the loop's ``A``."""
+    status)``.  Returns ``(X, cost, state, n_accepted, lam)``, with ``return_cov`` ``_lib.posterior_cov_numpy``'s
+    three of the loop's ``A`` behind them, and with a process noise ``next_prior`` ``_lib.prior_propagate_numpy``'s
+    two behind those."""
     M = X0.shape[0]
     X = np.array(X0, dtype=np.float64)
     lam = np.full(M, float(lam0))
@@ -67,9 +70,12 @@ def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, r
                                   down, up, LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
         if it % 4 == 3 and np.all(state == 1):
             break
+    out = (X, cost, state, n_acc, lam)
     if return_cov:
-        return (X, cost, state, n_acc, lam) + _lib.posterior_cov_numpy(A, prior[1] if prior is not None else None)
-    return X, cost, state, n_acc, lam
+        out += _lib.posterior_cov_numpy(A, prior[1] if prior is not None else None)
+    if next_prior is not None:
+        out += _lib.prior_propagate_numpy(A, prior[1] if prior is not None else None, next_prior)
+    return out
 
 
 class Scratch(object):
@@ -96,12 +102,16 @@ class Scratch(object):
             self.ctx.free(p)
 
 
-def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov, misfit):
+def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov, misfit, next_prior=None):
     """The loop on the device from the host rows ``X0``, in the precision and on the context of ``scratch`` (the
     caller's ``Scratch``, which also holds whatever ``misfit`` reads).  ``misfit(d_rows, d_cost, d_grad, d_A)`` enqueues
     the data term at ``d_rows`` on the context's stream.  Every iteration is that, ``lm_update_device`` and
     ``newton_step_device``; nothing comes back inside the loop but ``state``, every fourth iteration, to stop when every
-    row has converged.  Returns what ``lm_numpy`` returns, in the scratch's precision."""
+    row has converged.  With a per-row prior -- ``x0`` (M, D) or ``P`` (M, D, D) -- the two are the ``_rows`` entries
+    with the arrays' row strides; with a shared or absent prior the calls are exactly the plain ones.  A process noise
+    ``next_prior`` (D, D) or (M, D, D) adds one ``prior_propagate_device`` call after the loop (and after the
+    covariance) on the loop's own ``d_A`` and ``d_P``.  Returns what ``lm_numpy`` returns, in the scratch's
+    precision."""
     ctx, dt = scratch.ctx, scratch.dt
     up_, alloc, isz = scratch.up, scratch.alloc, dt.itemsize
     d_x, d_lam = up_(X0), up_(np.full(M, float(lam0)))
@@ -113,17 +123,27 @@ def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, 
     d_acc = alloc(max_iter * M * 4)            # one (M,) slice per iteration, summed after the loop
     _lib.check(ctx.lib.gp_memset(ctx.h, d_state, 0, M * 4), "gp_memset")
 
+    strides = _lib.row_strides(*prior) if prior is not None else (0, 0)
+    rows = any(strides)
+
     def newton():
-        ctx.newton_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0, d_P,
-                               d_lo, d_hi)
+        if rows:
+            ctx.newton_step_rows_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0,
+                                        d_P, d_lo, d_hi, strides[0], strides[1])
+        else:
+            ctx.newton_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0, d_P,
+                                   d_lo, d_hi)
     misfit(d_x, d_cost, d_grad, d_A)
     newton()
     done = 0
     for it in range(max_iter):
         misfit(d_trial, d_cost_t, d_grad_t, d_A_t)
-        ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status,
-                             d_state, _lib.c_void_p(d_acc.value + it * M * 4), M, D, d_x0, d_P, down, up,
-                             LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
+        update = (dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status, d_state,
+                  _lib.c_void_p(d_acc.value + it * M * 4), M, D, d_x0, d_P, down, up, LAMBDA_MIN, LAMBDA_MAX, ftol, xtol)
+        if rows:
+            ctx.lm_update_rows_device(*update + strides)
+        else:
+            ctx.lm_update_device(*update)
         newton()
         done = it + 1
         if it % 4 == 3:                       # (the copy synchronises the stream first)
@@ -134,10 +154,52 @@ def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, 
     X, cost, lam = (np.array(ctx.to_host(p, s, dt)) for p, s in ((d_x, (M, D)), (d_cost, (M,)), (d_lam, (M,))))
     state = np.array(ctx.to_host(d_state, (M,), np.int32))
     n_acc = np.array(ctx.to_host(d_acc, (done, M), np.int32)).sum(axis=0, dtype=np.int32) if done else np.zeros(M, np.int32)
+    out = (X, cost, state, n_acc, lam)
     if return_cov:
         d_cov, d_sigma, d_cstat = alloc(M * D * D * isz), alloc(M * D * isz), alloc(M * 4)
-        ctx.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D)
+        if strides[1]:
+            ctx.posterior_cov_rows_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D, strides[1])
+        else:
+            ctx.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D)
         ctx.synchronize()
-        return (X, cost, state, n_acc, lam, np.array(ctx.to_host(d_cov, (M, D, D), dt)),
-                np.array(ctx.to_host(d_sigma, (M, D), dt)), np.array(ctx.to_host(d_cstat, (M,), np.int32)))
-    return X, cost, state, n_acc, lam
+        out += (np.array(ctx.to_host(d_cov, (M, D, D), dt)), np.array(ctx.to_host(d_sigma, (M, D), dt)),
+                np.array(ctx.to_host(d_cstat, (M,), np.int32)))
+    if next_prior is not None:
+        Q = _lib.prec_rows(next_prior, M, D)
+        d_Q, d_next, d_pstat = up_(Q), alloc(M * D * D * isz), alloc(M * 4)
+        ctx.prior_propagate_device(dt, d_A, d_P, strides[1], d_Q, _lib.row_strides(None, Q)[1], d_next, d_pstat, M, D)
+        ctx.synchronize()
+        out += (np.array(ctx.to_host(d_next, (M, D, D), dt)), np.array(ctx.to_host(d_pstat, (M,), np.int32)))
+    return out
+
+
+def retrieve_series(retrieve, X0, obs, weights, prior, noise, **loop_args):
+    """A time series of retrievals, date after date, each date's posterior the next date's prior (random-walk
+    dynamics: the next prior mean is the retrieved state, the next prior precision ``((A + P)^-1 + Q)^-1`` with the
+    process noise ``Q = noise`` (D, D) or (M, D, D)).  ``retrieve(X0, obs, weights, prior=, return_cov=, next_prior=,
+    **loop_args)`` is one date's retrieval (``retrieve_bands`` on its emulators, or ``retrieve_many``); ``obs`` and
+    ``weights`` carry a leading date axis T (``weights`` may be None).  ``prior`` is required: it keeps ``A + P``
+    positive definite for the pixels without a valid observation on a date.  Date 0 starts from ``X0`` with ``prior``,
+    date t from ``X[t - 1]`` with ``(X[t - 1], next_prec[t - 1])``.
+
+    Returns ``(X (T, M, D), sigma (T, M, D), cost (T, M), state (T, M), cov_status (T, M), prior_status (T, M),
+    next_prec (M, D, D))``, the last the prior precision for the date after the series.  A host loop over the dates:
+    the state goes down and up once per date."""
+    if prior is None:
+        raise ValueError("a series needs a prior")
+    T = len(obs)
+    if T == 0:
+        raise ValueError("obs has no dates")
+    if weights is not None and len(weights) != T:
+        raise ValueError("obs has %d dates, weights %d" % (T, len(weights)))
+    for name in ("prior", "return_cov", "next_prior"):
+        if name in loop_args:
+            raise ValueError("%s is the series' own argument" % name)
+    X, keep, next_prec = X0, [], None
+    for t in range(T):
+        out = retrieve(X, obs[t], weights[t] if weights is not None else None, prior=prior, return_cov=True,
+                       next_prior=noise, **loop_args)
+        X, next_prec = out[0], out[8]
+        keep.append((X, out[6], out[1], out[2], out[7], out[9]))
+        prior = (X, next_prec)
+    return tuple(np.stack(a) for a in zip(*keep)) + (next_prec,)

@@ -1,4 +1,5 @@
-// Launch sizing, and predict, Hessian, Newton step, LM update and posterior covariance on device buffers.
+// Launch sizing, and predict, Hessian, Newton step, LM update, posterior covariance and prior propagation on device
+// buffers.
 #include "gp_host.hpp"
 
 #include "gp_generic_kernel.hpp"
@@ -9,6 +10,7 @@
 #include "gp_misfit_kernel.hpp"
 #include "gp_newton_kernel.hpp"
 #include "gp_posterior_cov_kernel.hpp"
+#include "gp_prior_propagate_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
 
 // The per-size launchers by their run-time size: one switch over the compiled NK, one over the compiled NB.
@@ -365,10 +367,18 @@ static int newton_sizes(int dtype, int64_t n_rows, int n_inputs) {
   return GP_OK;
 }
 
-int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
-                          const void* d_lambda, int damping, const void* d_prior_mean, const void* d_prior_prec,
-                          const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
-                          int64_t n_rows, int n_inputs) {
+// a row stride in elements: 0 (one array for all rows) or at least one row's elements; never without the pointer
+static int row_stride(const char* what, const void* ptr, int64_t stride, int64_t row_elems) {
+  if (stride != 0 && stride < row_elems)
+    return fail(GP_ERR_INVALID, "%s stride %lld is neither 0 nor >= %lld", what, (long long)stride, (long long)row_elems);
+  if (stride != 0 && !ptr) return fail(GP_ERR_INVALID, "%s stride without a pointer", what);
+  return GP_OK;
+}
+
+int gp_newton_step_rows_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
+                               const void* d_lambda, int damping, const void* d_prior_mean, const void* d_prior_prec,
+                               const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
+                               int64_t n_rows, int n_inputs, int64_t prior_mean_stride, int64_t prior_prec_stride) {
   if (!ctx) return fail(GP_ERR_INVALID, "null context");
   if (!d_x || !d_grad || !d_A || !d_lambda || !d_status || (!d_step && !d_trial))
     return fail(GP_ERR_INVALID, "null device pointer");
@@ -377,6 +387,8 @@ int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d
   if ((d_prior_mean != nullptr) != (d_prior_prec != nullptr))
     return fail(GP_ERR_INVALID, "prior mean and prior precision go together");
   if ((d_lo != nullptr) != (d_hi != nullptr)) return fail(GP_ERR_INVALID, "lower and upper bounds go together");
+  if (int rc = row_stride("prior mean", d_prior_mean, prior_mean_stride, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   return for_dtype(dtype, [&](auto t) {
     using T = GP_TAG_TYPE(t);
@@ -387,6 +399,8 @@ int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d
     a.lambda = as<T>(d_lambda);
     a.prior_mean = as<T>(d_prior_mean);
     a.prior_prec = as<T>(d_prior_prec);
+    a.prior_mean_stride = prior_mean_stride;
+    a.prior_prec_stride = prior_prec_stride;
     a.lo = as<T>(d_lo);
     a.hi = as<T>(d_hi);
     a.step = as<T>(d_step);
@@ -401,12 +415,20 @@ int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d
   });
 }
 
-int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost, const void* d_cost_trial,
-                        void* d_grad, const void* d_grad_trial, void* d_A, const void* d_A_trial,
-                        void* d_lambda, const int32_t* d_status, int32_t* d_state, int32_t* d_accepted,
-                        const void* d_prior_mean, const void* d_prior_prec, double down, double up,
-                        double lambda_min, double lambda_max, double ftol, double xtol,
-                        int64_t n_rows, int n_inputs) {
+int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
+                          const void* d_lambda, int damping, const void* d_prior_mean, const void* d_prior_prec,
+                          const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
+                          int64_t n_rows, int n_inputs) {
+  return gp_newton_step_rows_device(ctx, dtype, d_x, d_grad, d_A, d_lambda, damping, d_prior_mean, d_prior_prec, d_lo, d_hi,
+                                    d_step, d_trial, d_status, n_rows, n_inputs, 0, 0);
+}
+
+int gp_lm_update_rows_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost,
+                             const void* d_cost_trial, void* d_grad, const void* d_grad_trial, void* d_A,
+                             const void* d_A_trial, void* d_lambda, const int32_t* d_status, int32_t* d_state,
+                             int32_t* d_accepted, const void* d_prior_mean, const void* d_prior_prec, double down,
+                             double up, double lambda_min, double lambda_max, double ftol, double xtol,
+                             int64_t n_rows, int n_inputs, int64_t prior_mean_stride, int64_t prior_prec_stride) {
   if (!ctx) return fail(GP_ERR_INVALID, "null context");
   if (!d_x || !d_trial || !d_cost || !d_cost_trial || !d_lambda || !d_status || !d_state)
     return fail(GP_ERR_INVALID, "null device pointer");
@@ -415,6 +437,8 @@ int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, 
     return fail(GP_ERR_INVALID, "grad / grad_trial and A / A_trial are given or left out as pairs");
   if ((d_prior_mean != nullptr) != (d_prior_prec != nullptr))
     return fail(GP_ERR_INVALID, "prior mean and prior precision go together");
+  if (int rc = row_stride("prior mean", d_prior_mean, prior_mean_stride, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   return for_dtype(dtype, [&](auto t) {
     using T = GP_TAG_TYPE(t);
@@ -433,6 +457,8 @@ int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, 
     a.accepted = d_accepted;
     a.prior_mean = as<T>(d_prior_mean);
     a.prior_prec = as<T>(d_prior_prec);
+    a.prior_mean_stride = prior_mean_stride;
+    a.prior_prec_stride = prior_prec_stride;
     a.down = down;
     a.up = up;
     a.lambda_min = lambda_min;
@@ -447,17 +473,31 @@ int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, 
   });
 }
 
-int gp_posterior_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, void* d_cov, void* d_sigma,
-                            int32_t* d_status, int64_t n_rows, int n_inputs) {
+int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost, const void* d_cost_trial,
+                        void* d_grad, const void* d_grad_trial, void* d_A, const void* d_A_trial,
+                        void* d_lambda, const int32_t* d_status, int32_t* d_state, int32_t* d_accepted,
+                        const void* d_prior_mean, const void* d_prior_prec, double down, double up,
+                        double lambda_min, double lambda_max, double ftol, double xtol,
+                        int64_t n_rows, int n_inputs) {
+  return gp_lm_update_rows_device(ctx, dtype, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A, d_A_trial,
+                                  d_lambda, d_status, d_state, d_accepted, d_prior_mean, d_prior_prec, down, up, lambda_min,
+                                  lambda_max, ftol, xtol, n_rows, n_inputs, 0, 0);
+}
+
+int gp_posterior_cov_rows_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, void* d_cov,
+                                 void* d_sigma, int32_t* d_status, int64_t n_rows, int n_inputs,
+                                 int64_t prior_prec_stride) {
   if (!ctx) return fail(GP_ERR_INVALID, "null context");
   if (!d_A || !d_status || (!d_cov && !d_sigma)) return fail(GP_ERR_INVALID, "null device pointer");
   if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   return for_dtype(dtype, [&](auto t) {
     using T = GP_TAG_TYPE(t);
     gpk::PosteriorCovArgs<T> a;
     a.A = as<T>(d_A);
     a.prior_prec = as<T>(d_prior_prec);
+    a.prior_prec_stride = prior_prec_stride;
     a.cov = as<T>(d_cov);
     a.sigma = as<T>(d_sigma);
     a.status = d_status;
@@ -465,6 +505,38 @@ int gp_posterior_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void*
     a.d = n_inputs;
     hipError_t e = gpk::launch_posterior_cov<T>(a, ctx->stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "posterior covariance kernel launch: %s", hipGetErrorString(e));
+    return (int)GP_OK;
+  });
+}
+
+int gp_posterior_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, void* d_cov, void* d_sigma,
+                            int32_t* d_status, int64_t n_rows, int n_inputs) {
+  return gp_posterior_cov_rows_device(ctx, dtype, d_A, d_prior_prec, d_cov, d_sigma, d_status, n_rows, n_inputs, 0);
+}
+
+int gp_prior_propagate_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, int64_t prior_prec_stride,
+                              const void* d_noise, int64_t noise_stride, void* d_next_prec, int32_t* d_status,
+                              int64_t n_rows, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_A || !d_noise || !d_next_prec || !d_status) return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  if (int rc = row_stride("process noise", d_noise, noise_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::PriorPropagateArgs<T> a;
+    a.A = as<T>(d_A);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_prec_stride = prior_prec_stride;
+    a.noise = as<T>(d_noise);
+    a.noise_stride = noise_stride;
+    a.next_prec = as<T>(d_next_prec);
+    a.status = d_status;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    hipError_t e = gpk::launch_prior_propagate<T>(a, ctx->stream);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "prior propagation kernel launch: %s", hipGetErrorString(e));
     return (int)GP_OK;
   });
 }

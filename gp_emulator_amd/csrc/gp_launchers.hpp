@@ -16,6 +16,7 @@ template <typename T> struct BandMisfitArgs;
 template <typename T> struct NewtonArgs;
 template <typename T> struct LmUpdateArgs;
 template <typename T> struct PosteriorCovArgs;
+template <typename T> struct PriorPropagateArgs;
 template <typename T> struct ReconArgs;
 template <typename T> struct MisfitArgs;
 template <typename T> struct GramArgs;
@@ -35,6 +36,7 @@ template <typename T> hipError_t launch_band_misfit_add(const T* gn, T* hess, lo
 template <typename T> hipError_t launch_newton_step(const NewtonArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_lm_update(const LmUpdateArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_posterior_cov(const PosteriorCovArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_prior_propagate(const PriorPropagateArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_reconstruct(const ReconArgs<T>&, int wide, int cus, hipStream_t);
 template <typename T> hipError_t launch_misfit(const MisfitArgs<T>&, int cus, hipStream_t);
 template <typename T> hipError_t launch_gauss_newton(const T* deriv, const T* A, T* gn, long long M, int P, int D, int cus, hipStream_t);

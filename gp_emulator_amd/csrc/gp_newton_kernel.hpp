@@ -3,7 +3,8 @@
 //
 // newton_step_kernel<T>, for every row m (D = n_inputs <= 32, a run-time argument):
 //
-//   A' = A[m] (+ P)                       P [D][D] prior precision, x0 [D] prior mean: both or neither
+//   A' = A[m] (+ P)                       P [D][D] prior precision, x0 [D] prior mean: both or neither; each shared
+//                                         by the rows (stride 0) or row m's own at m * stride elements
 //   g' = grad[m] (+ P (x_m - x0))         chain over the column index, ascending, started from grad
 //   A'_dd += lambda[m] s_d                s_d = A'_dd (GP_DAMP_DIAGONAL, before damping) or 1 (GP_DAMP_IDENTITY)
 //   L L^T = A'                            Cholesky of the LOWER triangle; the upper triangle is never loaded
@@ -39,7 +40,8 @@
 //
 // lm_update_kernel<T>: one row per wave, four rows per workgroup, plain grid.  For a row with state == 0,
 //   F   = cost       + 1/2 (x - x0)^T P (x - x0)          (the prior term only with P; double; sum_i d_i (sum_c P_ic d_c),
-//   F_t = cost_trial + 1/2 (t - x0)^T P (t - x0)           outer and inner index ascending, every lane the same chain)
+//   F_t = cost_trial + 1/2 (t - x0)^T P (t - x0)           outer and inner index ascending, every lane the same chain;
+//                                                          x0 and P shared or the row's own, as in the step)
 //   accept = status == 0 && isfinite(F_t) && F_t < F
 //   accept: x, cost, grad, A <- trial, cost_trial, grad_trial, A_trial (copies), lambda <- max(lambda down, lambda_min),
 //           state <- (F - F_t <= ftol F || max_d |t_d - x_d| <= xtol)
@@ -62,6 +64,8 @@ struct NewtonArgs {
   const T* lambda;       // [rows]
   const T* prior_mean;   // [d] or nullptr (with prior_prec)
   const T* prior_prec;   // [d][d] or nullptr
+  long long prior_mean_stride;   // elements from one row's prior mean to the next; 0 = one for all rows
+  long long prior_prec_stride;   // the same of the prior precision
   const T* lo;           // [d] or nullptr (with hi)
   const T* hi;
   T* step;               // [rows][d] or nullptr
@@ -88,6 +92,8 @@ struct LmUpdateArgs {
   int* accepted;         // [rows] or nullptr
   const T* prior_mean;   // [d] or nullptr (with prior_prec)
   const T* prior_prec;   // [d][d] or nullptr
+  long long prior_mean_stride;   // elements from one row's prior mean to the next; 0 = one for all rows
+  long long prior_prec_stride;   // the same of the prior precision
   double down, up, lambda_min, lambda_max, ftol, xtol;
   long long rows;
   int d;
@@ -111,10 +117,41 @@ __device__ inline void newton_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// A wave's run of nr matrices at row0, consecutive lanes on consecutive elements: the lower triangles (+ P) to the packed
+// triangles Lw (newton_step_kernel, posterior_cov_kernel and prior_propagate_kernel stage alike).  ROWS = false is the
+// shared prior, element e of the one matrix; ROWS = true reads the global row's, row0 + r.  The caller branches once per
+// wave on the stride, so a shared prior costs the address arithmetic it always did.
+template <typename T, bool ROWS>
+__device__ inline void newton_stage_run(double* Lw, const T* A, const T* prior_prec, long long prior_prec_stride, long long row0,
+                                        int nr, int D, int S, int lane) {
+  const int DD = D * D;
+  const T* Ag = A + row0 * DD;
+  const T* Pw = ROWS ? prior_prec + row0 * prior_prec_stride : prior_prec;      // (the wave's first row's)
+  const int n = nr * DD;
+  for (int idx = lane; idx < n; idx += 64) {
+    const int r = idx / DD, e = idx - r * DD;
+    const int i = e / D, c = e - i * D;
+    if (c <= i) {
+      double v = (double)Ag[idx];
+      if (prior_prec) v += (double)(ROWS ? Pw[r * prior_prec_stride + e] : Pw[e]);
+      Lw[r * S + newton_tri(i) + c] = v;
+    }
+  }
+}
+
+template <typename T>
+__device__ inline void newton_stage(double* Lw, const T* A, const T* prior_prec, long long prior_prec_stride, long long row0,
+                                    int nr, int D, int S, int lane) {
+  if (prior_prec_stride == 0)
+    newton_stage_run<T, false>(Lw, A, prior_prec, 0, row0, nr, D, S, lane);
+  else
+    newton_stage_run<T, true>(Lw, A, prior_prec, prior_prec_stride, row0, nr, D, S, lane);
+}
+
 template <typename T>
 __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<T> p) {
   extern __shared__ double newton_lds[];
-  const int D = p.d, DD = D * D;
+  const int D = p.d;
   const int G = newton_group(D), S = newton_pitch(D);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int R = 64 / G;                                     // rows of a wave
@@ -124,19 +161,7 @@ __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<
   double* Lw = newton_lds + wave * R * S;                   // this wave's matrices
 
   // the wave's run of A, consecutive lanes on consecutive elements; the lower triangles (+ P) to LDS
-  {
-    const T* Ag = p.A + row0 * DD;
-    const int n = nr * DD;
-    for (int idx = lane; idx < n; idx += 64) {
-      const int r = idx / DD, e = idx - r * DD;
-      const int i = e / D, c = e - i * D;
-      if (c <= i) {
-        double v = (double)Ag[idx];
-        if (p.prior_prec) v += (double)p.prior_prec[e];
-        Lw[r * S + newton_tri(i) + c] = v;
-      }
-    }
-  }
+  newton_stage(Lw, p.A, p.prior_prec, p.prior_prec_stride, row0, nr, D, S, lane);
   newton_wave_sync();
 
   const int r = lane / G, j = lane - r * G;                 // matrix row j of the wave's row r
@@ -151,9 +176,14 @@ __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<
     xj = (double)p.x[m * D + j];
     acc = (double)p.grad[m * D + j];
     if (p.prior_prec) {
-      const T* Pj = p.prior_prec + j * D;
+      const T* Pj = p.prior_prec + m * p.prior_prec_stride + j * D;
       const T* xm = p.x + m * D;
-      for (int c = 0; c < D; ++c) acc = fma((double)Pj[c], (double)xm[c] - (double)p.prior_mean[c], acc);
+      if (p.prior_mean_stride == 0) {         // one x0 for all rows: one address per load for the whole wave
+        for (int c = 0; c < D; ++c) acc = fma((double)Pj[c], (double)xm[c] - (double)p.prior_mean[c], acc);
+      } else {
+        const T* x0 = p.prior_mean + m * p.prior_mean_stride;
+        for (int c = 0; c < D; ++c) acc = fma((double)Pj[c], (double)xm[c] - (double)x0[c], acc);
+      }
     }
     const double lam = (double)p.lambda[m];
     const double a = L[tj + j];
@@ -223,10 +253,14 @@ __global__ __launch_bounds__(kNewtonThreads) void lm_update_kernel(LmUpdateArgs<
   double dx = 0.0;
   for (int d = 0; d < D; ++d) dx = fmax(dx, fabs((double)t[d] - (double)x[d]));
   if (p.prior_prec) {
-    const T* x0 = p.prior_mean;
+    // the row once more, as a value the compiler knows to be the same in every lane: the row's prior, which the
+    // kernel never writes, is then read as the shared one is, by loads of the wave rather than of its lanes
+    const long long mw = (long long)blockIdx.x * (kNewtonThreads / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const T* x0 = p.prior_mean + mw * p.prior_mean_stride;
+    const T* Pm = p.prior_prec + mw * p.prior_prec_stride;
     double q = 0.0, qt = 0.0;
     for (int i = 0; i < D; ++i) {
-      const T* Pi = p.prior_prec + i * D;
+      const T* Pi = Pm + i * D;
       double ri = 0.0, rti = 0.0;
       for (int c = 0; c < D; ++c) {
         const double pic = (double)Pi[c], x0c = (double)x0[c];

@@ -1,6 +1,8 @@
-// newton_step_kernel<T>, lm_update_kernel<T> and posterior_cov_kernel<T> launchers; both dtypes in one unit.
+// newton_step_kernel<T>, lm_update_kernel<T>, posterior_cov_kernel<T> and prior_propagate_kernel<T> launchers; both
+// dtypes in one unit.
 #include "gp_newton_kernel.hpp"
 #include "gp_posterior_cov_kernel.hpp"
+#include "gp_prior_propagate_kernel.hpp"
 #include "gp_launchers.hpp"
 
 namespace gpk {
@@ -41,11 +43,25 @@ hipError_t launch_posterior_cov(const PosteriorCovArgs<T>& a, hipStream_t stream
   return hipGetLastError();
 }
 
+// the covariance kernel's geometry and LDS: two inversions on the same two triangles
+template <typename T>
+hipError_t launch_prior_propagate(const PriorPropagateArgs<T>& a, hipStream_t stream) {
+  if (a.rows <= 0) return hipSuccess;
+  if (a.d < 1 || a.d > kNewtonMaxD) return hipErrorInvalidValue;
+  const int per_wg = post_cov_rows_per_wg(a.d);
+  const long long blocks = (a.rows + per_wg - 1) / per_wg;
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((prior_propagate_kernel<T>), dim3((unsigned)blocks), dim3(kPostCovThreads), post_cov_lds_bytes(a.d), stream, a);
+  return hipGetLastError();
+}
+
 template hipError_t launch_newton_step<float>(const NewtonArgs<float>&, hipStream_t);
 template hipError_t launch_newton_step<double>(const NewtonArgs<double>&, hipStream_t);
 template hipError_t launch_lm_update<float>(const LmUpdateArgs<float>&, hipStream_t);
 template hipError_t launch_lm_update<double>(const LmUpdateArgs<double>&, hipStream_t);
 template hipError_t launch_posterior_cov<float>(const PosteriorCovArgs<float>&, hipStream_t);
 template hipError_t launch_posterior_cov<double>(const PosteriorCovArgs<double>&, hipStream_t);
+template hipError_t launch_prior_propagate<float>(const PriorPropagateArgs<float>&, hipStream_t);
+template hipError_t launch_prior_propagate<double>(const PriorPropagateArgs<double>&, hipStream_t);
 
 }  // namespace gpk

@@ -3,8 +3,9 @@
 //
 // posterior_cov_kernel<T>, for every row m (D = n_inputs <= 32, a run-time argument):
 //
-//   A' = A[m] (+ P)                       P [D][D] prior precision, nullable; the lower triangle is read, the upper
-//                                         never loaded; no damping
+//   A' = A[m] (+ P)                       P [D][D] prior precision, nullable, shared by the rows (stride 0) or row m's
+//                                         own at m * stride elements; the lower triangle is read, the upper never
+//                                         loaded; no damping
 //   L L^T = A'                            newton_step_kernel's factorisation: same chains, same order, same pivot test
 //   C[:, j] = L^-T L^-1 e_j               every column a Cholesky solve of a unit vector
 //   cov[m]   = C, [D][D]                  elements i >= j from column j's solve, the upper triangle mirrored from them
@@ -63,6 +64,7 @@ template <typename T>
 struct PosteriorCovArgs {
   const T* A;            // [rows][d][d], lower triangle read
   const T* prior_prec;   // [d][d] or nullptr
+  long long prior_prec_stride;   // elements from one row's prior precision to the next; 0 = one for all rows
   T* cov;                // [rows][d][d] or nullptr
   T* sigma;              // [rows][d] or nullptr (not both)
   int* status;           // [rows]
@@ -73,44 +75,13 @@ struct PosteriorCovArgs {
 __host__ __device__ inline int post_cov_rows_per_wg(int d) { return kPostCovThreads / newton_group(d); }
 inline size_t post_cov_lds_bytes(int d) { return (size_t)post_cov_rows_per_wg(d) * 2 * newton_pitch(d) * sizeof(double); }
 
-template <typename T>
-__global__ __launch_bounds__(kPostCovThreads) void posterior_cov_kernel(PosteriorCovArgs<T> p) {
-  extern __shared__ double post_cov_lds[];
-  const int D = p.d, DD = D * D;
-  const int G = newton_group(D), S = newton_pitch(D);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int R = 64 / G;                                     // rows of a wave
-  const long long row0 = ((long long)blockIdx.x * (kPostCovThreads / 64) + wave) * R;
-  const long long left = p.rows - row0;
-  const int nr = left >= R ? R : (left > 0 ? (int)left : 0);
-  double* Lw = post_cov_lds + wave * (2 * R * S);           // this wave's L triangles, R of them
-  double* Ww = Lw + R * S;                                  // and its W triangles behind them
+// The pieces of the kernel, shared with prior_propagate_kernel (gp_prior_propagate_kernel.hpp).  Lw / Ww are a wave's
+// L and W triangles, L / W those of the calling lane's row; lane j of the row's sub-group of G lanes, act = j < D.
+// (The staging of A (+ P) is newton_stage of gp_newton_kernel.hpp, the step kernel's.)
 
-  // the wave's run of A, consecutive lanes on consecutive elements; the lower triangles (+ P) to LDS
-  {
-    const T* Ag = p.A + row0 * DD;
-    const int n = nr * DD;
-    for (int idx = lane; idx < n; idx += 64) {
-      const int r = idx / DD, e = idx - r * DD;
-      const int i = e / D, c = e - i * D;
-      if (c <= i) {
-        double v = (double)Ag[idx];
-        if (p.prior_prec) v += (double)p.prior_prec[e];
-        Lw[r * S + newton_tri(i) + c] = v;
-      }
-    }
-  }
-  newton_wave_sync();
-
-  const int r = lane / G, j = lane - r * G;                 // matrix row j, then column j of C, of the wave's row r
-  const long long m = row0 + r;
-  const bool act = j < D;                                   // (every index below stays inside the row's triangles)
-  const bool live = act && r < nr;
-  double* L = Lw + r * S;
-  double* W = Ww + r * S;
+// L L^T = A' in place, column after column (newton_step_kernel's loop); 0, or k + 1 for the first failed pivot
+__device__ inline int post_cov_factor(double* L, int D, int G, int j, bool act) {
   const int tj = newton_tri(j);
-
-  // L L^T = A', column after column (newton_step_kernel's loop)
   int bad = 0;
   for (int k = 0; k < D; ++k) {
     double s = 0.0;
@@ -125,7 +96,11 @@ __global__ __launch_bounds__(kPostCovThreads) void posterior_cov_kernel(Posterio
     if (act && j >= k) L[tj + k] = j == k ? dk : s / dk;
     newton_wave_sync();
   }
+  return bad;
+}
 
+// column j of (L L^T)^-1 at the rows i >= j into W[i][j]; quiet NaN throughout when bad
+__device__ inline void post_cov_solve(const double* L, double* W, int D, int j, bool act, int bad) {
   // y = L^-1 e_j: lane j runs i = j .. D-1, W[i][j] = y_i (the loops are uniform so that L[i][k] is a broadcast)
   for (int i = 0; i < D; ++i) {
     const bool on = act && j <= i;
@@ -145,24 +120,56 @@ __global__ __launch_bounds__(kPostCovThreads) void posterior_cov_kernel(Posterio
       if (on) a = fma(-L[newton_tri(k) + i], W[newton_tri(k) + j], a);
     if (on) W[ti + j] = bad ? qnan : a / L[ti + i];
   }
+}
+
+// the wave's run of nr result matrices at row0 from Ww, consecutive lanes on consecutive elements: (i, c) and (c, i)
+// are the same double
+template <typename T>
+__device__ inline void post_cov_store(T* out, const double* Ww, long long row0, int nr, int D, int S, int lane) {
+  const int DD = D * D;
+  T* Cg = out + row0 * DD;
+  const int n = nr * DD;
+  for (int idx = lane; idx < n; idx += 64) {
+    const int rr = idx / DD, e = idx - rr * DD;
+    const int i = e / D, c = e - i * D;
+    const int hi = i > c ? i : c, lo = i > c ? c : i;
+    Cg[idx] = (T)Ww[rr * S + newton_tri(hi) + lo];
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPostCovThreads) void posterior_cov_kernel(PosteriorCovArgs<T> p) {
+  extern __shared__ double post_cov_lds[];
+  const int D = p.d;
+  const int G = newton_group(D), S = newton_pitch(D);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int R = 64 / G;                                     // rows of a wave
+  const long long row0 = ((long long)blockIdx.x * (kPostCovThreads / 64) + wave) * R;
+  const long long left = p.rows - row0;
+  const int nr = left >= R ? R : (left > 0 ? (int)left : 0);
+  double* Lw = post_cov_lds + wave * (2 * R * S);           // this wave's L triangles, R of them
+  double* Ww = Lw + R * S;                                  // and its W triangles behind them
+
+  newton_stage(Lw, p.A, p.prior_prec, p.prior_prec_stride, row0, nr, D, S, lane);
+  newton_wave_sync();
+
+  const int r = lane / G, j = lane - r * G;                 // matrix row j, then column j of C, of the wave's row r
+  const long long m = row0 + r;
+  const bool act = j < D;                                   // (every index below stays inside the row's triangles)
+  const bool live = act && r < nr;
+  double* L = Lw + r * S;
+  double* W = Ww + r * S;
+
+  const int bad = post_cov_factor(L, D, G, j, act);
+  post_cov_solve(L, W, D, j, act, bad);
 
   if (live) {
-    if (p.sigma) p.sigma[m * D + j] = (T)(bad ? qnan : sqrt(W[tj + j]));
+    if (p.sigma) p.sigma[m * D + j] = (T)(bad ? __builtin_nan("") : sqrt(W[newton_tri(j) + j]));
     if (j == 0) p.status[m] = bad;
   }
   if (!p.cov) return;
   newton_wave_sync();
-  // the wave's run of cov, consecutive lanes on consecutive elements: (i, c) and (c, i) are the same double
-  {
-    T* Cg = p.cov + row0 * DD;
-    const int n = nr * DD;
-    for (int idx = lane; idx < n; idx += 64) {
-      const int rr = idx / DD, e = idx - rr * DD;
-      const int i = e / D, c = e - i * D;
-      const int hi = i > c ? i : c, lo = i > c ? c : i;
-      Cg[idx] = (T)Ww[rr * S + newton_tri(hi) + lo];
-    }
-  }
+  post_cov_store(p.cov, Ww, row0, nr, D, S, lane);
 }
 
 }  // namespace gpk

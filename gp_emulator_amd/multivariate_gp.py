@@ -477,7 +477,7 @@ class MultivariateEmulator(object):
         return cost, coef, grads, grad, None if G is None else self._contract_numpy(grads, G)
 
     def retrieve_many(self, Y0, obs, weights=None, prior=None, bounds=None, lam0=1e-2, max_iter=20, down=1.0 / 3.0,
-                      up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False):
+                      up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False, next_prior=None):
         """Levenberg-Marquardt retrieval of M state vectors at once on this emulator: minimises, row by row,
 
             F(y) = 1/2 sum_b w_b (f_b(y) - obs_b)^2  (+ 1/2 (y - y0)^T P (y - y0) with ``prior=(y0 (D,), P (D, D))``)
@@ -507,7 +507,20 @@ class MultivariateEmulator(object):
         inside the loop but ``state``, every fourth iteration, to stop when every row has converged; after it,
         ``posterior_cov_device`` on the loop's own arrays.  ``is_gpu=False`` is the explicit numpy branch, the same loop
         from the numpy forms of ``misfit_many`` / ``gauss_newton_many`` and ``_lib.newton_step_numpy``; never a
-        fallback."""
+        fallback.
+
+        ``prior=(x0, P)`` is shared by the rows -- ``x0`` (D,), ``P`` (D, D) -- or per row -- ``x0`` (M, D), ``P`` (M, D, D) --
+        each of the two independently: a prior map, or the propagated posterior of an earlier date.  On the GPU a per-row
+        prior goes up once and the loop calls the ``_rows`` entries (the same kernels with a row stride); a shared prior
+        makes exactly the calls it always made.
+
+        ``next_prior=Q``, a process-noise covariance (D, D) or per row (M, D, D), appends ``next_prec (M, D, D)`` and
+        ``prior_status (M,) int32`` behind everything else: ``next_prec = ((A + P)^-1 + Q)^-1``, the posterior precision
+        relaxed by ``Q``, which with the returned state as its mean is the prior of the next date of a time series
+        (random-walk dynamics).  ``prior_status`` is 0, k + 1 when pivot k of ``A + P`` fails, or D + k + 1 when pivot k of
+        ``(A + P)^-1 + Q`` fails; then the row's ``next_prec`` is NaN.  On the GPU this is one ``prior_propagate_device`` call
+        on the loop's own device arrays after the loop (the covariance in between never leaves the chip); on the numpy
+        branch ``_lib.prior_propagate_numpy``.  With ``None`` nothing changes."""
         from . import _lib, _retrieve
         Y0 = np.asarray(Y0)
         if Y0.ndim != 2:
@@ -517,7 +530,7 @@ class MultivariateEmulator(object):
         if D != self.emulators[0].inputs.shape[1]:
             raise ValueError("Y0 has %d columns, the emulators have %d inputs" % (D, self.emulators[0].inputs.shape[1]))
         _, obs, weights = self._misfit_args(Y0, obs, weights, False)
-        prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D)
+        prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D, M)
         max_iter = int(max_iter)
         per_row = weights is not None and weights.ndim == 2
 
@@ -532,7 +545,8 @@ class MultivariateEmulator(object):
 
             def step(x, g, A, lam):
                 return _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds)
-            return _retrieve.lm_numpy(data_term, step, Y0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov)
+            return _retrieve.lm_numpy(data_term, step, Y0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov,
+                                      next_prior)
 
         dt = np.dtype(precision)
         isz = dt.itemsize
@@ -557,7 +571,15 @@ class MultivariateEmulator(object):
                 else:
                     ctx.mv_gauss_newton_device(dt, d_der, d_G, a, M, P, D)
             return _retrieve.lm_device(scratch, M, D, Y0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                       misfit)
+                                       misfit, next_prior)
+
+    def retrieve_series(self, Y0, obs, weights, prior, noise, **loop_args):
+        """A time series of ``retrieve_many`` on this emulator: ``obs`` (T, N_full) or (T, M, N_full) and ``weights``
+        the same or None, one retrieval per date, the posterior of a date propagated by the process noise ``noise``
+        (D, D) or (M, D, D) into the prior of the next (``_retrieve.retrieve_series``: what it returns, and why
+        ``prior`` is required).  ``loop_args`` are ``retrieve_many``'s other keywords."""
+        from . import _retrieve
+        return _retrieve.retrieve_series(self.retrieve_many, Y0, obs, weights, prior, noise, **loop_args)
 
     # ---- second derivatives ---------------------------------------------------------------------
     def hessian(self, y, is_gpu=False, weights=None):

@@ -276,7 +276,7 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
 
 def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prior=None, bounds=None, lam0=1e-2,
                    max_iter=20, down=1.0 / 3.0, up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64,
-                   device=None, step_fn=None, return_cov=False):
+                   device=None, step_fn=None, return_cov=False, next_prior=None):
     """Levenberg-Marquardt retrieval of M state vectors at once on E per-band emulators: minimises, row by row,
 
         F(x) = 1/2 sum_e w (mu_e(x) - obs[e])^2  (+ 1/2 (x - x0)^T P (x - x0) with ``prior=(x0 (D,), P (D, D))``)
@@ -308,7 +308,20 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     ignored: a component held at its bound gets the unconstrained variance.  ``C`` is a covariance only when
     ``weights`` are the inverse variances of the observations (and ``P`` that of the prior).  On the GPU this is one
     ``posterior_cov_device`` call on the loop's own device arrays after the loop, and only the three results come
-    back; on the numpy branch ``_lib.posterior_cov_numpy`` on the loop's ``A``.  With ``False`` nothing changes."""
+    back; on the numpy branch ``_lib.posterior_cov_numpy`` on the loop's ``A``.  With ``False`` nothing changes.
+
+    ``prior=(x0, P)`` is shared by the rows -- ``x0`` (D,), ``P`` (D, D) -- or per row -- ``x0`` (M, D), ``P`` (M, D, D) --
+    each of the two independently: a prior map, or the propagated posterior of an earlier date.  On the GPU a per-row
+    prior goes up once and the loop calls the ``_rows`` entries (the same kernels with a row stride); a shared prior
+    makes exactly the calls it always made.
+
+    ``next_prior=Q``, a process-noise covariance (D, D) or per row (M, D, D), appends ``next_prec (M, D, D)`` and
+    ``prior_status (M,) int32`` behind everything else: ``next_prec = ((A + P)^-1 + Q)^-1``, the posterior precision
+    relaxed by ``Q``, which with the returned state as its mean is the prior of the next date of a time series
+    (random-walk dynamics).  ``prior_status`` is 0, k + 1 when pivot k of ``A + P`` fails, or D + k + 1 when pivot k of
+    ``(A + P)^-1 + Q`` fails; then the row's ``next_prec`` is NaN.  On the GPU this is one ``prior_propagate_device`` call
+    on the loop's own device arrays after the loop (the covariance in between never leaves the chip); on the numpy
+    branch ``_lib.prior_propagate_numpy``.  With ``None`` nothing changes."""
     if second_order not in ("gauss_newton", "full"):
         raise ValueError("second_order must be 'gauss_newton' or 'full'")
     X0 = np.asarray(X0)
@@ -321,14 +334,14 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     obs = _em_broadcast(obs, E, M, "obs")
     if weights is not None:
         weights = _em_broadcast(weights, E, M, "weights")
-    prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D)
+    prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D, M)
     max_iter = int(max_iter)
 
     if step_fn is not None or not is_gpu:
         step = step_fn if step_fn is not None else (
             lambda x, g, A, lam: _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds))
         return _retrieve.lm_numpy(lambda X: _misfit_numpy(gps, X, obs, weights, second_order, False), step, X0, lam0,
-                                  max_iter, down, up, ftol, xtol, prior, return_cov)
+                                  max_iter, down, up, ftol, xtol, prior, return_cov, next_prior)
 
     ctx = _lib.default_context(device)
     batch = _batch_model(ctx, gps, inputs, precision, False)
@@ -345,9 +358,19 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
                 batch.misfit_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a if second_order == "gauss_newton" else None,
                                     d_hess=a if second_order == "full" else None)
             return _retrieve.lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                       misfit)
+                                       misfit, next_prior)
     finally:
         batch.close()
+
+
+def retrieve_bands_series(gps, X0, obs, weights, prior, noise, **loop_args):
+    """A time series of ``retrieve_bands`` on the emulators ``gps``: ``obs`` (T, E, M) -- or anything ``retrieve_bands``
+    takes, per date -- and ``weights`` the same or None, one retrieval per date, the posterior of a date propagated by
+    the process noise ``noise`` (D, D) or (M, D, D) into the prior of the next (``_retrieve.retrieve_series``: what it
+    returns, and why ``prior`` is required).  ``loop_args`` are ``retrieve_bands``' other keywords."""
+    def retrieve(X, obs_t, weights_t, **kw):
+        return retrieve_bands(gps, X, obs_t, weights_t, **kw)
+    return _retrieve.retrieve_series(retrieve, X0, obs, weights, prior, noise, **loop_args)
 
 
 # ---------------------------------------------------------------------------------------------

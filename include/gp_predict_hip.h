@@ -416,6 +416,23 @@ int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, 
                         double lambda_min, double lambda_max, double ftol, double xtol,
                         int64_t n_rows, int n_inputs);
 
+/* The two entries above with a prior per row (a prior map, or the propagated posterior of an earlier acquisition).
+ * prior_mean_stride and prior_prec_stride are in elements of `dtype`: 0 is one x0 [D] / one P [D][D] for all rows
+ * (then the call IS the entry above, bit for bit); otherwise row m reads d_prior_mean + m * prior_mean_stride
+ * (stride >= n_inputs) and d_prior_prec + m * prior_prec_stride (stride >= n_inputs^2).  The two strides are
+ * independent: per-row means with one shared precision is a valid call.  Any other stride, or a non-zero stride
+ * with a NULL pointer, is GP_ERR_INVALID.  The same kernels: the arithmetic and its order do not change. */
+int gp_newton_step_rows_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
+                               const void* d_lambda, int damping, const void* d_prior_mean, const void* d_prior_prec,
+                               const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
+                               int64_t n_rows, int n_inputs, int64_t prior_mean_stride, int64_t prior_prec_stride);
+int gp_lm_update_rows_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost,
+                             const void* d_cost_trial, void* d_grad, const void* d_grad_trial, void* d_A,
+                             const void* d_A_trial, void* d_lambda, const int32_t* d_status, int32_t* d_state,
+                             int32_t* d_accepted, const void* d_prior_mean, const void* d_prior_prec, double down,
+                             double up, double lambda_min, double lambda_max, double ftol, double xtol,
+                             int64_t n_rows, int n_inputs, int64_t prior_mean_stride, int64_t prior_prec_stride);
+
 /* ---- posterior covariance ----------------------------------------------------------------------------
  * The inverse of the matrix the Newton step factors, without the damping: what a retrieval reports beside its
  * state as x +- sigma, from the d_A (and prior precision) that the loop above leaves on the device.  For each of
@@ -440,6 +457,37 @@ int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, 
  * 1 <= n_inputs <= 32 (GP_ERR_UNSUPPORTED beyond). */
 int gp_posterior_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec,
                             void* d_cov, void* d_sigma, int32_t* d_status, int64_t n_rows, int n_inputs);
+/* The same with a prior precision per row: row m reads d_prior_prec + m * prior_prec_stride elements; 0 is one P for
+ * all rows (then the call IS the entry above), otherwise the stride is >= n_inputs^2.  Any other stride, or a
+ * non-zero stride with a NULL d_prior_prec, is GP_ERR_INVALID. */
+int gp_posterior_cov_rows_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec,
+                                 void* d_cov, void* d_sigma, int32_t* d_status, int64_t n_rows, int n_inputs,
+                                 int64_t prior_prec_stride);
+
+/* ---- prior propagation -------------------------------------------------------------------------------
+ * The posterior of one acquisition, relaxed by a process noise, as the prior precision of the next: the step
+ * between the dates of a time series of retrievals (random-walk dynamics: the next prior MEAN is the retrieved
+ * state itself).  For each of n_rows rows, D = n_inputs,
+ *   A' = A[m] (+ P[m])                   d_A [n_rows][D][D];  d_prior_prec NULL, one P [D][D] (stride 0) or row m's at
+ *                                        m * prior_prec_stride elements; lower triangles read; NO damping
+ *   C  = A'^-1                           gp_posterior_cov_device's factorisation and unit-vector solves
+ *   S  = C + Q[m]                        d_noise, the process-noise covariance: one Q [D][D] (stride 0) or row m's at
+ *                                        m * noise_stride elements; required; lower triangle read
+ *   N  = S^-1                            the same factorisation and solves again
+ *   next_prec[m] = N                     d_next_prec [n_rows][D][D]: elements i >= j from column j's solve, the upper
+ *                                        triangle mirrored from them, so next_prec[m] is symmetric bit for bit
+ *   status[m] = 0; k + 1 when pivot k (0-based) of A' is not > 0 or not finite; D + k + 1 when pivot k of S is; then
+ *                                        every element of next_prec[m] is a quiet NaN
+ * Everything runs in double in both precisions: C is never rounded to `dtype` and never leaves the chip (two
+ * gp_posterior_cov_device calls would round it in between, and write and re-read it); next_prec is rounded to
+ * `dtype` once on store.  Every sum is the covariance entry's fma chain.  No atomics: a row's result does not
+ * depend on the other rows, on its place in the call or on the grid, and two calls agree bit for bit.
+ * Strides are 0 or >= n_inputs^2 (GP_ERR_INVALID otherwise, and for a non-zero stride with a NULL pointer).
+ * Device pointers of `dtype` (d_status int32), asynchronous on the context's stream; n_rows > 0,
+ * 1 <= n_inputs <= 32 (GP_ERR_UNSUPPORTED beyond). */
+int gp_prior_propagate_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec,
+                              int64_t prior_prec_stride, const void* d_noise, int64_t noise_stride,
+                              void* d_next_prec, int32_t* d_status, int64_t n_rows, int n_inputs);
 
 /* ---- training objective (next after the predict path: SURVEY.md 8f rank 2) -------------------
  * For each of n_sets hyper-parameter vectors theta [n_sets][n_inputs+2]: what

@@ -5,6 +5,7 @@ retrieve_bands iteration against its misfit_device alone.  Prints one JSON line 
 
     python tools/newton_step_timing.py [--legs device,host,iteration] [--out FILE] [--reps 20] [--warmup 5]
     python tools/newton_step_timing.py --legs posterior [--out FILE] [--reps 50] [--warmup 5]
+    python tools/newton_step_timing.py --legs rows,propagate [--shared-only] [--out FILE]
     python tools/newton_step_timing.py --legs registers        # no GPU: compiles csrc/gp_newton_tu.hip once
 
 device     gp_newton_step_device at M = 1e5 rows, D in {11, 16}, both dtypes, trial and status out: the median of
@@ -21,6 +22,15 @@ posterior  gp_posterior_cov_device (cov, sigma and status out) beside gp_newton_
            inside one loop, each between its own pair of events, so that both see the same machine; per entry the
            median, the minimum and the maximum of --reps calls after --warmup of each, and the ratio of the medians
            (profiles/r10_posterior_cov.txt quotes such a run's lines).
+rows       the step (trial and status out), the update (every row accepting) and the covariance (cov, sigma, status out)
+           with a prior, shared by the rows through the plain entries against per row through the _rows entries:
+           M = 1e5, D in {11, 16}, both dtypes.  The two forms of an entry alternate inside one loop, each call between
+           its own pair of events; per form the median, minimum and maximum of --reps calls after --warmup.  With
+           --shared-only only the plain entries are called, so the same file also times a checkout from before the
+           _rows entries (profiles/r12_row_prior.txt compares the two that way).
+propagate  gp_prior_propagate_device (next_prec and status out) against the two gp_posterior_cov_device launches it
+           replaces -- (A + P)^-1 to a covariance array, then that array with Q in the prior's place -- the pair between
+           one pair of events; shared P and Q, and per-row P and Q for the one kernel.  Same rows, same alternation.
 
 Every leg that touches the GPU runs under the caller's time limit, e.g.
     timeout -k 10 300 python tools/newton_step_timing.py --legs device,host,iteration --out profiles/r09_newton_step.txt
@@ -189,6 +199,123 @@ def leg_posterior(a):
                 ctx.free(p)
 
 
+def timed_alternating(ctx, calls, a, before=None):
+    """{name: [ms, ...]} of the calls taken in turn inside one loop, each between its own pair of events."""
+    t = {k: [] for k in calls}
+    e0, e1 = ctx.event(), ctx.event()
+    for i in range(a.warmup + a.reps):
+        for name, fn in calls.items():
+            if before:
+                before()
+            ctx.record(e0)
+            fn()
+            ctx.record(e1)
+            ctx.synchronize()
+            if i >= a.warmup:
+                t[name].append(ctx.elapsed_ms(e0, e1))
+    ctx.event_destroy(e0)
+    ctx.event_destroy(e1)
+    return t
+
+
+def stats(t):
+    return dict(ms=round(float(np.median(t)), 4), ms_min=round(min(t), 4), ms_max=round(max(t), 4))
+
+
+def priors(D, dt, seed=0):
+    """A shared prior (x0, P) on the matrices' scale and its per-row form: P[m] = u_m P, x0[m] = x0 + delta_m."""
+    rs = np.random.RandomState(100 + seed + D)
+    B = rs.standard_normal((D + 2, D))
+    x0, P = rs.random_sample(D), B.T @ B
+    rows = ((x0 + 0.1 * rs.uniform(-1.0, 1.0, (M, D))).astype(dt), (rs.uniform(0.5, 2.0, M)[:, None, None] * P).astype(dt))
+    return (x0.astype(dt), P.astype(dt)), rows
+
+
+def leg_rows(a):
+    ctx = _lib.default_context(0)
+    for D in (11, 16):
+        for prec in (np.float64, np.float32):
+            dt = np.dtype(prec)
+            isz = dt.itemsize
+            x, g, A, lam = systems(D, dt)
+            shared, rows = priors(D, dt)
+            d_x, d_g, d_A, d_lam = (ctx.to_device(v) for v in (x, g, A, lam))
+            d_g2, d_A2 = ctx.to_device(g), ctx.to_device(A)
+            d_x0, d_P = (ctx.to_device(v) for v in shared)
+            d_x0r, d_Pr = (ctx.to_device(v) for v in rows) if not a.shared_only else (None, None)
+            d_trial, d_status, d_state = ctx.malloc(M * D * isz), ctx.malloc(M * 4), ctx.to_device(np.zeros(M, np.int32))
+            d_cost, d_cost_t = ctx.to_device(np.full(M, 2e6, dt)), ctx.to_device(np.full(M, 1.0, dt))
+            d_cov, d_sigma, d_cstat = ctx.malloc(M * D * D * isz), ctx.malloc(M * D * isz), ctx.malloc(M * 4)
+            big = np.full(M, 2e6, dt)
+            step = dict(shared=lambda: ctx.newton_step_device(dt, d_x, d_g, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal",
+                                                              d_x0, d_P))
+            cov = dict(shared=lambda: ctx.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_cstat, M, D))
+            # the update with every row accepting: after the first call x is the trial, so the two prior terms are equal
+            # and the reset cost stays above the trial's (ftol = 0, xtol < 0: no row ever converges)
+            update = dict(shared=lambda: ctx.lm_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_g, d_g2, d_A, d_A2, d_lam,
+                                                              d_status, d_state, None, M, D, d_x0, d_P, ftol=0.0, xtol=-1.0))
+            if not a.shared_only:
+                step["rows"] = lambda: ctx.newton_step_rows_device(dt, d_x, d_g, d_A, d_lam, None, d_trial, d_status, M, D,
+                                                                   "diagonal", d_x0r, d_Pr, None, None, D, D * D)
+                cov["rows"] = lambda: ctx.posterior_cov_rows_device(dt, d_A, d_Pr, d_cov, d_sigma, d_cstat, M, D, D * D)
+                update["rows"] = lambda: ctx.lm_update_rows_device(dt, d_x, d_trial, d_cost, d_cost_t, d_g, d_g2, d_A, d_A2, d_lam,
+                                                                   d_status, d_state, None, M, D, d_x0r, d_Pr, ftol=0.0, xtol=-1.0,
+                                                                   prior_mean_stride=D, prior_prec_stride=D * D)
+            t_step = timed_alternating(ctx, step, a)
+            failed = int(np.count_nonzero(ctx.to_host(d_status, (M,), np.int32)))
+            t_cov = timed_alternating(ctx, cov, a)
+            ctx.h2d(d_status, np.zeros(M, np.int32))
+            t_update = timed_alternating(ctx, update, a, before=lambda: ctx.h2d(d_cost, big))
+            for entry, t in (("newton_step", t_step), ("lm_update_all_accept", t_update), ("posterior_cov", t_cov)):
+                row = dict(leg="rows", entry=entry, dtype=dt.name, rows=M, D=D, reps=a.reps)
+                for form, ts in t.items():
+                    row.update({"%s_%s" % (form, k): v for k, v in stats(ts).items()})
+                if "rows" in t:
+                    row["rows_over_shared"] = round(float(np.median(t["rows"]) / np.median(t["shared"])), 3)
+                if entry == "newton_step":
+                    row["rows_failed"] = failed
+                emit(a, **row)
+            for p in (d_x, d_g, d_A, d_lam, d_g2, d_A2, d_x0, d_P, d_x0r, d_Pr, d_trial, d_status, d_state, d_cost, d_cost_t, d_cov,
+                      d_sigma, d_cstat):
+                if p is not None:
+                    ctx.free(p)
+
+
+def leg_propagate(a):
+    ctx = _lib.default_context(0)
+    for D in (11, 16):
+        for prec in (np.float64, np.float32):
+            dt = np.dtype(prec)
+            isz = dt.itemsize
+            _, _, A, _ = systems(D, dt)
+            shared, rows = priors(D, dt)
+            rs = np.random.RandomState(7 + D)
+            B = rs.standard_normal((D + 2, D))
+            Q = (1e-3 * (B.T @ B)).astype(dt)                   # on the covariance's scale: C ~ 1 / (D + 8)
+            Qr = (rs.uniform(0.5, 2.0, M)[:, None, None] * Q).astype(dt)
+            d_A, d_P, d_Pr, d_Q, d_Qr = (ctx.to_device(v) for v in (A, shared[1], rows[1], Q, Qr))
+            d_cov, d_next = ctx.malloc(M * D * D * isz), ctx.malloc(M * D * D * isz)
+            d_s1, d_s2 = ctx.malloc(M * 4), ctx.malloc(M * 4)
+
+            def two():
+                ctx.posterior_cov_device(dt, d_A, d_P, d_cov, None, d_s1, M, D)
+                ctx.posterior_cov_device(dt, d_cov, d_Q, d_next, None, d_s2, M, D)
+            calls = dict(two_launches=two,
+                         fused=lambda: ctx.prior_propagate_device(dt, d_A, d_P, 0, d_Q, 0, d_next, d_s2, M, D),
+                         fused_rows=lambda: ctx.prior_propagate_device(dt, d_A, d_Pr, D * D, d_Qr, D * D, d_next, d_s2, M, D))
+            t = timed_alternating(ctx, calls, a)
+            failed = int(np.count_nonzero(ctx.to_host(d_s2, (M,), np.int32)))
+            nbytes = 2 * M * D * D * isz                        # A in, next_prec out (shared P and Q; status not counted)
+            row = dict(leg="propagate", dtype=dt.name, rows=M, D=D, reps=a.reps, rows_failed=failed, MB=round(nbytes / 1e6, 1))
+            for form, ts in t.items():
+                row.update({"%s_%s" % (form, k): v for k, v in stats(ts).items()})
+            row["fused_GB_per_s"] = round(nbytes / (np.median(t["fused"]) * 1e-3) / 1e9, 1)
+            row["fused_over_two_launches"] = round(float(np.median(t["fused"]) / np.median(t["two_launches"])), 3)
+            emit(a, **row)
+            for p in (d_A, d_P, d_Pr, d_Q, d_Qr, d_cov, d_next, d_s1, d_s2):
+                ctx.free(p)
+
+
 def leg_iteration(a):
     N, D, E = 250, 11, 12
     ctx = _lib.default_context(0)
@@ -252,7 +379,7 @@ def leg_registers(a):
             continue
         if m.group(1) == "Function Name":
             flush()
-            t = re.search(r"\d+(newton_step_kernel|lm_update_kernel|posterior_cov_kernel)I([fd])E", m.group(2))
+            t = re.search(r"\d+(newton_step_kernel|lm_update_kernel|posterior_cov_kernel|prior_propagate_kernel)I([fd])E", m.group(2))
             name = "%s<%s>" % (t.group(1), {"f": "float", "d": "double"}[t.group(2)]) if t else m.group(2)
             row = {}
         else:
@@ -265,7 +392,8 @@ def leg_registers(a):
     for D in (11, 16, 32):          # gp_posterior_cov_kernel.hpp: post_cov_rows_per_wg, two triangles per row
         rows, tri = (8 if D <= 16 else 4), D * (D + 1) // 2
         pitch = tri + (16 - tri % 32) % 32
-        print("dynamic LDS of posterior_cov_kernel at D = %d: %d rows x 2 x %d doubles = %d bytes per workgroup" % (D, rows, pitch, rows * 2 * pitch * 8))
+        print("dynamic LDS of posterior_cov_kernel and prior_propagate_kernel at D = %d: %d rows x 2 x %d doubles = %d bytes per workgroup"
+              % (D, rows, pitch, rows * 2 * pitch * 8))
 
 
 if __name__ == "__main__":
@@ -274,6 +402,7 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--shared-only", action="store_true", help="rows leg: the plain entries only (also runs on a checkout without the _rows entries)")
     a = ap.parse_args()
     legs = a.legs.split(",")
     if "registers" in legs:
@@ -284,3 +413,7 @@ if __name__ == "__main__":
         leg_iteration(a)
     if "posterior" in legs:
         leg_posterior(a)
+    if "rows" in legs:
+        leg_rows(a)
+    if "propagate" in legs:
+        leg_propagate(a)
