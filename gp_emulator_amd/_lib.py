@@ -76,6 +76,7 @@ SIGNATURES = {
     "gp_lm_update_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 14 + [ctypes.c_double] * 6 + [c_i64, c_int, c_i64, c_i64]),
     "gp_posterior_cov_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_i64, c_int, c_i64]),
     "gp_prior_propagate_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int]),
+    "gp_rts_smooth_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 9 + [c_i64, c_int]),
     "gp_hessian_f64": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_hessian_f32": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_reconstruct_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
@@ -458,6 +459,63 @@ def prior_propagate_numpy(A, prior_prec, noise):
     return np.tril(W) + np.transpose(np.tril(W, -1), (0, 2, 1)), status
 
 
+def _mirror_lower(W):
+    """The symmetric matrices whose lower triangles are those of ``W`` (M, D, D)."""
+    return np.tril(W) + np.transpose(np.tril(W, -1), (0, 2, 1))
+
+
+def rts_smooth_numpy(A, prior_prec, noise, x, x_next, cov_next, bounds=None):
+    """One backward step of the Rauch-Tung-Striebel smoother of ``gp_rts_smooth_device`` in float64 numpy, in the
+    kernel's summation order: ``(x_smooth (M, D), cov_smooth (M, D, D), sigma_smooth (M, D), status (M,) int32)``.  The
+    explicit CPU branch of ``Context.rts_smooth`` and of the series' ``smooth=True``, and the reference of the CPU
+    tests; never a fallback.
+
+        A' = A (+ P),  C = A'^-1,  S = C + Q,  N = S^-1 as ``prior_propagate_numpy``,  G = C N,
+        x_smooth = clip(x + G (x_next - x), lo, hi),  Delta = cov_next - S,  cov_smooth = C + (G Delta) G^T (the lower
+        triangle computed, the upper mirrored),  sigma_smooth = sqrt(diag cov_smooth);  every product a sum from 0 in
+        ascending index;  status = k + 1 when pivot k of A' fails, D + k + 1 when pivot k of S fails, then the row's
+        outputs are NaN.
+
+    ``prior_prec`` is None, ``(D, D)`` or ``(M, D, D)``; ``noise`` ``(D, D)`` or ``(M, D, D)``; ``x`` the filtered
+    states of the date, ``x_next`` and ``cov_next`` the smoothed state and covariance of the next date;
+    ``bounds=(lo (D,), hi (D,))``.  Only the lower triangles of the matrices are read."""
+    L = np.array(A, dtype=np.float64)
+    if L.ndim != 3 or L.shape[1] != L.shape[2]:
+        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+    M, D = L.shape[:2]
+    x = np.asarray(x, dtype=np.float64).reshape(M, D)
+    d = np.asarray(x_next, dtype=np.float64).reshape(M, D) - x
+    if prior_prec is not None:
+        L = L + prec_rows(prior_prec, M, D)
+    Cw, first = _cholesky_inverse_numpy(L)
+    with np.errstate(all="ignore"):
+        S = Cw + prec_rows(noise, M, D)                              # (NaN where the first inversion failed)
+        Delta = _mirror_lower(np.asarray(cov_next, dtype=np.float64).reshape(M, D, D) - S)
+    Nw, second = _cholesky_inverse_numpy(S)                          # (factors S in place: Delta is taken first)
+    status = np.where(first != 0, first, np.where(second != 0, D + second, 0)).astype(np.int32)
+    with np.errstate(all="ignore"):
+        C, N = _mirror_lower(Cw), _mirror_lower(Nw)
+        G, F, K = np.zeros((M, D, D)), np.zeros((M, D, D)), np.zeros((M, D, D))
+        gd = np.zeros((M, D))
+        for k in range(D):
+            G += C[:, :, k, None] * N[:, None, k, :]
+        for c in range(D):
+            gd += G[:, :, c] * d[:, c, None]
+        for l in range(D):
+            F += G[:, :, l, None] * Delta[:, None, l, :]
+        for k in range(D):
+            K += F[:, :, k, None] * G[:, None, :, k]                 # K_ij += F_ik G_jk
+        xs = x + gd
+        if bounds is not None:
+            xs = np.minimum(np.maximum(xs, np.asarray(bounds[0], dtype=np.float64)), np.asarray(bounds[1], dtype=np.float64))
+        cov = _mirror_lower(C + K)
+        idx = np.arange(D)
+        sigma = np.sqrt(cov[:, idx, idx])
+    bad = status != 0
+    xs[bad], cov[bad], sigma[bad] = np.nan, np.nan, np.nan
+    return xs, cov, sigma, status
+
+
 class Context:
     """One device + one HIP stream (gp_ctx).  Use one per thread / per GPU."""
 
@@ -685,6 +743,55 @@ class Context:
             self.prior_propagate_device(dt, ptrs[0], ptrs[1], row_strides(None, P)[1], ptrs[2], row_strides(None, Q)[1],
                                         d_next, d_status, M, D)
             return np.array(self.to_host(d_next, (M, D, D), dt)), np.array(self.to_host(d_status, (M,), np.int32))
+        finally:
+            for p in ptrs:
+                if p is not None:
+                    self.free(p)
+
+    def rts_smooth_device(self, dtype, d_A, d_prior_prec, prior_prec_stride, d_noise, noise_stride, d_x, d_x_next,
+                          d_cov_next, d_lo, d_hi, d_x_smooth, d_cov_smooth, d_sigma_smooth, d_status, n_rows, n_inputs):
+        """Asynchronous backward step of the Rauch-Tung-Striebel smoother for ``n_rows`` systems on the device
+        (``gp_rts_smooth_device``): with ``C = (A + P)^-1``, ``S = C + Q`` and the gain ``G = C S^-1``,
+        ``x_smooth = clamp(x + G (x_next - x))`` and ``cov_smooth = C + G (cov_next - S) G^T`` row by row in one kernel,
+        ``sigma_smooth`` the square roots of its diagonal, ``status`` as ``prior_propagate_device``'s (then the row's
+        outputs are NaN).  Device pointers of ``dtype``; ``d_prior_prec``, the ``d_lo`` / ``d_hi`` pair and one of
+        ``d_cov_smooth`` / ``d_sigma_smooth`` may be None; the strides are in elements, 0 = one matrix for all rows."""
+        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+        check(self.lib.gp_rts_smooth_device(self.h, code, d_A, d_prior_prec, int(prior_prec_stride), d_noise,
+                                            int(noise_stride), d_x, d_x_next, d_cov_next, d_lo, d_hi, d_x_smooth,
+                                            d_cov_smooth, d_sigma_smooth, d_status, int(n_rows), int(n_inputs)),
+              "gp_rts_smooth_device")
+
+    def rts_smooth(self, A, prior_prec, noise, x, x_next, cov_next, bounds=None, precision=None, is_gpu=True):
+        """``(x_smooth (M, D), cov_smooth (M, D, D), sigma_smooth (M, D), status (M,) int32)`` of one backward step of
+        the Rauch-Tung-Striebel smoother for the host arrays ``A`` (M, D, D), ``prior_prec`` None, (D, D) or
+        (M, D, D), ``noise`` (D, D) or (M, D, D), the filtered states ``x`` (M, D) and the next date's smoothed
+        ``x_next`` (M, D) and ``cov_next`` (M, D, D): uploads, launches ``gp_rts_smooth_device``, downloads.
+        ``precision`` is the device dtype (default: float32 when ``A`` is float32, else float64).  ``is_gpu=False`` is
+        the explicit numpy branch (``rts_smooth_numpy``: the same algorithm in float64); never a fallback."""
+        if not is_gpu:
+            return rts_smooth_numpy(A, prior_prec, noise, x, x_next, cov_next, bounds)
+        A = np.asarray(A)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+        dt = np.dtype(precision if precision is not None else (np.float32 if A.dtype == np.float32 else np.float64))
+        M, D = A.shape[:2]
+        P = prec_rows(prior_prec, M, D, dt) if prior_prec is not None else None
+        Q = prec_rows(noise, M, D, dt)
+        ins = [A, P, Q, np.reshape(x, (M, D)), np.reshape(x_next, (M, D)), np.reshape(cov_next, (M, D, D))]
+        ins += [np.reshape(b, D) for b in bounds] if bounds is not None else [None, None]
+        ptrs = []
+        try:
+            for a in ins:
+                ptrs.append(self.to_device(np.ascontiguousarray(a, dtype=dt)) if a is not None else None)
+            isz = dt.itemsize
+            d_xs, d_cov, d_sigma, d_status = (self.malloc(M * D * isz), self.malloc(M * D * D * isz),
+                                              self.malloc(M * D * isz), self.malloc(M * 4))
+            ptrs += [d_xs, d_cov, d_sigma, d_status]
+            self.rts_smooth_device(dt, ptrs[0], ptrs[1], row_strides(None, P)[1], ptrs[2], row_strides(None, Q)[1],
+                                   ptrs[3], ptrs[4], ptrs[5], ptrs[6], ptrs[7], d_xs, d_cov, d_sigma, d_status, M, D)
+            return (np.array(self.to_host(d_xs, (M, D), dt)), np.array(self.to_host(d_cov, (M, D, D), dt)),
+                    np.array(self.to_host(d_sigma, (M, D), dt)), np.array(self.to_host(d_status, (M,), np.int32)))
         finally:
             for p in ptrs:
                 if p is not None:

@@ -52,11 +52,12 @@ def prior_and_bounds(prior, bounds, D, M=1):
     return prior, bounds
 
 
-def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov, next_prior=None):
+def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov, next_prior=None, return_A=False):
     """The loop on the host in float64: ``data_term(X) -> (cost, grad, A)``, ``step(x, grad, A, lam) -> (step, trial,
     status)``.  Returns ``(X, cost, state, n_accepted, lam)``, with ``return_cov`` ``_lib.posterior_cov_numpy``'s
     three of the loop's ``A`` behind them, and with a process noise ``next_prior`` ``_lib.prior_propagate_numpy``'s
-    two behind those."""
+    two behind those; ``return_A`` appends the loop's final data-term matrix ``A (M, D, D)`` as the last element (what
+    the smoother of a series needs of a date)."""
     M = X0.shape[0]
     X = np.array(X0, dtype=np.float64)
     lam = np.full(M, float(lam0))
@@ -75,6 +76,8 @@ def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, r
         out += _lib.posterior_cov_numpy(A, prior[1] if prior is not None else None)
     if next_prior is not None:
         out += _lib.prior_propagate_numpy(A, prior[1] if prior is not None else None, next_prior)
+    if return_A:
+        out += (A,)
     return out
 
 
@@ -102,7 +105,8 @@ class Scratch(object):
             self.ctx.free(p)
 
 
-def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov, misfit, next_prior=None):
+def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov, misfit, next_prior=None,
+              return_A=False):
     """The loop on the device from the host rows ``X0``, in the precision and on the context of ``scratch`` (the
     caller's ``Scratch``, which also holds whatever ``misfit`` reads).  ``misfit(d_rows, d_cost, d_grad, d_A)`` enqueues
     the data term at ``d_rows`` on the context's stream.  Every iteration is that, ``lm_update_device`` and
@@ -110,8 +114,8 @@ def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, 
     row has converged.  With a per-row prior -- ``x0`` (M, D) or ``P`` (M, D, D) -- the two are the ``_rows`` entries
     with the arrays' row strides; with a shared or absent prior the calls are exactly the plain ones.  A process noise
     ``next_prior`` (D, D) or (M, D, D) adds one ``prior_propagate_device`` call after the loop (and after the
-    covariance) on the loop's own ``d_A`` and ``d_P``.  Returns what ``lm_numpy`` returns, in the scratch's
-    precision."""
+    covariance) on the loop's own ``d_A`` and ``d_P``; ``return_A`` adds one download, of ``d_A``, behind everything
+    else.  Returns what ``lm_numpy`` returns, in the scratch's precision."""
     ctx, dt = scratch.ctx, scratch.dt
     up_, alloc, isz = scratch.up, scratch.alloc, dt.itemsize
     d_x, d_lam = up_(X0), up_(np.full(M, float(lam0)))
@@ -170,10 +174,59 @@ def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, 
         ctx.prior_propagate_device(dt, d_A, d_P, strides[1], d_Q, _lib.row_strides(None, Q)[1], d_next, d_pstat, M, D)
         ctx.synchronize()
         out += (np.array(ctx.to_host(d_next, (M, D, D), dt)), np.array(ctx.to_host(d_pstat, (M,), np.int32)))
+    if return_A:
+        out += (np.array(ctx.to_host(d_A, (M, D, D), dt)),)
     return out
 
 
-def retrieve_series(retrieve, X0, obs, weights, prior, noise, **loop_args):
+def smooth_numpy(A, P, noise, X, cov_last, sigma_last, bounds):
+    """The backward pass of a series on the host: ``_lib.rts_smooth_numpy`` for t = T-2 .. 0 on the dates' ``A[t]``,
+    ``P[t]`` and filtered states ``X[t]``, started from the last date's state and covariance.  Returns ``(X_s (T, M, D),
+    sigma_s (T, M, D), status (T, M) int32)``; the last date's are the filtered ones and zeros."""
+    T = len(A)
+    xs, cov = np.asarray(X[T - 1], dtype=np.float64), cov_last
+    keep = [(xs, np.asarray(sigma_last, dtype=np.float64), np.zeros(xs.shape[0], np.int32))]
+    for t in range(T - 2, -1, -1):
+        xs, cov, sig, status = _lib.rts_smooth_numpy(A[t], P[t], noise, X[t], xs, cov, bounds)
+        keep.append((xs, sig, status))
+    return tuple(np.stack(a) for a in zip(*keep[::-1]))
+
+
+def smooth_device(ctx, dt, A, P, noise, X, cov_last, sigma_last, bounds):
+    """The backward pass of a series on the device in the precision ``dt``: one ``rts_smooth_device`` call per date,
+    t = T-2 .. 0.  The smoothed state and covariance of date t + 1 stay on the device: two buffer pairs take turns as
+    the call's input and output.  The noise and the bounds go up once; per date only ``A[t]``, ``P[t]`` and ``X[t]`` go
+    up and only the smoothed state, its sigma and the status come down.  Returns what ``smooth_numpy`` returns, in
+    ``dt``."""
+    T = len(A)
+    M, D = np.shape(X[T - 1])
+    isz = dt.itemsize
+    keep = [(np.array(X[T - 1], dtype=dt), np.array(sigma_last, dtype=dt), np.zeros(M, np.int32))]
+    if T == 1:
+        return tuple(np.stack(a) for a in zip(*keep))
+    with Scratch(ctx, dt) as scratch:
+        up_, alloc = scratch.up, scratch.alloc
+        Q = _lib.prec_rows(noise, M, D)
+        d_Q, q_stride = up_(Q), _lib.row_strides(None, Q)[1]
+        d_lo, d_hi = (up_(bounds[0]), up_(bounds[1])) if bounds is not None else (None, None)
+        d_A, d_P, d_x = alloc(M * D * D * isz), alloc(M * D * D * isz), alloc(M * D * isz)
+        pairs = [(up_(X[T - 1]), up_(cov_last)), (alloc(M * D * isz), alloc(M * D * D * isz))]
+        d_sigma, d_status = alloc(M * D * isz), alloc(M * 4)
+        for n, t in enumerate(range(T - 2, -1, -1)):
+            nxt, cur = pairs[n % 2], pairs[(n + 1) % 2]
+            Pt = _lib.prec_rows(P[t], M, D, dt)
+            ctx.h2d(d_A, np.ascontiguousarray(A[t], dtype=dt))
+            ctx.h2d(d_P, Pt)
+            ctx.h2d(d_x, np.ascontiguousarray(X[t], dtype=dt))
+            ctx.rts_smooth_device(dt, d_A, d_P, _lib.row_strides(None, Pt)[1], d_Q, q_stride, d_x, nxt[0], nxt[1], d_lo, d_hi,
+                                  cur[0], cur[1], d_sigma, d_status, M, D)
+            ctx.synchronize()
+            keep.append((np.array(ctx.to_host(cur[0], (M, D), dt)), np.array(ctx.to_host(d_sigma, (M, D), dt)),
+                         np.array(ctx.to_host(d_status, (M,), np.int32))))
+    return tuple(np.stack(a) for a in zip(*keep[::-1]))
+
+
+def retrieve_series(retrieve, X0, obs, weights, prior, noise, smooth=False, context=None, **loop_args):
     """A time series of retrievals, date after date, each date's posterior the next date's prior (random-walk
     dynamics: the next prior mean is the retrieved state, the next prior precision ``((A + P)^-1 + Q)^-1`` with the
     process noise ``Q = noise`` (D, D) or (M, D, D)).  ``retrieve(X0, obs, weights, prior=, return_cov=, next_prior=,
@@ -184,7 +237,19 @@ def retrieve_series(retrieve, X0, obs, weights, prior, noise, **loop_args):
 
     Returns ``(X (T, M, D), sigma (T, M, D), cost (T, M), state (T, M), cov_status (T, M), prior_status (T, M),
     next_prec (M, D, D))``, the last the prior precision for the date after the series.  A host loop over the dates:
-    the state goes down and up once per date."""
+    the state goes down and up once per date.
+
+    That is a forward filter: date t has seen the observations up to t only.  ``smooth=True`` adds the fixed-interval
+    (Rauch-Tung-Striebel) backward pass over the filtered posteriors and appends ``X_s (T, M, D)``, ``sigma_s
+    (T, M, D)`` and ``smooth_status (T, M) int32`` to the seven: for t = T-2 .. 0, with ``C = (A[t] + P[t])^-1``,
+    ``S = C + Q`` and ``G = C S^-1``, ``X_s[t] = X[t] + G (X_s[t + 1] - X[t])`` (clamped to the series' ``bounds``) and
+    ``C_s[t] = C + G (C_s[t + 1] - S) G^T``, ``sigma_s[t]`` the square roots of its diagonal; the last date's are the
+    filtered ones and its status zeros; a status is ``prior_status``' code of that date's two inversions, and then the
+    row's smoothed values are NaN.  The forward pass then also keeps, per date, the loop's matrix ``A[t]`` (the
+    retrievals' ``return_A=True``) and the prior precision ``P[t]`` the date was retrieved with, and the last date's
+    covariance; the first seven values are those of ``smooth=False``.  ``context`` is a callable that returns the
+    ``_lib.Context`` of the forward pass: the backward pass is then ``smooth_device`` in ``loop_args``' precision;
+    with ``None`` it is ``smooth_numpy``, the explicit host branch.  With ``smooth=False`` nothing changes."""
     if prior is None:
         raise ValueError("a series needs a prior")
     T = len(obs)
@@ -192,14 +257,26 @@ def retrieve_series(retrieve, X0, obs, weights, prior, noise, **loop_args):
         raise ValueError("obs has no dates")
     if weights is not None and len(weights) != T:
         raise ValueError("obs has %d dates, weights %d" % (T, len(weights)))
-    for name in ("prior", "return_cov", "next_prior"):
+    for name in ("prior", "return_cov", "next_prior") + (("return_A",) if smooth else ()):
         if name in loop_args:
             raise ValueError("%s is the series' own argument" % name)
-    X, keep, next_prec = X0, [], None
+    more = dict(return_A=True) if smooth else {}
+    X, keep, next_prec, mats, cov = X0, [], None, [], None
     for t in range(T):
         out = retrieve(X, obs[t], weights[t] if weights is not None else None, prior=prior, return_cov=True,
-                       next_prior=noise, **loop_args)
+                       next_prior=noise, **dict(loop_args, **more))
+        if smooth:
+            mats.append((out[10], prior[1]))
+            cov = out[5]
         X, next_prec = out[0], out[8]
         keep.append((X, out[6], out[1], out[2], out[7], out[9]))
         prior = (X, next_prec)
-    return tuple(np.stack(a) for a in zip(*keep)) + (next_prec,)
+    result = tuple(np.stack(a) for a in zip(*keep)) + (next_prec,)
+    if not smooth:
+        return result
+    A, P = zip(*mats)
+    bounds = loop_args.get("bounds")
+    if context is None:
+        return result + smooth_numpy(A, P, noise, result[0], cov, result[1][T - 1], bounds)
+    dt = np.dtype(loop_args.get("precision", np.float64))
+    return result + smooth_device(context(), dt, A, P, noise, result[0], cov, result[1][T - 1], bounds)

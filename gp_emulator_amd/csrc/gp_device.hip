@@ -12,6 +12,7 @@
 #include "gp_posterior_cov_kernel.hpp"
 #include "gp_prior_propagate_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
+#include "gp_rts_smooth_kernel.hpp"
 
 // The per-size launchers by their run-time size: one switch over the compiled NK, one over the compiled NB.
 template <typename T>
@@ -537,6 +538,49 @@ int gp_prior_propagate_device(gp_ctx* ctx, int dtype, const void* d_A, const voi
     a.d = n_inputs;
     hipError_t e = gpk::launch_prior_propagate<T>(a, ctx->stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "prior propagation kernel launch: %s", hipGetErrorString(e));
+    return (int)GP_OK;
+  });
+}
+
+int gp_rts_smooth_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, int64_t prior_prec_stride,
+                         const void* d_noise, int64_t noise_stride, const void* d_x, const void* d_x_next,
+                         const void* d_cov_next, const void* d_lo, const void* d_hi, void* d_x_smooth, void* d_cov_smooth,
+                         void* d_sigma_smooth, int32_t* d_status, int64_t n_rows, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_A || !d_noise || !d_x || !d_x_next || !d_cov_next || !d_x_smooth || !d_status || (!d_cov_smooth && !d_sigma_smooth))
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if ((d_lo == nullptr) != (d_hi == nullptr)) return fail(GP_ERR_INVALID, "bounds need both lo and hi");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  if (int rc = row_stride("process noise", d_noise, noise_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  // a row's sub-group stores x_smooth before another wave has loaded its inputs: nothing may be smoothed in place
+  const void* ins[] = {d_A, d_prior_prec, d_noise, d_x, d_x_next, d_cov_next, d_lo, d_hi};
+  const void* outs[] = {d_x_smooth, d_cov_smooth, d_sigma_smooth, d_status};
+  for (const void* o : outs)
+    for (const void* in : ins)
+      if (o && o == in) return fail(GP_ERR_INVALID, "an output is an input");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::RtsSmoothArgs<T> a;
+    a.A = as<T>(d_A);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_prec_stride = prior_prec_stride;
+    a.noise = as<T>(d_noise);
+    a.noise_stride = noise_stride;
+    a.x = as<T>(d_x);
+    a.x_next = as<T>(d_x_next);
+    a.cov_next = as<T>(d_cov_next);
+    a.lo = as<T>(d_lo);
+    a.hi = as<T>(d_hi);
+    a.x_smooth = as<T>(d_x_smooth);
+    a.cov_smooth = as<T>(d_cov_smooth);
+    a.sigma_smooth = as<T>(d_sigma_smooth);
+    a.status = d_status;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    hipError_t e = gpk::launch_rts_smooth<T>(a, ctx->stream);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "smoother kernel launch: %s", hipGetErrorString(e));
     return (int)GP_OK;
   });
 }

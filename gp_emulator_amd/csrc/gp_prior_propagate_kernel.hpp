@@ -45,10 +45,27 @@ struct PriorPropagateArgs {
   int d;
 };
 
+// S = C + Q over the wave's L triangles from its W triangles (shared with rts_smooth_kernel, gp_rts_smooth_kernel.hpp):
+// the wave's run of Q (or the one Q again for every row), consecutive lanes on consecutive elements
+template <typename T>
+__device__ inline void prior_stage_noise(double* Lw, const double* Ww, const T* noise, long long noise_stride, long long row0,
+                                         int nr, int D, int S, int lane) {
+  const int DD = D * D;
+  const int n = nr * DD;
+  for (int idx = lane; idx < n; idx += 64) {
+    const int rr = idx / DD, e = idx - rr * DD;
+    const int i = e / D, c = e - i * D;
+    if (c <= i) {
+      const int at = rr * S + newton_tri(i) + c;
+      Lw[at] = Ww[at] + (double)noise[(row0 + rr) * noise_stride + e];              // (the global row's)
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kPostCovThreads) void prior_propagate_kernel(PriorPropagateArgs<T> p) {
   extern __shared__ double prior_propagate_lds[];
-  const int D = p.d, DD = D * D;
+  const int D = p.d;
   const int G = newton_group(D), S = newton_pitch(D);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int R = 64 / G;                                     // rows of a wave
@@ -70,18 +87,7 @@ __global__ __launch_bounds__(kPostCovThreads) void prior_propagate_kernel(PriorP
   post_cov_solve(L, W, D, j, act, bad1);                    // W = C
   newton_wave_sync();
 
-  // S = C + Q over L: the wave's run of Q (or the one Q again for every row), consecutive lanes on consecutive elements
-  {
-    const int n = nr * DD;
-    for (int idx = lane; idx < n; idx += 64) {
-      const int rr = idx / DD, e = idx - rr * DD;
-      const int i = e / D, c = e - i * D;
-      if (c <= i) {
-        const int at = rr * S + newton_tri(i) + c;
-        Lw[at] = Ww[at] + (double)p.noise[(row0 + rr) * p.noise_stride + e];      // (the global row's)
-      }
-    }
-  }
+  prior_stage_noise(Lw, Ww, p.noise, p.noise_stride, row0, nr, D, S, lane);      // S = C + Q over L
   newton_wave_sync();
 
   const int bad2 = post_cov_factor(L, D, G, j, act);

@@ -477,7 +477,8 @@ class MultivariateEmulator(object):
         return cost, coef, grads, grad, None if G is None else self._contract_numpy(grads, G)
 
     def retrieve_many(self, Y0, obs, weights=None, prior=None, bounds=None, lam0=1e-2, max_iter=20, down=1.0 / 3.0,
-                      up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False, next_prior=None):
+                      up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False, next_prior=None,
+                      return_A=False):
         """Levenberg-Marquardt retrieval of M state vectors at once on this emulator: minimises, row by row,
 
             F(y) = 1/2 sum_b w_b (f_b(y) - obs_b)^2  (+ 1/2 (y - y0)^T P (y - y0) with ``prior=(y0 (D,), P (D, D))``)
@@ -520,7 +521,10 @@ class MultivariateEmulator(object):
         (random-walk dynamics).  ``prior_status`` is 0, k + 1 when pivot k of ``A + P`` fails, or D + k + 1 when pivot k of
         ``(A + P)^-1 + Q`` fails; then the row's ``next_prec`` is NaN.  On the GPU this is one ``prior_propagate_device`` call
         on the loop's own device arrays after the loop (the covariance in between never leaves the chip); on the numpy
-        branch ``_lib.prior_propagate_numpy``.  With ``None`` nothing changes."""
+        branch ``_lib.prior_propagate_numpy``.  With ``None`` nothing changes.
+
+        ``return_A=True`` appends, as the last element, the loop's final data-term matrix ``A (M, D, D)`` (the
+        Gauss-Newton term whose ``(A + P)^-1`` is ``cov``), as ``retrieve_bands`` does.  With ``False`` nothing changes."""
         from . import _lib, _retrieve
         Y0 = np.asarray(Y0)
         if Y0.ndim != 2:
@@ -546,7 +550,7 @@ class MultivariateEmulator(object):
             def step(x, g, A, lam):
                 return _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds)
             return _retrieve.lm_numpy(data_term, step, Y0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov,
-                                      next_prior)
+                                      next_prior, return_A)
 
         dt = np.dtype(precision)
         isz = dt.itemsize
@@ -571,15 +575,26 @@ class MultivariateEmulator(object):
                 else:
                     ctx.mv_gauss_newton_device(dt, d_der, d_G, a, M, P, D)
             return _retrieve.lm_device(scratch, M, D, Y0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                       misfit, next_prior)
+                                       misfit, next_prior, return_A)
 
-    def retrieve_series(self, Y0, obs, weights, prior, noise, **loop_args):
+    def retrieve_series(self, Y0, obs, weights, prior, noise, smooth=False, **loop_args):
         """A time series of ``retrieve_many`` on this emulator: ``obs`` (T, N_full) or (T, M, N_full) and ``weights``
         the same or None, one retrieval per date, the posterior of a date propagated by the process noise ``noise``
         (D, D) or (M, D, D) into the prior of the next (``_retrieve.retrieve_series``: what it returns, and why
-        ``prior`` is required).  ``loop_args`` are ``retrieve_many``'s other keywords."""
+        ``prior`` is required).  ``loop_args`` are ``retrieve_many``'s other keywords.
+
+        ``smooth=True`` appends the Rauch-Tung-Striebel smoothed trajectory ``X_s (T, M, D)``, ``sigma_s (T, M, D)``
+        and ``smooth_status (T, M)``, as ``perband.retrieve_bands_series`` does: on the GPU one ``rts_smooth_device``
+        call per date on this emulator's context, with ``is_gpu=False`` ``_lib.rts_smooth_numpy``; never a fallback."""
         from . import _retrieve
-        return _retrieve.retrieve_series(self.retrieve_many, Y0, obs, weights, prior, noise, **loop_args)
+        if not smooth:
+            return _retrieve.retrieve_series(self.retrieve_many, Y0, obs, weights, prior, noise, **loop_args)
+        context = None
+        if loop_args.get("is_gpu", True):
+            dt = np.dtype(loop_args.get("precision", np.float64))
+            context = lambda: self._fresh_gpu_state(dt)["ctx"]
+        return _retrieve.retrieve_series(self.retrieve_many, Y0, obs, weights, prior, noise, smooth=True, context=context,
+                                         **loop_args)
 
     # ---- second derivatives ---------------------------------------------------------------------
     def hessian(self, y, is_gpu=False, weights=None):

@@ -276,7 +276,7 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
 
 def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prior=None, bounds=None, lam0=1e-2,
                    max_iter=20, down=1.0 / 3.0, up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64,
-                   device=None, step_fn=None, return_cov=False, next_prior=None):
+                   device=None, step_fn=None, return_cov=False, next_prior=None, return_A=False):
     """Levenberg-Marquardt retrieval of M state vectors at once on E per-band emulators: minimises, row by row,
 
         F(x) = 1/2 sum_e w (mu_e(x) - obs[e])^2  (+ 1/2 (x - x0)^T P (x - x0) with ``prior=(x0 (D,), P (D, D))``)
@@ -321,7 +321,11 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     (random-walk dynamics).  ``prior_status`` is 0, k + 1 when pivot k of ``A + P`` fails, or D + k + 1 when pivot k of
     ``(A + P)^-1 + Q`` fails; then the row's ``next_prec`` is NaN.  On the GPU this is one ``prior_propagate_device`` call
     on the loop's own device arrays after the loop (the covariance in between never leaves the chip); on the numpy
-    branch ``_lib.prior_propagate_numpy``.  With ``None`` nothing changes."""
+    branch ``_lib.prior_propagate_numpy``.  With ``None`` nothing changes.
+
+    ``return_A=True`` appends, as the last element, the loop's final data-term matrix ``A (M, D, D)``: the matrix whose
+    ``(A + P)^-1`` is ``cov``, which the backward pass of a smoothed series reads (on the GPU one more download).  With
+    ``False`` nothing changes."""
     if second_order not in ("gauss_newton", "full"):
         raise ValueError("second_order must be 'gauss_newton' or 'full'")
     X0 = np.asarray(X0)
@@ -341,7 +345,7 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
         step = step_fn if step_fn is not None else (
             lambda x, g, A, lam: _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds))
         return _retrieve.lm_numpy(lambda X: _misfit_numpy(gps, X, obs, weights, second_order, False), step, X0, lam0,
-                                  max_iter, down, up, ftol, xtol, prior, return_cov, next_prior)
+                                  max_iter, down, up, ftol, xtol, prior, return_cov, next_prior, return_A)
 
     ctx = _lib.default_context(device)
     batch = _batch_model(ctx, gps, inputs, precision, False)
@@ -358,19 +362,29 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
                 batch.misfit_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a if second_order == "gauss_newton" else None,
                                     d_hess=a if second_order == "full" else None)
             return _retrieve.lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                       misfit, next_prior)
+                                       misfit, next_prior, return_A)
     finally:
         batch.close()
 
 
-def retrieve_bands_series(gps, X0, obs, weights, prior, noise, **loop_args):
+def retrieve_bands_series(gps, X0, obs, weights, prior, noise, smooth=False, **loop_args):
     """A time series of ``retrieve_bands`` on the emulators ``gps``: ``obs`` (T, E, M) -- or anything ``retrieve_bands``
     takes, per date -- and ``weights`` the same or None, one retrieval per date, the posterior of a date propagated by
     the process noise ``noise`` (D, D) or (M, D, D) into the prior of the next (``_retrieve.retrieve_series``: what it
-    returns, and why ``prior`` is required).  ``loop_args`` are ``retrieve_bands``' other keywords."""
+    returns, and why ``prior`` is required).  ``loop_args`` are ``retrieve_bands``' other keywords.
+
+    ``smooth=True`` appends the Rauch-Tung-Striebel smoothed trajectory ``X_s (T, M, D)``, ``sigma_s (T, M, D)`` and
+    ``smooth_status (T, M)``: every date then also carries the observations after it (a gap is filled from both
+    sides).  On the GPU the backward pass is one ``rts_smooth_device`` call per date with the smoothed state and
+    covariance of the later date resident on the device; with ``is_gpu=False`` (or a ``step_fn``) it is
+    ``_lib.rts_smooth_numpy``; never a fallback."""
     def retrieve(X, obs_t, weights_t, **kw):
         return retrieve_bands(gps, X, obs_t, weights_t, **kw)
-    return _retrieve.retrieve_series(retrieve, X0, obs, weights, prior, noise, **loop_args)
+    if not smooth:
+        return _retrieve.retrieve_series(retrieve, X0, obs, weights, prior, noise, **loop_args)
+    on_device = loop_args.get("is_gpu", True) and loop_args.get("step_fn") is None
+    context = (lambda: _lib.default_context(loop_args.get("device"))) if on_device else None
+    return _retrieve.retrieve_series(retrieve, X0, obs, weights, prior, noise, smooth=True, context=context, **loop_args)
 
 
 # ---------------------------------------------------------------------------------------------

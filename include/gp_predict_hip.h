@@ -489,6 +489,44 @@ int gp_prior_propagate_device(gp_ctx* ctx, int dtype, const void* d_A, const voi
                               int64_t prior_prec_stride, const void* d_noise, int64_t noise_stride,
                               void* d_next_prec, int32_t* d_status, int64_t n_rows, int n_inputs);
 
+/* ---- fixed-interval smoother -------------------------------------------------------------------------
+ * One backward step of the Rauch-Tung-Striebel smoother over a series of retrievals (random-walk dynamics): the
+ * filtered posterior of date t corrected by the smoothed posterior of date t + 1.  Called for t = T-2 .. 0, with the
+ * last date's filtered state and covariance as the first x_next / cov_next, it completes the forward pass that
+ * gp_prior_propagate_device chains.  For each of n_rows rows, D = n_inputs,
+ *   A' = A[m] (+ P[m])                   d_A [n_rows][D][D] of date t and the prior precision it was retrieved with:
+ *                                        NULL, one P [D][D] (stride 0) or row m's at m * prior_prec_stride elements
+ *   C  = A'^-1,  S = C + Q[m],  N = S^-1 exactly gp_prior_propagate_device's doubles (the same functions); d_noise one
+ *                                        Q [D][D] (stride 0) or row m's at m * noise_stride elements; required
+ *   G  = C N                             smoother gain
+ *   x_smooth[m] = x[m] + G (x_next[m] - x[m])      d_x the filtered state of date t, d_x_next the smoothed state of
+ *                                        date t + 1, [n_rows][D]; then clamped to [lo, hi] (d_lo / d_hi [D], both or
+ *                                        neither) as gp_newton_step_device clamps its trial
+ *   Delta = cov_next[m] - S              d_cov_next [n_rows][D][D], the smoothed covariance of date t + 1
+ *   C_s = C + G Delta G^T
+ *   cov_smooth[m] = C_s                  d_cov_smooth [n_rows][D][D]: elements i >= j computed, the upper triangle
+ *                                        stored from the same doubles, so cov_smooth[m] is symmetric bit for bit
+ *   sigma_smooth[m] = sqrt(C_s_dd)       d_sigma_smooth [n_rows][D], from the unrounded diagonal
+ *   status[m] = 0; k + 1 when pivot k (0-based) of A' is not > 0 or not finite; D + k + 1 when pivot k of S is; then
+ *                                        every element of x_smooth[m], cov_smooth[m] and sigma_smooth[m] is a quiet NaN
+ * Only the lower triangles of A, P, Q and cov_next are read.  Either of d_cov_smooth and d_sigma_smooth may be NULL,
+ * not both.  Everything runs in double in both precisions: C, S, N, G and Delta never leave the chip and are never
+ * rounded to `dtype`; each output is rounded once, on store.  Delta_ij and (x_next - x)_j are one subtraction each of
+ * the inputs as doubles; every product (C N, G Delta, (G Delta) G^T, G (x_next - x)) is a sum of fma chains from 0 in
+ * ascending index.  No atomics: a row is computed by its own lanes from its own data, so its result does not depend on
+ * the other rows, on its place in the call or on the grid; two calls agree bit for bit, and so do stride 0 and the
+ * same matrix repeated for every row.
+ * Strides are 0 or >= n_inputs^2 (GP_ERR_INVALID otherwise, and for a non-zero stride with a NULL pointer).
+ * GP_ERR_INVALID also when only one of d_lo / d_hi is given, when d_cov_smooth and d_sigma_smooth are both NULL, and
+ * when an output pointer equals an input pointer (nothing is smoothed in place).
+ * Device pointers of `dtype` (d_status int32), asynchronous on the context's stream; n_rows > 0,
+ * 1 <= n_inputs <= 32 (GP_ERR_UNSUPPORTED beyond). */
+int gp_rts_smooth_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec,
+                         int64_t prior_prec_stride, const void* d_noise, int64_t noise_stride,
+                         const void* d_x, const void* d_x_next, const void* d_cov_next,
+                         const void* d_lo, const void* d_hi, void* d_x_smooth, void* d_cov_smooth,
+                         void* d_sigma_smooth, int32_t* d_status, int64_t n_rows, int n_inputs);
+
 /* ---- training objective (next after the predict path: SURVEY.md 8f rank 2) -------------------
  * For each of n_sets hyper-parameter vectors theta [n_sets][n_inputs+2]: what
  * GaussianProcess.loglikelihood + partial_devs compute (gp_emulator/GaussianProcess.py:52-125):

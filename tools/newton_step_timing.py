@@ -6,6 +6,7 @@ retrieve_bands iteration against its misfit_device alone.  Prints one JSON line 
     python tools/newton_step_timing.py [--legs device,host,iteration] [--out FILE] [--reps 20] [--warmup 5]
     python tools/newton_step_timing.py --legs posterior [--out FILE] [--reps 50] [--warmup 5]
     python tools/newton_step_timing.py --legs rows,propagate [--shared-only] [--out FILE]
+    python tools/newton_step_timing.py --legs smooth,smooth_series [--out FILE] [--reps 30]
     python tools/newton_step_timing.py --legs registers        # no GPU: compiles csrc/gp_newton_tu.hip once
 
 device     gp_newton_step_device at M = 1e5 rows, D in {11, 16}, both dtypes, trial and status out: the median of
@@ -31,6 +32,12 @@ rows       the step (trial and status out), the update (every row accepting) and
 propagate  gp_prior_propagate_device (next_prec and status out) against the two gp_posterior_cov_device launches it
            replaces -- (A + P)^-1 to a covariance array, then that array with Q in the prior's place -- the pair between
            one pair of events; shared P and Q, and per-row P and Q for the one kernel.  Same rows, same alternation.
+
+smooth     gp_rts_smooth_device (x_smooth, cov_smooth, sigma_smooth, status out) against gp_prior_propagate_device on the
+           same resident A, P and Q, alternating inside one loop, each call between its own pair of events: M = 1e5,
+           D in {11, 16, 32}, both dtypes, P and Q shared and per row; the numpy branch on --numpy-rows rows, scaled to M.
+smooth_series  one retrieve_bands_series at E = 12, N = 250, D = 11, 1e5 rows, T = 8: wall clock of the forward pass, of
+           the smoothed series and of the backward pass alone (profiles/r13_rts_smooth.txt quotes both legs).
 
 Every leg that touches the GPU runs under the caller's time limit, e.g.
     timeout -k 10 300 python tools/newton_step_timing.py --legs device,host,iteration --out profiles/r09_newton_step.txt
@@ -316,6 +323,107 @@ def leg_propagate(a):
                 ctx.free(p)
 
 
+def leg_smooth(a):
+    """gp_rts_smooth_device (x_smooth, cov_smooth, sigma_smooth and status out) beside gp_prior_propagate_device on the same
+    resident A, P and Q: the smoother's first half is the propagation, so the ratio is what the gain, the three products
+    and the smaller occupancy cost.  The numpy branch is timed on --numpy-rows rows and scaled to M."""
+    ctx = _lib.default_context(0)
+    for D in (11, 16, 32):
+        for prec in (np.float64, np.float32):
+            dt = np.dtype(prec)
+            isz = dt.itemsize
+            x, _, A, _ = systems(D, dt)
+            shared, rows = priors(D, dt)
+            rs = np.random.RandomState(7 + D)
+            B = rs.standard_normal((D + 2, D))
+            Q = (1e-3 * (B.T @ B)).astype(dt)                   # on the covariance's scale: C ~ 1 / (D + 8)
+            u = rs.uniform(0.5, 2.0, M)[:, None, None]
+            Qr = (u * Q).astype(dt)
+            x_next = (x + 0.1 * rs.uniform(-1.0, 1.0, (M, D))).astype(dt)
+            cov_next = (u * (2.0 * Q.astype(np.float64) + np.eye(D) / (D + 8))).astype(dt)      # SPD, of the size of S
+            d_A, d_P, d_Pr, d_Q, d_Qr, d_x, d_xn, d_cn = (ctx.to_device(v) for v in (A, shared[1], rows[1], Q, Qr, x, x_next, cov_next))
+            d_next, d_cs = ctx.malloc(M * D * D * isz), ctx.malloc(M * D * D * isz)
+            d_xs, d_ss = ctx.malloc(M * D * isz), ctx.malloc(M * D * isz)
+            d_s1, d_s2 = ctx.malloc(M * 4), ctx.malloc(M * 4)
+            DD = D * D
+            calls = dict(propagate=lambda: ctx.prior_propagate_device(dt, d_A, d_P, 0, d_Q, 0, d_next, d_s1, M, D),
+                         smooth=lambda: ctx.rts_smooth_device(dt, d_A, d_P, 0, d_Q, 0, d_x, d_xn, d_cn, None, None, d_xs, d_cs,
+                                                              d_ss, d_s2, M, D),
+                         propagate_rows=lambda: ctx.prior_propagate_device(dt, d_A, d_Pr, DD, d_Qr, DD, d_next, d_s1, M, D),
+                         smooth_rows=lambda: ctx.rts_smooth_device(dt, d_A, d_Pr, DD, d_Qr, DD, d_x, d_xn, d_cn, None, None, d_xs,
+                                                                   d_cs, d_ss, d_s2, M, D))
+            t = timed_alternating(ctx, calls, a)
+            failed = int(np.count_nonzero(ctx.to_host(d_s2, (M,), np.int32)))
+            n = a.numpy_rows
+            t0 = time.perf_counter()
+            _lib.rts_smooth_numpy(A[:n], shared[1], Q, x[:n], x_next[:n], cov_next[:n])
+            numpy_ms = (time.perf_counter() - t0) * 1e3 * M / n
+            nbytes = M * (3 * DD + 4 * D) * isz                 # A, cov_next in, cov_smooth out; x, x_next in, x_s, sigma out
+            row = dict(leg="smooth", dtype=dt.name, rows=M, D=D, reps=a.reps, rows_failed=failed, MB=round(nbytes / 1e6, 1))
+            for form, ts in t.items():
+                row.update({"%s_%s" % (form, k): v for k, v in stats(ts).items()})
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            row["smooth_GB_per_s"] = round(nbytes / (med["smooth"] * 1e-3) / 1e9, 1)
+            row["smooth_over_propagate"] = round(med["smooth"] / med["propagate"], 3)
+            row["smooth_rows_over_propagate_rows"] = round(med["smooth_rows"] / med["propagate_rows"], 3)
+            row["numpy_branch_ms_scaled_from_rows"] = n
+            row["numpy_branch_ms"] = round(numpy_ms, 1)
+            row["numpy_over_smooth"] = round(numpy_ms / med["smooth"], 1)
+            emit(a, **row)
+            for p in (d_A, d_P, d_Pr, d_Q, d_Qr, d_x, d_xn, d_cn, d_next, d_cs, d_xs, d_ss, d_s1, d_s2):
+                ctx.free(p)
+
+
+def leg_smooth_series(a):
+    """One series of retrieve_bands at E = 12 (N = 250, D = 11, 1e5 rows, T = 8 dates, 8 trials per date): the wall clock
+    of the forward pass alone (smooth=False), of the smoothed series, and of the backward pass by itself on the kept
+    per-date arrays (_retrieve.smooth_device: uploads of A, P and x per date, one launch, three downloads)."""
+    from gp_emulator_amd import _retrieve, perband
+    from gp_emulator_amd.GaussianProcess import GaussianProcess
+    N, D, E, T = 250, 11, 12, 8
+    rs = np.random.RandomState(5)
+    inputs = rs.random_sample((N, D))
+    gps = []
+    for e in range(E):
+        gp = GaussianProcess(inputs, [])
+        gp.theta, gp.invQt = rs.random_sample(D + 2), rs.standard_normal(N) / N
+        gps.append(gp)
+    x_true = rs.uniform(0.2, 0.8, (M, D))
+    X0 = np.clip(x_true + 0.05 * rs.uniform(-1.0, 1.0, (M, D)), 0.0, 1.0)
+    prior, Q = (X0, 32.0 * np.eye(D) + 4.0), 1e-3 * np.eye(D) + 1e-4
+    for prec in (np.float64, np.float32):
+        obs = np.asarray(perband.predict_bands(gps, x_true.astype(prec), do_unc=False, precision=prec)[0], dtype=np.float64)
+        obs_t = obs + 1e-3 * np.max(np.abs(obs)) * rs.standard_normal((T,) + obs.shape)
+        kw = dict(bounds=(np.zeros(D), np.ones(D)), precision=prec, max_iter=8)
+        perband.retrieve_bands_series(gps, X0, obs_t[:1], None, prior, Q, **kw)           # warm-up: one date
+        t0 = time.perf_counter()
+        perband.retrieve_bands_series(gps, X0, obs_t, None, prior, Q, **kw)
+        t1 = time.perf_counter()
+        kept = {}
+
+        def context():
+            return _lib.default_context(None)
+        real = _retrieve.smooth_device
+
+        def recording(ctx, dt, *args):
+            kept["args"] = (ctx, dt) + args
+            return real(ctx, dt, *args)
+        _retrieve.smooth_device = recording
+        try:
+            t2 = time.perf_counter()
+            full = perband.retrieve_bands_series(gps, X0, obs_t, None, prior, Q, smooth=True, **kw)
+            t3 = time.perf_counter()
+        finally:
+            _retrieve.smooth_device = real
+        t4 = time.perf_counter()
+        real(*kept["args"])
+        t5 = time.perf_counter()
+        emit(a, leg="smooth_series", dtype=np.dtype(prec).name, emulators=E, rows=M, D=D, n_train=N, dates=T, max_iter=8,
+             forward_ms=round((t1 - t0) * 1e3, 1), smoothed_series_ms=round((t3 - t2) * 1e3, 1),
+             backward_pass_ms=round((t5 - t4) * 1e3, 1), backward_over_forward=round((t5 - t4) / (t1 - t0), 3),
+             smooth_status_set=int(np.count_nonzero(full[9])), sigma_ratio_first_date=round(float(np.median(full[8][0] / full[1][0])), 4))
+
+
 def leg_iteration(a):
     N, D, E = 250, 11, 12
     ctx = _lib.default_context(0)
@@ -379,7 +487,7 @@ def leg_registers(a):
             continue
         if m.group(1) == "Function Name":
             flush()
-            t = re.search(r"\d+(newton_step_kernel|lm_update_kernel|posterior_cov_kernel|prior_propagate_kernel)I([fd])E", m.group(2))
+            t = re.search(r"\d+(newton_step_kernel|lm_update_kernel|posterior_cov_kernel|prior_propagate_kernel|rts_smooth_kernel)I([fd])E", m.group(2))
             name = "%s<%s>" % (t.group(1), {"f": "float", "d": "double"}[t.group(2)]) if t else m.group(2)
             row = {}
         else:
@@ -394,6 +502,12 @@ def leg_registers(a):
         pitch = tri + (16 - tri % 32) % 32
         print("dynamic LDS of posterior_cov_kernel and prior_propagate_kernel at D = %d: %d rows x 2 x %d doubles = %d bytes per workgroup"
               % (D, rows, pitch, rows * 2 * pitch * 8))
+    for D in (11, 16, 32):          # gp_rts_smooth_kernel.hpp: one wave per workgroup, two triangles and two full matrices per row
+        rows, tri = (4 if D <= 16 else 2), D * (D + 1) // 2
+        pitch, full = tri + (16 - tri % 32) % 32, D * D + (16 - D * D % 32) % 32
+        nbytes = rows * (2 * pitch + 2 * full) * 8
+        print("dynamic LDS of rts_smooth_kernel at D = %d: %d rows x (2 x %d + 2 x %d) doubles = %d bytes per workgroup of one wave, "
+              "%d workgroups per CU of 160 KB" % (D, rows, pitch, full, nbytes, 160 * 1024 // nbytes))
 
 
 if __name__ == "__main__":
@@ -402,6 +516,7 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--numpy-rows", type=int, default=2000, help="smooth leg: rows of the numpy branch's timing, scaled to 1e5")
     ap.add_argument("--shared-only", action="store_true", help="rows leg: the plain entries only (also runs on a checkout without the _rows entries)")
     a = ap.parse_args()
     legs = a.legs.split(",")
@@ -417,3 +532,7 @@ if __name__ == "__main__":
         leg_rows(a)
     if "propagate" in legs:
         leg_propagate(a)
+    if "smooth" in legs:
+        leg_smooth(a)
+    if "smooth_series" in legs:
+        leg_smooth_series(a)
