@@ -1,4 +1,5 @@
-"""ctypes binding of libgp_predict_hip.so (the C ABI in include/gp_predict_hip.h).
+"""ctypes binding of libgp_predict_hip.so (the C ABI in include/gp_predict_hip.h).  The float64 numpy branches of the
+small dense solves live in ``_dense_numpy``; their names are imported here for the callers that take them from ``_lib``.
 
 No PyTorch, no GPU framework: device memory, streams and events all go through the
 library.  Loading FAILS LOUDLY (``GpuPredictUnavailable``) when the library has not been
@@ -11,6 +12,9 @@ import threading
 
 import numpy as np
 
+from ._dense_numpy import (DAMPINGS, newton_step_numpy, posterior_cov_numpy, prec_rows, prior_propagate_numpy,  # noqa: F401
+                           prior_rows, row_strides, rts_smooth_numpy, _cholesky_inverse_numpy, _mirror_lower)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_PREDICT_LIB lets tools/ab_bench.py time differently-built variants of the library on
 # one device; it never points at anything but a build of this repo's csrc/.
@@ -19,7 +23,7 @@ LIB_PATH = os.environ.get("GP_PREDICT_LIB") or os.path.join(HERE, "libgp_predict
 GP_F32, GP_F64 = 0, 1
 GP_DERIV_DMAJOR, GP_DERIV_ROWMAJOR = 0, 1
 GP_DAMP_DIAGONAL, GP_DAMP_IDENTITY = 0, 1
-_DAMPING = {"diagonal": GP_DAMP_DIAGONAL, "identity": GP_DAMP_IDENTITY}
+_DAMPING = dict(zip(DAMPINGS, (GP_DAMP_DIAGONAL, GP_DAMP_IDENTITY)))
 
 c_int, c_i64, c_void_p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
 c_dp = ctypes.POINTER(ctypes.c_double)
@@ -219,6 +223,24 @@ def _ptr(a):
     return a.ctypes.data_as(c_void_p)
 
 
+def _dtype_code(dtype):
+    """The C ABI's dtype code of a numpy dtype: GP_F64 for float64, GP_F32 for anything else."""
+    return GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
+
+
+def _device_dtype(precision, a):
+    """The device dtype of a host wrapper: ``precision`` when given, else float32 when ``a`` is float32, else float64."""
+    return np.dtype(precision if precision is not None else (np.float32 if a.dtype == np.float32 else np.float64))
+
+
+def _matrix_rows(A, precision):
+    """``(A as an array, its device dtype, M, D)`` of a host wrapper's ``A`` (M, D, D)."""
+    A = np.asarray(A)
+    if A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
+    return A, _device_dtype(precision, A), A.shape[0], A.shape[1]
+
+
 def device_numa_cpus(device=0):
     """The cpus of the NUMA node ``device`` is attached to that this process may run on (empty
     set when sysfs does not tell).  Initialises the HIP runtime."""
@@ -296,224 +318,35 @@ class OutputPool:
         return base.view(dtype).reshape(shape)
 
 
-def prec_rows(P, M, D, dtype=np.float64):
-    """A prior precision (or a process noise) as a contiguous ``dtype`` array: one matrix ``(D, D)`` for all rows, or
-    ``(M, D, D)``, row m's own.  With one row the two say the same and the array is taken as shared, so a one-row call
-    goes the way it always went."""
-    P = np.asarray(P, dtype=dtype)
-    return np.ascontiguousarray(P if M > 1 and P.ndim == 3 and P.shape == (M, D, D) else P.reshape(D, D))
+class Scratch(object):
+    """Device arrays of one call, freed together on exit -- also when the call raises half way: ``up(array)`` uploads
+    in the call's precision (None stays None), ``alloc(nbytes)`` reserves."""
+
+    def __init__(self, ctx, dt):
+        self.ctx, self.dt, self.held = ctx, dt, []
+
+    def up(self, a):
+        if a is None:
+            return None
+        self.held.append(self.ctx.to_device(np.ascontiguousarray(a, dtype=self.dt)))
+        return self.held[-1]
+
+    def alloc(self, nbytes):
+        self.held.append(self.ctx.malloc(max(1, nbytes)))
+        return self.held[-1]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        held, self.held = self.held, []
+        for p in held:
+            self.ctx.free(p)
 
 
-def prior_rows(prior, M, D, dtype=np.float64):
-    """``prior = (x0, P)`` as contiguous ``dtype`` arrays: ``x0`` ``(D,)`` or per row ``(M, D)``, ``P`` ``(D, D)`` or
-    per row ``(M, D, D)``, independently of one another (with one row: shared, as ``prec_rows``)."""
-    x0 = np.asarray(prior[0], dtype=dtype)
-    x0 = np.ascontiguousarray(x0 if M > 1 and x0.ndim == 2 and x0.shape == (M, D) else x0.reshape(D))
-    return x0, prec_rows(prior[1], M, D, dtype)
-
-
-def row_strides(x0, P):
-    """The element strides of the ``_rows`` entries for what ``prior_rows`` / ``prec_rows`` returned: 0 = shared."""
-    return (x0.shape[1] if x0 is not None and x0.ndim == 2 else 0), (P.shape[1] * P.shape[2] if P is not None and P.ndim == 3 else 0)
-
-
-def newton_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=None):
-    """The damped Newton step of ``gp_newton_step_device`` in float64 numpy, vectorised over the rows and written out
-    in the kernel's summation order (ascending index in the factorisation, in both substitutions and in the prior's
-    chain): ``(step (M, D), trial (M, D), status (M,) int32)``.  The explicit CPU branch of ``Context.newton_step``
-    and of ``perband.retrieve_bands``, and the reference of the CPU tests; never a fallback.
-
-        A' = A (+ P),  g' = grad (+ P (x - x0)),  A'_dd += lam * (A'_dd | 1),  L L^T = A' (lower triangle read),
-        step = -L^-T L^-1 g',  trial = clip(x + step, lo, hi);  status = k + 1 when pivot k is not > 0 or not finite,
-        then step = 0 and trial = x.
-
-    ``prior=(x0 (D,) or (M, D), P (D, D) or (M, D, D))`` (shared or row m's own, as ``gp_newton_step_rows_device``),
-    ``bounds=(lo (D,), hi (D,))``, ``lam`` (M,) or a scalar."""
-    if damping not in _DAMPING:
-        raise ValueError("damping must be 'diagonal' or 'identity'")
-    x = np.array(x, dtype=np.float64, ndmin=2)
-    M, D = x.shape
-    g = np.array(grad, dtype=np.float64).reshape(M, D)
-    L = np.array(A, dtype=np.float64).reshape(M, D, D)
-    lam = np.broadcast_to(np.asarray(lam, dtype=np.float64), (M,))
-    if prior is not None:
-        x0, P = prior_rows(prior, M, D)
-        L = L + P
-        for c in range(D):
-            g += P[..., :, c] * (x[:, c] - x0[..., c])[:, None]
-    idx = np.arange(D)
-    diag = L[:, idx, idx]
-    L[:, idx, idx] = diag + lam[:, None] * (diag if damping == "diagonal" else 1.0)
-    status = np.zeros(M, np.int32)
-    with np.errstate(all="ignore"):
-        for k in range(D):
-            s = L[:, k:, k].copy()                                   # rows j >= k of column k
-            for q in range(k):
-                s -= L[:, k:, q] * L[:, k, q][:, None]
-            piv = s[:, 0]
-            bad = ~(piv > 0.0) | ~np.isfinite(piv)
-            status[(status == 0) & bad] = k + 1
-            dk = np.sqrt(piv)
-            L[:, k, k] = dk
-            L[:, k + 1:, k] = s[:, 1:] / dk[:, None]
-        y = g                                                       # y = L^-1 g'
-        for k in range(D):
-            y[:, k] = y[:, k] / L[:, k, k]
-            y[:, k + 1:] -= L[:, k + 1:, k] * y[:, k][:, None]
-        z = np.zeros((M, D))                                        # z = L^-T y
-        for i in range(D - 1, -1, -1):
-            a = y[:, i].copy()
-            for k in range(i + 1, D):
-                a -= L[:, k, i] * z[:, k]
-            z[:, i] = a / L[:, i, i]
-    ok = (status == 0)[:, None]
-    step = np.where(ok, -z, 0.0)
-    trial = x + step
-    if bounds is not None:
-        trial = np.minimum(np.maximum(trial, np.asarray(bounds[0], dtype=np.float64)), np.asarray(bounds[1], dtype=np.float64))
-    trial = np.where(ok, trial, x)
-    return step, trial, status
-
-
-def _cholesky_inverse_numpy(L):
-    """``(W, status)`` for the matrices ``L`` (M, D, D), factored in place: ``W[:, i, j]``, i >= j, is element (i, j) of
-    the inverse by the kernels' chains (ascending index in the factorisation and in both substitutions of every unit
-    vector), NaN throughout where ``status`` (k + 1 for the first pivot that is not > 0 or not finite) is not 0.  Only
-    the lower triangle of ``L`` is read."""
-    M, D = L.shape[:2]
-    status = np.zeros(M, np.int32)
-    W = np.zeros((M, D, D))                                         # W[:, i, j]: y_i, then z_i, of column j
-    with np.errstate(all="ignore"):
-        for k in range(D):
-            s = L[:, k:, k].copy()                                   # rows j >= k of column k
-            for q in range(k):
-                s -= L[:, k:, q] * L[:, k, q][:, None]
-            piv = s[:, 0]
-            bad = ~(piv > 0.0) | ~np.isfinite(piv)
-            status[(status == 0) & bad] = k + 1
-            dk = np.sqrt(piv)
-            L[:, k, k] = dk
-            L[:, k + 1:, k] = s[:, 1:] / dk[:, None]
-        for i in range(D):                                           # y = L^-1 e_j, the columns j <= i side by side
-            s = np.zeros((M, i + 1))
-            s[:, i] = 1.0
-            for k in range(i):                                       # (column j takes the terms k >= j)
-                s[:, :k + 1] -= L[:, i, k][:, None] * W[:, k, :k + 1]
-            W[:, i, :i + 1] = s / L[:, i, i][:, None]
-        for i in range(D - 1, -1, -1):                               # z = L^-T y, down to row j
-            a = W[:, i, :i + 1].copy()
-            for k in range(i + 1, D):
-                a -= L[:, k, i][:, None] * W[:, k, :i + 1]
-            W[:, i, :i + 1] = a / L[:, i, i][:, None]
-        W[status != 0] = np.nan
-    return W, status
-
-
-def posterior_cov_numpy(A, prior_prec=None):
-    """The posterior covariance of ``gp_posterior_cov_device`` in float64 numpy, vectorised over the rows and written
-    out in the kernel's summation order (ascending index in the factorisation and in both substitutions):
-    ``(cov (M, D, D), sigma (M, D), status (M,) int32)``.  The explicit CPU branch of ``Context.posterior_cov`` and of
-    ``perband.retrieve_bands(return_cov=True)``, and the reference of the CPU tests; never a fallback.
-
-        A' = A (+ P), no damping,  L L^T = A' (lower triangle read),  C[:, j] = L^-T L^-1 e_j,
-        cov = C with the elements i >= j from column j's solve and the upper triangle mirrored from them,
-        sigma = sqrt(diag C);  status = k + 1 when pivot k is not > 0 or not finite, then cov and sigma are NaN.
-
-    ``prior_prec`` is ``(D, D)``, shared, or ``(M, D, D)``, row m's own (``gp_posterior_cov_rows_device``)."""
-    L = np.array(A, dtype=np.float64)
-    if L.ndim != 3 or L.shape[1] != L.shape[2]:
-        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
-    M, D = L.shape[:2]
-    if prior_prec is not None:
-        L = L + prec_rows(prior_prec, M, D)
-    W, status = _cholesky_inverse_numpy(L)
-    with np.errstate(all="ignore"):
-        cov = np.tril(W) + np.transpose(np.tril(W, -1), (0, 2, 1))
-        idx = np.arange(D)
-        sigma = np.sqrt(W[:, idx, idx])
-    return cov, sigma, status
-
-
-def prior_propagate_numpy(A, prior_prec, noise):
-    """The prior propagation of ``gp_prior_propagate_device`` in float64 numpy, in the kernel's summation order:
-    ``(next_prec (M, D, D), status (M,) int32)``.  The explicit CPU branch of ``Context.prior_propagate`` and of the
-    retrievals' ``next_prior=``, and the reference of the CPU tests; never a fallback.
-
-        A' = A (+ P),  C = A'^-1 as ``posterior_cov_numpy``,  S = C + Q (lower triangles),  N = S^-1 the same way,
-        next_prec = N with the upper triangle mirrored;  status = k + 1 when pivot k of A' fails, D + k + 1 when pivot
-        k of S fails, then next_prec is NaN.
-
-    ``prior_prec`` is None, ``(D, D)`` or ``(M, D, D)``; ``noise`` (the process-noise covariance Q) ``(D, D)`` or
-    ``(M, D, D)``."""
-    L = np.array(A, dtype=np.float64)
-    if L.ndim != 3 or L.shape[1] != L.shape[2]:
-        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
-    M, D = L.shape[:2]
-    if prior_prec is not None:
-        L = L + prec_rows(prior_prec, M, D)
-    C, first = _cholesky_inverse_numpy(L)
-    with np.errstate(all="ignore"):
-        S = C + prec_rows(noise, M, D)                               # (NaN where the first inversion failed)
-    W, second = _cholesky_inverse_numpy(S)
-    status = np.where(first != 0, first, np.where(second != 0, D + second, 0)).astype(np.int32)
-    return np.tril(W) + np.transpose(np.tril(W, -1), (0, 2, 1)), status
-
-
-def _mirror_lower(W):
-    """The symmetric matrices whose lower triangles are those of ``W`` (M, D, D)."""
-    return np.tril(W) + np.transpose(np.tril(W, -1), (0, 2, 1))
-
-
-def rts_smooth_numpy(A, prior_prec, noise, x, x_next, cov_next, bounds=None):
-    """One backward step of the Rauch-Tung-Striebel smoother of ``gp_rts_smooth_device`` in float64 numpy, in the
-    kernel's summation order: ``(x_smooth (M, D), cov_smooth (M, D, D), sigma_smooth (M, D), status (M,) int32)``.  The
-    explicit CPU branch of ``Context.rts_smooth`` and of the series' ``smooth=True``, and the reference of the CPU
-    tests; never a fallback.
-
-        A' = A (+ P),  C = A'^-1,  S = C + Q,  N = S^-1 as ``prior_propagate_numpy``,  G = C N,
-        x_smooth = clip(x + G (x_next - x), lo, hi),  Delta = cov_next - S,  cov_smooth = C + (G Delta) G^T (the lower
-        triangle computed, the upper mirrored),  sigma_smooth = sqrt(diag cov_smooth);  every product a sum from 0 in
-        ascending index;  status = k + 1 when pivot k of A' fails, D + k + 1 when pivot k of S fails, then the row's
-        outputs are NaN.
-
-    ``prior_prec`` is None, ``(D, D)`` or ``(M, D, D)``; ``noise`` ``(D, D)`` or ``(M, D, D)``; ``x`` the filtered
-    states of the date, ``x_next`` and ``cov_next`` the smoothed state and covariance of the next date;
-    ``bounds=(lo (D,), hi (D,))``.  Only the lower triangles of the matrices are read."""
-    L = np.array(A, dtype=np.float64)
-    if L.ndim != 3 or L.shape[1] != L.shape[2]:
-        raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
-    M, D = L.shape[:2]
-    x = np.asarray(x, dtype=np.float64).reshape(M, D)
-    d = np.asarray(x_next, dtype=np.float64).reshape(M, D) - x
-    if prior_prec is not None:
-        L = L + prec_rows(prior_prec, M, D)
-    Cw, first = _cholesky_inverse_numpy(L)
-    with np.errstate(all="ignore"):
-        S = Cw + prec_rows(noise, M, D)                              # (NaN where the first inversion failed)
-        Delta = _mirror_lower(np.asarray(cov_next, dtype=np.float64).reshape(M, D, D) - S)
-    Nw, second = _cholesky_inverse_numpy(S)                          # (factors S in place: Delta is taken first)
-    status = np.where(first != 0, first, np.where(second != 0, D + second, 0)).astype(np.int32)
-    with np.errstate(all="ignore"):
-        C, N = _mirror_lower(Cw), _mirror_lower(Nw)
-        G, F, K = np.zeros((M, D, D)), np.zeros((M, D, D)), np.zeros((M, D, D))
-        gd = np.zeros((M, D))
-        for k in range(D):
-            G += C[:, :, k, None] * N[:, None, k, :]
-        for c in range(D):
-            gd += G[:, :, c] * d[:, c, None]
-        for l in range(D):
-            F += G[:, :, l, None] * Delta[:, None, l, :]
-        for k in range(D):
-            K += F[:, :, k, None] * G[:, None, :, k]                 # K_ij += F_ik G_jk
-        xs = x + gd
-        if bounds is not None:
-            xs = np.minimum(np.maximum(xs, np.asarray(bounds[0], dtype=np.float64)), np.asarray(bounds[1], dtype=np.float64))
-        cov = _mirror_lower(C + K)
-        idx = np.arange(D)
-        sigma = np.sqrt(cov[:, idx, idx])
-    bad = status != 0
-    xs[bad], cov[bad], sigma[bad] = np.nan, np.nan, np.nan
-    return xs, cov, sigma, status
+def _download(ctx, dptr, shape, dtype):
+    """A device array as a host array of the caller's own (``to_host`` may hand out pooled memory)."""
+    return np.array(ctx.to_host(dptr, shape, dtype))
 
 
 class Context:
@@ -604,8 +437,7 @@ class Context:
 
     def reconstruct_device(self, dtype, d_basis, d_coef, d_out, n_rows, n_pcs, n_bands):
         """out[r][band] = sum_p coef[p][r] * basis[p][band] on the device (asynchronous)."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_reconstruct_device(self.h, code, d_basis, d_coef, d_out, int(n_rows),
+        check(self.lib.gp_reconstruct_device(self.h, _dtype_code(dtype), d_basis, d_coef, d_out, int(n_rows),
                                              int(n_pcs), int(n_bands)), "gp_reconstruct_device")
 
     def mv_misfit_device(self, dtype, d_basis, d_mu, d_deriv, d_obs, obs_stride, d_weights, weights_stride,
@@ -613,31 +445,27 @@ class Context:
         """cost [M], coef [P][M] and grad [M][D] of the observation misfit from the per-PC mean [P][M] and
         gradient [P][M][D] on the device (asynchronous; ``gp_mv_misfit_device``).  Strides in elements, 0 = one
         vector for all rows; ``d_weights`` and any output may be None."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_mv_misfit_device(self.h, code, d_basis, d_mu, d_deriv, d_obs, int(obs_stride), d_weights,
+        check(self.lib.gp_mv_misfit_device(self.h, _dtype_code(dtype), d_basis, d_mu, d_deriv, d_obs, int(obs_stride), d_weights,
                                            int(weights_stride), d_cost, d_coef, d_grad, int(n_rows), int(n_pcs),
                                            int(n_bands), int(n_inputs)), "gp_mv_misfit_device")
 
     def mv_gauss_newton_device(self, dtype, d_deriv, d_A, d_gn, n_rows, n_pcs, n_inputs):
         """gn[m] = deriv[:, m].T @ A @ deriv[:, m] on the device, exactly symmetric (asynchronous)."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_mv_gauss_newton_device(self.h, code, d_deriv, d_A, d_gn, int(n_rows), int(n_pcs),
+        check(self.lib.gp_mv_gauss_newton_device(self.h, _dtype_code(dtype), d_deriv, d_A, d_gn, int(n_rows), int(n_pcs),
                                                  int(n_inputs)), "gp_mv_gauss_newton_device")
 
     def mv_weight_gram_device(self, dtype, d_basis, d_weights, weights_stride, d_gram, n_rows, n_pcs, n_bands):
         """gram[m] = basis @ diag(w[m]) @ basis.T, [M][P][P], symmetric bit for bit, on the device (asynchronous;
         ``gp_mv_weight_gram_device``).  Row m of the weights is ``weights_stride`` elements behind row m - 1; 0 = one
         vector for all rows."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_mv_weight_gram_device(self.h, code, d_basis, d_weights, int(weights_stride), d_gram,
+        check(self.lib.gp_mv_weight_gram_device(self.h, _dtype_code(dtype), d_basis, d_weights, int(weights_stride), d_gram,
                                                 int(n_rows), int(n_pcs), int(n_bands)), "gp_mv_weight_gram_device")
 
     def mv_gauss_newton_rows_device(self, dtype, d_deriv, d_gram, gram_stride, d_gn, n_rows, n_pcs, n_inputs):
         """gn[m] = deriv[:, m].T @ gram[m] @ deriv[:, m] on the device, exactly symmetric (asynchronous;
         ``gp_mv_gauss_newton_rows_device``).  Row m's matrix is at ``d_gram + m * gram_stride`` elements; 0 = one
         matrix for all rows, which is ``mv_gauss_newton_device``."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_mv_gauss_newton_rows_device(self.h, code, d_deriv, d_gram, int(gram_stride), d_gn, int(n_rows),
+        check(self.lib.gp_mv_gauss_newton_rows_device(self.h, _dtype_code(dtype), d_deriv, d_gram, int(gram_stride), d_gn, int(n_rows),
                                                       int(n_pcs), int(n_inputs)), "gp_mv_gauss_newton_rows_device")
 
     def newton_step_device(self, dtype, d_x, d_grad, d_A, d_lambda, d_step, d_trial, d_status, n_rows, n_inputs,
@@ -646,8 +474,7 @@ class Context:
         ``(A + damping) step = -grad`` row by row by Cholesky, ``trial = clamp(x + step)``, ``status`` int32 (0, or
         the 1-based index of the failed pivot: then step = 0, trial = x).  Device pointers of ``dtype``; the prior
         pair, the bounds pair and one of ``d_step`` / ``d_trial`` may be None."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_newton_step_device(self.h, code, d_x, d_grad, d_A, d_lambda, _DAMPING[damping], d_prior_mean,
+        check(self.lib.gp_newton_step_device(self.h, _dtype_code(dtype), d_x, d_grad, d_A, d_lambda, _DAMPING[damping], d_prior_mean,
                                              d_prior_prec, d_lo, d_hi, d_step, d_trial, d_status, int(n_rows),
                                              int(n_inputs)), "gp_newton_step_device")
 
@@ -658,8 +485,7 @@ class Context:
         rows with ``state == 0`` whose trial lowers ``cost (+ prior term)`` take the trial's x, cost, grad and A and
         ``lambda * down``, the others keep theirs and take ``lambda * up``; ``state`` becomes 1 on convergence
         (``ftol``, ``xtol``).  The grad pair, the A pair, ``d_accepted`` and the prior pair may be None."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_lm_update_device(self.h, code, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A,
+        check(self.lib.gp_lm_update_device(self.h, _dtype_code(dtype), d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A,
                                            d_A_trial, d_lambda, d_status, d_state, d_accepted, d_prior_mean, d_prior_prec,
                                            float(down), float(up), float(lambda_min), float(lambda_max), float(ftol),
                                            float(xtol), int(n_rows), int(n_inputs)), "gp_lm_update_device")
@@ -669,8 +495,7 @@ class Context:
         ``cov = (A + P)^-1`` row by row by Cholesky and unit-vector solves, symmetric bit for bit, ``sigma`` the square
         roots of its diagonal, ``status`` int32 (0, or the 1-based index of the failed pivot: then cov and sigma are
         NaN).  Device pointers of ``dtype``; ``d_prior_prec`` and one of ``d_cov`` / ``d_sigma`` may be None."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_posterior_cov_device(self.h, code, d_A, d_prior_prec, d_cov, d_sigma, d_status, int(n_rows),
+        check(self.lib.gp_posterior_cov_device(self.h, _dtype_code(dtype), d_A, d_prior_prec, d_cov, d_sigma, d_status, int(n_rows),
                                                int(n_inputs)), "gp_posterior_cov_device")
 
     def newton_step_rows_device(self, dtype, d_x, d_grad, d_A, d_lambda, d_step, d_trial, d_status, n_rows, n_inputs,
@@ -679,8 +504,7 @@ class Context:
         """``newton_step_device`` with a prior per row (``gp_newton_step_rows_device``): row m's prior mean is at
         ``d_prior_mean + m * prior_mean_stride`` elements and its precision at ``d_prior_prec + m * prior_prec_stride``;
         0 = one for all rows, which is ``newton_step_device``.  The two strides are independent."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_newton_step_rows_device(self.h, code, d_x, d_grad, d_A, d_lambda, _DAMPING[damping], d_prior_mean,
+        check(self.lib.gp_newton_step_rows_device(self.h, _dtype_code(dtype), d_x, d_grad, d_A, d_lambda, _DAMPING[damping], d_prior_mean,
                                                   d_prior_prec, d_lo, d_hi, d_step, d_trial, d_status, int(n_rows),
                                                   int(n_inputs), int(prior_mean_stride), int(prior_prec_stride)),
               "gp_newton_step_rows_device")
@@ -691,8 +515,7 @@ class Context:
                               xtol=0.0, prior_mean_stride=0, prior_prec_stride=0):
         """``lm_update_device`` with a prior per row (``gp_lm_update_rows_device``); the strides as in
         ``newton_step_rows_device``."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_lm_update_rows_device(self.h, code, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A,
+        check(self.lib.gp_lm_update_rows_device(self.h, _dtype_code(dtype), d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A,
                                                 d_A_trial, d_lambda, d_status, d_state, d_accepted, d_prior_mean,
                                                 d_prior_prec, float(down), float(up), float(lambda_min), float(lambda_max),
                                                 float(ftol), float(xtol), int(n_rows), int(n_inputs),
@@ -702,8 +525,7 @@ class Context:
                                   prior_prec_stride=0):
         """``posterior_cov_device`` with a prior precision per row (``gp_posterior_cov_rows_device``): row m's is at
         ``d_prior_prec + m * prior_prec_stride`` elements; 0 = one for all rows, which is ``posterior_cov_device``."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_posterior_cov_rows_device(self.h, code, d_A, d_prior_prec, d_cov, d_sigma, d_status, int(n_rows),
+        check(self.lib.gp_posterior_cov_rows_device(self.h, _dtype_code(dtype), d_A, d_prior_prec, d_cov, d_sigma, d_status, int(n_rows),
                                                     int(n_inputs), int(prior_prec_stride)), "gp_posterior_cov_rows_device")
 
     def prior_propagate_device(self, dtype, d_A, d_prior_prec, prior_prec_stride, d_noise, noise_stride, d_next_prec,
@@ -713,8 +535,7 @@ class Context:
         chip; symmetric bit for bit; ``status`` int32 (0, k + 1 for a failed pivot of ``A + P``, D + k + 1 for one of
         ``(A + P)^-1 + Q``: then next_prec is NaN).  Device pointers of ``dtype``; ``d_prior_prec`` may be None; the
         strides are in elements, 0 = one matrix for all rows."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_prior_propagate_device(self.h, code, d_A, d_prior_prec, int(prior_prec_stride), d_noise,
+        check(self.lib.gp_prior_propagate_device(self.h, _dtype_code(dtype), d_A, d_prior_prec, int(prior_prec_stride), d_noise,
                                                  int(noise_stride), d_next_prec, d_status, int(n_rows), int(n_inputs)),
               "gp_prior_propagate_device")
 
@@ -726,27 +547,15 @@ class Context:
         (``prior_propagate_numpy``: the same algorithm in float64); never a fallback."""
         if not is_gpu:
             return prior_propagate_numpy(A, prior_prec, noise)
-        A = np.asarray(A)
-        if A.ndim != 3 or A.shape[1] != A.shape[2]:
-            raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
-        dt = np.dtype(precision if precision is not None else (np.float32 if A.dtype == np.float32 else np.float64))
-        M, D = A.shape[:2]
+        A, dt, M, D = _matrix_rows(A, precision)
         P = prec_rows(prior_prec, M, D, dt) if prior_prec is not None else None
         Q = prec_rows(noise, M, D, dt)
-        ptrs = []
-        try:
-            ptrs.append(self.to_device(np.ascontiguousarray(A, dtype=dt)))
-            ptrs.append(self.to_device(P) if P is not None else None)
-            ptrs.append(self.to_device(Q))
-            d_next, d_status = self.malloc(M * D * D * dt.itemsize), self.malloc(M * 4)
-            ptrs += [d_next, d_status]
-            self.prior_propagate_device(dt, ptrs[0], ptrs[1], row_strides(None, P)[1], ptrs[2], row_strides(None, Q)[1],
-                                        d_next, d_status, M, D)
-            return np.array(self.to_host(d_next, (M, D, D), dt)), np.array(self.to_host(d_status, (M,), np.int32))
-        finally:
-            for p in ptrs:
-                if p is not None:
-                    self.free(p)
+        with Scratch(self, dt) as scratch:
+            d_A, d_P, d_Q = scratch.up(A), scratch.up(P), scratch.up(Q)
+            d_next, d_status = scratch.alloc(M * D * D * dt.itemsize), scratch.alloc(M * 4)
+            self.prior_propagate_device(dt, d_A, d_P, row_strides(None, P)[1], d_Q, row_strides(None, Q)[1], d_next, d_status,
+                                        M, D)
+            return _download(self, d_next, (M, D, D), dt), _download(self, d_status, (M,), np.int32)
 
     def rts_smooth_device(self, dtype, d_A, d_prior_prec, prior_prec_stride, d_noise, noise_stride, d_x, d_x_next,
                           d_cov_next, d_lo, d_hi, d_x_smooth, d_cov_smooth, d_sigma_smooth, d_status, n_rows, n_inputs):
@@ -756,8 +565,7 @@ class Context:
         ``sigma_smooth`` the square roots of its diagonal, ``status`` as ``prior_propagate_device``'s (then the row's
         outputs are NaN).  Device pointers of ``dtype``; ``d_prior_prec``, the ``d_lo`` / ``d_hi`` pair and one of
         ``d_cov_smooth`` / ``d_sigma_smooth`` may be None; the strides are in elements, 0 = one matrix for all rows."""
-        code = GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
-        check(self.lib.gp_rts_smooth_device(self.h, code, d_A, d_prior_prec, int(prior_prec_stride), d_noise,
+        check(self.lib.gp_rts_smooth_device(self.h, _dtype_code(dtype), d_A, d_prior_prec, int(prior_prec_stride), d_noise,
                                             int(noise_stride), d_x, d_x_next, d_cov_next, d_lo, d_hi, d_x_smooth,
                                             d_cov_smooth, d_sigma_smooth, d_status, int(n_rows), int(n_inputs)),
               "gp_rts_smooth_device")
@@ -771,31 +579,20 @@ class Context:
         the explicit numpy branch (``rts_smooth_numpy``: the same algorithm in float64); never a fallback."""
         if not is_gpu:
             return rts_smooth_numpy(A, prior_prec, noise, x, x_next, cov_next, bounds)
-        A = np.asarray(A)
-        if A.ndim != 3 or A.shape[1] != A.shape[2]:
-            raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
-        dt = np.dtype(precision if precision is not None else (np.float32 if A.dtype == np.float32 else np.float64))
-        M, D = A.shape[:2]
+        A, dt, M, D = _matrix_rows(A, precision)
         P = prec_rows(prior_prec, M, D, dt) if prior_prec is not None else None
         Q = prec_rows(noise, M, D, dt)
         ins = [A, P, Q, np.reshape(x, (M, D)), np.reshape(x_next, (M, D)), np.reshape(cov_next, (M, D, D))]
         ins += [np.reshape(b, D) for b in bounds] if bounds is not None else [None, None]
-        ptrs = []
-        try:
-            for a in ins:
-                ptrs.append(self.to_device(np.ascontiguousarray(a, dtype=dt)) if a is not None else None)
+        with Scratch(self, dt) as scratch:
+            d_A, d_P, d_Q, d_x, d_xn, d_cn, d_lo, d_hi = [scratch.up(a) for a in ins]
             isz = dt.itemsize
-            d_xs, d_cov, d_sigma, d_status = (self.malloc(M * D * isz), self.malloc(M * D * D * isz),
-                                              self.malloc(M * D * isz), self.malloc(M * 4))
-            ptrs += [d_xs, d_cov, d_sigma, d_status]
-            self.rts_smooth_device(dt, ptrs[0], ptrs[1], row_strides(None, P)[1], ptrs[2], row_strides(None, Q)[1],
-                                   ptrs[3], ptrs[4], ptrs[5], ptrs[6], ptrs[7], d_xs, d_cov, d_sigma, d_status, M, D)
-            return (np.array(self.to_host(d_xs, (M, D), dt)), np.array(self.to_host(d_cov, (M, D, D), dt)),
-                    np.array(self.to_host(d_sigma, (M, D), dt)), np.array(self.to_host(d_status, (M,), np.int32)))
-        finally:
-            for p in ptrs:
-                if p is not None:
-                    self.free(p)
+            d_xs, d_cov, d_sigma, d_status = (scratch.alloc(M * D * isz), scratch.alloc(M * D * D * isz),
+                                              scratch.alloc(M * D * isz), scratch.alloc(M * 4))
+            self.rts_smooth_device(dt, d_A, d_P, row_strides(None, P)[1], d_Q, row_strides(None, Q)[1], d_x, d_xn, d_cn,
+                                   d_lo, d_hi, d_xs, d_cov, d_sigma, d_status, M, D)
+            return (_download(self, d_xs, (M, D), dt), _download(self, d_cov, (M, D, D), dt),
+                    _download(self, d_sigma, (M, D), dt), _download(self, d_status, (M,), np.int32))
 
     def posterior_cov(self, A, prior_prec=None, precision=None, is_gpu=True):
         """``(cov (M, D, D), sigma (M, D), status (M,) int32)`` of the posterior covariance ``(A + P)^-1`` for the host
@@ -806,28 +603,17 @@ class Context:
         fallback."""
         if not is_gpu:
             return posterior_cov_numpy(A, prior_prec)
-        A = np.asarray(A)
-        if A.ndim != 3 or A.shape[1] != A.shape[2]:
-            raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
-        dt = np.dtype(precision if precision is not None else (np.float32 if A.dtype == np.float32 else np.float64))
-        M, D = A.shape[:2]
-        ptrs = []
-        try:
-            ptrs.append(self.to_device(np.ascontiguousarray(A, dtype=dt)))
-            P = prec_rows(prior_prec, M, D, dt) if prior_prec is not None else None
-            ptrs.append(self.to_device(P) if P is not None else None)
-            d_cov, d_sigma, d_status = self.malloc(M * D * D * dt.itemsize), self.malloc(M * D * dt.itemsize), self.malloc(M * 4)
-            ptrs += [d_cov, d_sigma, d_status]
+        A, dt, M, D = _matrix_rows(A, precision)
+        P = prec_rows(prior_prec, M, D, dt) if prior_prec is not None else None
+        with Scratch(self, dt) as scratch:
+            d_A, d_P = scratch.up(A), scratch.up(P)
+            d_cov, d_sigma, d_status = scratch.alloc(M * D * D * dt.itemsize), scratch.alloc(M * D * dt.itemsize), scratch.alloc(M * 4)
             if P is not None and P.ndim == 3:
-                self.posterior_cov_rows_device(dt, ptrs[0], ptrs[1], d_cov, d_sigma, d_status, M, D, D * D)
+                self.posterior_cov_rows_device(dt, d_A, d_P, d_cov, d_sigma, d_status, M, D, D * D)
             else:
-                self.posterior_cov_device(dt, ptrs[0], ptrs[1], d_cov, d_sigma, d_status, M, D)
-            return (np.array(self.to_host(d_cov, (M, D, D), dt)), np.array(self.to_host(d_sigma, (M, D), dt)),
-                    np.array(self.to_host(d_status, (M,), np.int32)))
-        finally:
-            for p in ptrs:
-                if p is not None:
-                    self.free(p)
+                self.posterior_cov_device(dt, d_A, d_P, d_cov, d_sigma, d_status, M, D)
+            return (_download(self, d_cov, (M, D, D), dt), _download(self, d_sigma, (M, D), dt),
+                    _download(self, d_status, (M,), np.int32))
 
     def newton_step(self, x, grad, A, lam, damping="diagonal", prior=None, bounds=None, precision=None, is_gpu=True):
         """``(step, trial, status)`` of the damped Newton step for host arrays ``x`` (M, D), ``grad`` (M, D), ``A``
@@ -843,33 +629,23 @@ class Context:
         x = np.asarray(x)
         if x.ndim != 2:
             raise ValueError("x must be (n_rows, n_inputs)")
-        dt = np.dtype(precision if precision is not None else (np.float32 if x.dtype == np.float32 else np.float64))
+        dt = _device_dtype(precision, x)
         M, D = x.shape
-        host = [np.ascontiguousarray(x, dtype=dt), np.ascontiguousarray(grad, dtype=dt).reshape(M, D),
-                np.ascontiguousarray(A, dtype=dt).reshape(M, D, D),
-                np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=dt), (M,)))]
+        host = [x, np.reshape(grad, (M, D)), np.reshape(A, (M, D, D)), np.broadcast_to(np.asarray(lam, dtype=dt), (M,))]
         host += list(prior_rows(prior, M, D, dt)) if prior is not None else [None, None]
         strides = row_strides(host[4], host[5])
-        host += [np.ascontiguousarray(bounds[0], dtype=dt).reshape(D), np.ascontiguousarray(bounds[1], dtype=dt).reshape(D)] \
-            if bounds is not None else [None, None]
-        ptrs = []
-        try:
-            for a in host:
-                ptrs.append(self.to_device(a) if a is not None else None)
-            d_step, d_trial, d_status = self.malloc(M * D * dt.itemsize), self.malloc(M * D * dt.itemsize), self.malloc(M * 4)
-            ptrs += [d_step, d_trial, d_status]
+        host += [np.reshape(b, D) for b in bounds] if bounds is not None else [None, None]
+        with Scratch(self, dt) as scratch:
+            d_x, d_grad, d_A, d_lam, d_x0, d_P, d_lo, d_hi = [scratch.up(a) for a in host]
+            d_step, d_trial, d_status = scratch.alloc(M * D * dt.itemsize), scratch.alloc(M * D * dt.itemsize), scratch.alloc(M * 4)
             if any(strides):
-                self.newton_step_rows_device(dt, ptrs[0], ptrs[1], ptrs[2], ptrs[3], d_step, d_trial, d_status, M, D,
-                                             damping, ptrs[4], ptrs[5], ptrs[6], ptrs[7], *strides)
+                self.newton_step_rows_device(dt, d_x, d_grad, d_A, d_lam, d_step, d_trial, d_status, M, D, damping, d_x0, d_P,
+                                             d_lo, d_hi, *strides)
             else:
-                self.newton_step_device(dt, ptrs[0], ptrs[1], ptrs[2], ptrs[3], d_step, d_trial, d_status, M, D, damping,
-                                        ptrs[4], ptrs[5], ptrs[6], ptrs[7])
-            return (np.array(self.to_host(d_step, (M, D), dt)), np.array(self.to_host(d_trial, (M, D), dt)),
-                    np.array(self.to_host(d_status, (M,), np.int32)))
-        finally:
-            for p in ptrs:
-                if p is not None:
-                    self.free(p)
+                self.newton_step_device(dt, d_x, d_grad, d_A, d_lam, d_step, d_trial, d_status, M, D, damping, d_x0, d_P,
+                                        d_lo, d_hi)
+            return (_download(self, d_step, (M, D), dt), _download(self, d_trial, (M, D), dt),
+                    _download(self, d_status, (M,), np.int32))
 
     def likelihood_batch(self, thetas, inputs, targets, want_inverse=False):
         """cost (E,), grad (E, D+2) [and invQ (E, N, N), invQt (E, N)] of the training
@@ -969,7 +745,7 @@ class Model:
         M = testing.shape[0]
         if M:
             check(self.ctx.lib.gp_predict_host(
-                self.ctx.h, self.h, GP_F64 if testing.dtype == np.float64 else GP_F32, _ptr(testing), _ptr(mu),
+                self.ctx.h, self.h, _dtype_code(testing.dtype), _ptr(testing), _ptr(mu),
                 _ptr(var), _ptr(deriv), M, int(deriv_layout), int(max_block_rows)), "gp_predict_host")
         return mu, var, deriv
 
@@ -991,7 +767,7 @@ class Model:
         M = testing.shape[0]
         if M:
             check(self.ctx.lib.gp_predict_mean_grad_host(
-                self.ctx.h, self.h, GP_F64 if testing.dtype == np.float64 else GP_F32, _ptr(testing),
+                self.ctx.h, self.h, _dtype_code(testing.dtype), _ptr(testing),
                 _ptr(mu), _ptr(deriv), M, int(deriv_layout), int(max_block_rows)), "gp_predict_mean_grad_host")
         return mu, deriv
 
@@ -1151,7 +927,7 @@ class BatchModel(Model):
             raise ValueError("out must be a writeable C-contiguous %s %s array" % (shape, hdt))
         if M:
             check(self.ctx.lib.gp_hessian_weighted_host(
-                self.ctx.h, self.h, GP_F64 if hdt == np.float64 else GP_F32, _ptr(testing), _ptr(weights),
+                self.ctx.h, self.h, _dtype_code(hdt), _ptr(testing), _ptr(weights),
                 _ptr(res), M), "gp_hessian_weighted_host")
         return res
 
@@ -1198,7 +974,7 @@ class BatchModel(Model):
         wr = np.empty((self.n_emulators, M), hdt) if return_residual else None
         if M:
             check(self.ctx.lib.gp_band_misfit_host(
-                self.ctx.h, self.h, GP_F64 if hdt == np.float64 else GP_F32, _ptr(testing), _ptr(obs), os_[0], os_[1],
+                self.ctx.h, self.h, _dtype_code(hdt), _ptr(testing), _ptr(obs), os_[0], os_[1],
                 _ptr(weights) if weights is not None else None, ws[0], ws[1], _ptr(cost), _ptr(grad),
                 _ptr(wr) if wr is not None else None, _ptr(second) if second_order == "gauss_newton" else None,
                 _ptr(second) if second_order == "full" else None, M), "gp_band_misfit_host")
@@ -1232,7 +1008,7 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
     k, wg, rwg, rpi = c_int(0), c_int(0), c_int(0), c_int(0)
     items, ritems = c_i64(0), c_i64(0)
     check(load().gp_launch_plan(
-        code, GP_F64 if np.dtype(precision) == np.float64 else GP_F32, int(n_train), int(n_pcs if recon else n_inputs),
+        code, _dtype_code(precision), int(n_train), int(n_pcs if recon else n_inputs),
         int(n_emulators), int(n_rows), int(n_bands if recon else 0), int(compute_units), int(bool(aligned16)),
         ctypes.byref(k), ctypes.byref(items), ctypes.byref(wg), ctypes.byref(ritems), ctypes.byref(rwg),
         ctypes.byref(rpi)), "gp_launch_plan")
@@ -1250,7 +1026,7 @@ def pack_model(expX, inputs, invQt, invQ, precision=np.float64):
     invQt = np.ascontiguousarray(invQt, dtype=dt).ravel()
     invQ = np.ascontiguousarray(invQ, dtype=dt)
     kd, knb, xl, fl = c_int(0), c_int(0), c_i64(0), c_i64(0)
-    check(lib.gp_pack_sizes(GP_F64 if dt == np.float64 else GP_F32, N, D, ctypes.byref(kd),
+    check(lib.gp_pack_sizes(_dtype_code(dt), N, D, ctypes.byref(kd),
                             ctypes.byref(knb), ctypes.byref(xl), ctypes.byref(fl)), "gp_pack_sizes")
     xa = np.zeros(xl.value, dt)
     fr = np.zeros(fl.value, dt)

@@ -81,28 +81,7 @@ def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, r
     return out
 
 
-class Scratch(object):
-    """Device arrays of one call, freed together on exit -- also when the call raises half way: ``up(array)`` uploads
-    in the call's precision, ``alloc(nbytes)`` reserves."""
-
-    def __init__(self, ctx, dt):
-        self.ctx, self.dt, self.held = ctx, dt, []
-
-    def up(self, a):
-        self.held.append(self.ctx.to_device(np.ascontiguousarray(a, dtype=self.dt)))
-        return self.held[-1]
-
-    def alloc(self, nbytes):
-        self.held.append(self.ctx.malloc(max(1, nbytes)))
-        return self.held[-1]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        held, self.held = self.held, []
-        for p in held:
-            self.ctx.free(p)
+Scratch = _lib.Scratch     # the device arrays of one call (the loop's callers open it; tests take it from here)
 
 
 def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov, misfit, next_prior=None,

@@ -126,7 +126,7 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
               ("gp_band_misfit_tu.hip", "band_misfit", []), ("gp_newton_tu.hip", "newton", []),
               ("gp_train_tu.hip", "train", [])]
     # the host units (gp_host.hpp lists them)
-    units += [("gp_%s.hip" % u, "gp_" + u, []) for u in ("ctx", "model", "device", "host_path", "folds", "mv")]
+    units += [("gp_%s.hip" % u, "gp_" + u, []) for u in ("ctx", "model", "device", "solve", "host_path", "folds", "mv")]
     tasks = [[HIPCC] + FLAGS + defines + extra + ["-c", os.path.join(CSRC, src), "-o", os.path.join(OBJ, name + ".o")]
              for src, name, extra in units]
     # plain host C++ (no device pass): the content digest with its per-ISA clones

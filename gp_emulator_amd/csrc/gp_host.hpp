@@ -2,7 +2,9 @@
 // plumbing, the dtype dispatch, the argument checks, and the functions one unit defines for another.
 //   gp_ctx.hip        the error buffer, contexts, device memory, events, the training objective
 //   gp_model.hip      kernel choice, packing, models and the context's model cache
-//   gp_device.hip     launch sizing; predict, Hessian, Newton step, LM update, posterior covariance on device buffers
+//   gp_device.hip     launch sizing; predict and Hessian on device buffers
+//   gp_solve.hip      the small dense solves on device buffers: Newton step, LM update, posterior covariance, prior
+//                     propagation, smoother (no model)
 //   gp_host_path.hip  predict and Hessian on host arrays: the slab pipeline, the pinned-array path
 //   gp_folds.hip      folds over the emulators of a batch: the weighted Hessian, the per-band misfit
 //   gp_mv.hip         the multivariate emulator: reconstruction, misfit, per-row Gram matrices, content digest

@@ -19,24 +19,14 @@
 // own lanes from its own data only, so its result does not depend on the other rows, on its place in the call or on
 // the grid, and two calls agree bit for bit.
 //
-// Geometry: a sub-group of G lanes per row, G = 16 for D <= 16 and 32 beyond, so a wave holds 4 or 2 rows and a
-// 256-thread workgroup 16 or 8; a plain grid of ceil(rows / that) workgroups.  A wave's rows are one contiguous run of
-// (64 / G) D^2 elements of A: the wave reads it with consecutive lanes on consecutive elements and leaves the lower
-// triangles in LDS, packed (row j of a matrix starts at j (j + 1) / 2), as doubles.  Lane j of a sub-group owns
-// matrix row j.  In column k of the factorisation the lanes j >= k each run their chain from their own packed row
-// and from row k (one address for the whole sub-group: a broadcast); the pivot reaches the other lanes by a
-// shuffle.  LDS banking: ds_read_b64 takes the bank from (address / 4) % 64, i.e. the double index mod 32, and
-// conflicts count inside a 32-lane half.  The lanes of a sub-group read column k at j (j + 1) / 2 + k, and the
-// triangular numbers are a permutation of the residues mod 32 (and mod 16), so 32 lanes of one matrix never meet;
-// two 16-lane sub-groups in one half stay apart because the matrix pitch is padded to 16 mod 32 doubles, which maps
-// the residues of the first sixteen triangular numbers onto their complement.  The packing is the padding: no
-// square pitch is stored.  Only the factorisation passes data between lanes through LDS (row k is written by lane
-// k, read by all), and always inside one wave, whose LDS operations execute in order: a wave-level barrier (a
-// compiler fence, no s_barrier) per column is all the synchronisation there is.  The forward substitution is
-// column-oriented (y_k by shuffle, every lane one fma per column: D steps); the backward substitution's ascending
-// order makes z_j start from the term of z_{j+1}, the last one to become known, so it is a serial chain of D^2 / 2
-// fmas that every lane of the sub-group runs redundantly (L[k][j] by broadcast reads, z_k by shuffle) -- as long as
-// the factorisation's own critical path.
+// Geometry: the sub-group of G lanes per row of gp_dense_device.hpp (4 or 2 rows per wave) in workgroups of 256 threads:
+// 16 or 8 rows per workgroup, a plain grid of ceil(rows / that) workgroups.  LDS: one packed triangle per row at pitch
+// dense_pitch(D), as doubles: 33,792 bytes per workgroup at D = 32.  Lane j of a sub-group owns matrix row j; the
+// factorisation is dense_factor's loop, written out here (its banking and its wave-level synchronisation are told in
+// that header).  The forward substitution is column-oriented (y_k by shuffle, every lane one fma per column: D steps);
+// the backward substitution's ascending order makes z_j start from the term of z_{j+1}, the last one to become known, so
+// it is a serial chain of D^2 / 2 fmas that every lane of the sub-group runs redundantly (L[k][j] by broadcast reads, z_k
+// by shuffle) -- as long as the factorisation's own critical path.
 //
 // lm_update_kernel<T>: one row per wave, four rows per workgroup, plain grid.  For a row with state == 0,
 //   F   = cost       + 1/2 (x - x0)^T P (x - x0)          (the prior term only with P; double; sum_i d_i (sum_c P_ic d_c),
@@ -51,10 +41,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gp_dense_device.hpp"
+
 namespace gpk {
 
 constexpr int kNewtonThreads = 256;
-constexpr int kNewtonMaxD = 32;
 
 template <typename T>
 struct NewtonArgs {
@@ -99,60 +90,15 @@ struct LmUpdateArgs {
   int d;
 };
 
-// lanes per row, rows per workgroup, and the LDS pitch of one packed lower triangle in doubles (16 mod 32: see above)
-__host__ __device__ inline int newton_group(int d) { return d <= 16 ? 16 : 32; }
-__host__ __device__ inline int newton_rows_per_wg(int d) { return kNewtonThreads / newton_group(d); }
-__host__ __device__ inline int newton_tri(int j) { return j * (j + 1) / 2; }
-__host__ __device__ inline int newton_pitch(int d) {
-  const int n = newton_tri(d);
-  return n + ((16 - n % 32) + 32) % 32;
-}
-inline size_t newton_lds_bytes(int d) { return (size_t)newton_rows_per_wg(d) * newton_pitch(d) * sizeof(double); }
-
-// LDS written by one lane of a wave and read by another lane of the same wave: the operations execute in order,
-// the compiler must not move them across this point
-__device__ inline void newton_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A wave's run of nr matrices at row0, consecutive lanes on consecutive elements: the lower triangles (+ P) to the packed
-// triangles Lw (newton_step_kernel, posterior_cov_kernel and prior_propagate_kernel stage alike).  ROWS = false is the
-// shared prior, element e of the one matrix; ROWS = true reads the global row's, row0 + r.  The caller branches once per
-// wave on the stride, so a shared prior costs the address arithmetic it always did.
-template <typename T, bool ROWS>
-__device__ inline void newton_stage_run(double* Lw, const T* A, const T* prior_prec, long long prior_prec_stride, long long row0,
-                                        int nr, int D, int S, int lane) {
-  const int DD = D * D;
-  const T* Ag = A + row0 * DD;
-  const T* Pw = ROWS ? prior_prec + row0 * prior_prec_stride : prior_prec;      // (the wave's first row's)
-  const int n = nr * DD;
-  for (int idx = lane; idx < n; idx += 64) {
-    const int r = idx / DD, e = idx - r * DD;
-    const int i = e / D, c = e - i * D;
-    if (c <= i) {
-      double v = (double)Ag[idx];
-      if (prior_prec) v += (double)(ROWS ? Pw[r * prior_prec_stride + e] : Pw[e]);
-      Lw[r * S + newton_tri(i) + c] = v;
-    }
-  }
-}
-
-template <typename T>
-__device__ inline void newton_stage(double* Lw, const T* A, const T* prior_prec, long long prior_prec_stride, long long row0,
-                                    int nr, int D, int S, int lane) {
-  if (prior_prec_stride == 0)
-    newton_stage_run<T, false>(Lw, A, prior_prec, 0, row0, nr, D, S, lane);
-  else
-    newton_stage_run<T, true>(Lw, A, prior_prec, prior_prec_stride, row0, nr, D, S, lane);
-}
+// rows per workgroup and its LDS: one packed triangle per row
+__host__ __device__ inline int newton_rows_per_wg(int d) { return kNewtonThreads / dense_group(d); }
+inline size_t newton_lds_bytes(int d) { return (size_t)newton_rows_per_wg(d) * dense_pitch(d) * sizeof(double); }
 
 template <typename T>
 __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<T> p) {
   extern __shared__ double newton_lds[];
   const int D = p.d;
-  const int G = newton_group(D), S = newton_pitch(D);
+  const int G = dense_group(D), S = dense_pitch(D);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int R = 64 / G;                                     // rows of a wave
   const long long row0 = ((long long)blockIdx.x * (kNewtonThreads / 64) + wave) * R;
@@ -161,15 +107,15 @@ __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<
   double* Lw = newton_lds + wave * R * S;                   // this wave's matrices
 
   // the wave's run of A, consecutive lanes on consecutive elements; the lower triangles (+ P) to LDS
-  newton_stage(Lw, p.A, p.prior_prec, p.prior_prec_stride, row0, nr, D, S, lane);
-  newton_wave_sync();
+  dense_stage(Lw, p.A, p.prior_prec, p.prior_prec_stride, row0, nr, D, S, lane);
+  dense_wave_sync();
 
   const int r = lane / G, j = lane - r * G;                 // matrix row j of the wave's row r
   const long long m = row0 + r;
   const bool act = j < D;                                   // (every index below stays inside the row's triangle)
   const bool live = act && r < nr;
   double* L = Lw + r * S;
-  const int tj = newton_tri(j);
+  const int tj = dense_tri(j);
 
   double xj = 0.0, acc = 0.0;
   if (live) {
@@ -190,12 +136,12 @@ __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<
     L[tj + j] = p.diagonal ? fma(lam, a, a) : a + lam;      // (read again by this lane only: no barrier)
   }
 
-  // L L^T = A', column after column
+  // L L^T = A': dense_factor written out -- called, it takes 62 VGPRs for 40 and measured up to 1.6 % slower at D = 11
   int bad = 0;
   for (int k = 0; k < D; ++k) {
     double s = 0.0;
     if (act && j >= k) {
-      const double* Lk = L + newton_tri(k);
+      const double* Lk = L + dense_tri(k);
       s = L[tj + k];
       for (int q = 0; q < k; ++q) s = fma(-L[tj + q], Lk[q], s);
     }
@@ -203,7 +149,7 @@ __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<
     if (bad == 0 && (!(piv > 0.0) || !isfinite(piv))) bad = k + 1;
     const double dk = sqrt(piv);
     if (act && j >= k) L[tj + k] = j == k ? dk : s / dk;
-    newton_wave_sync();
+    dense_wave_sync();
   }
 
   // y = L^-1 g': lane k finishes y_k, the lanes below take its term
@@ -217,7 +163,7 @@ __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<
   double z = 0.0;
   for (int i = D - 1; i >= 0; --i) {
     double a = __shfl(acc, i, G);
-    for (int k = i + 1; k < D; ++k) a = fma(-L[newton_tri(k) + i], __shfl(z, k, G), a);
+    for (int k = i + 1; k < D; ++k) a = fma(-L[dense_tri(k) + i], __shfl(z, k, G), a);
     a = a / __shfl(djj, i, G);
     if (j == i) z = a;
   }

@@ -8,64 +8,48 @@
 
 namespace gpk {
 
-// plain grids sized by the work, as the band misfit's: 16 or 8 rows per workgroup (a sub-group of lanes per row)
-template <typename T>
-hipError_t launch_newton_step(const NewtonArgs<T>& a, hipStream_t stream) {
+// Every launch here is a plain grid sized by the rows: nothing for no rows, d within the kernels' range,
+// ceil(rows / rows_per_wg) workgroups numbered in 31 bits, the launch, and what the runtime says of it.
+template <typename Args>
+static hipError_t launch_rows(void (*kernel)(Args), const Args& a, int rows_per_wg, int threads, size_t lds_bytes,
+                              hipStream_t stream) {
   if (a.rows <= 0) return hipSuccess;
   if (a.d < 1 || a.d > kNewtonMaxD) return hipErrorInvalidValue;
-  const int per_wg = newton_rows_per_wg(a.d);
-  const long long blocks = (a.rows + per_wg - 1) / per_wg;
+  const long long blocks = (a.rows + rows_per_wg - 1) / rows_per_wg;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((newton_step_kernel<T>), dim3((unsigned)blocks), dim3(kNewtonThreads), newton_lds_bytes(a.d), stream, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), lds_bytes, stream, a);
   return hipGetLastError();
+}
+
+// 16 or 8 rows per workgroup (a sub-group of lanes per row)
+template <typename T>
+hipError_t launch_newton_step(const NewtonArgs<T>& a, hipStream_t stream) {
+  return launch_rows(newton_step_kernel<T>, a, newton_rows_per_wg(a.d), kNewtonThreads, newton_lds_bytes(a.d), stream);
 }
 
 // a wave per row
 template <typename T>
 hipError_t launch_lm_update(const LmUpdateArgs<T>& a, hipStream_t stream) {
-  if (a.rows <= 0) return hipSuccess;
-  if (a.d < 1 || a.d > kNewtonMaxD) return hipErrorInvalidValue;
-  const int per_wg = kNewtonThreads / 64;
-  const long long blocks = (a.rows + per_wg - 1) / per_wg;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((lm_update_kernel<T>), dim3((unsigned)blocks), dim3(kNewtonThreads), 0, stream, a);
-  return hipGetLastError();
+  return launch_rows(lm_update_kernel<T>, a, kNewtonThreads / 64, kNewtonThreads, 0, stream);
 }
 
 // 8 or 4 rows per workgroup: half the step kernel's, for the second triangle in LDS (33,792 bytes at D = 32)
 template <typename T>
 hipError_t launch_posterior_cov(const PosteriorCovArgs<T>& a, hipStream_t stream) {
-  if (a.rows <= 0) return hipSuccess;
-  if (a.d < 1 || a.d > kNewtonMaxD) return hipErrorInvalidValue;
-  const int per_wg = post_cov_rows_per_wg(a.d);
-  const long long blocks = (a.rows + per_wg - 1) / per_wg;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((posterior_cov_kernel<T>), dim3((unsigned)blocks), dim3(kPostCovThreads), post_cov_lds_bytes(a.d), stream, a);
-  return hipGetLastError();
+  return launch_rows(posterior_cov_kernel<T>, a, post_cov_rows_per_wg(a.d), kPostCovThreads, post_cov_lds_bytes(a.d), stream);
 }
 
 // the covariance kernel's geometry and LDS: two inversions on the same two triangles
 template <typename T>
 hipError_t launch_prior_propagate(const PriorPropagateArgs<T>& a, hipStream_t stream) {
-  if (a.rows <= 0) return hipSuccess;
-  if (a.d < 1 || a.d > kNewtonMaxD) return hipErrorInvalidValue;
-  const int per_wg = post_cov_rows_per_wg(a.d);
-  const long long blocks = (a.rows + per_wg - 1) / per_wg;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((prior_propagate_kernel<T>), dim3((unsigned)blocks), dim3(kPostCovThreads), post_cov_lds_bytes(a.d), stream, a);
-  return hipGetLastError();
+  return launch_rows(prior_propagate_kernel<T>, a, prior_propagate_rows_per_wg(a.d), kPriorPropagateThreads,
+                     prior_propagate_lds_bytes(a.d), stream);
 }
 
-// one wave per workgroup, 4 or 2 rows: three triangles and two full matrices per row in LDS (58,624 bytes at D = 32)
+// one wave per workgroup, 4 or 2 rows: two triangles and two full matrices per row in LDS (50,176 bytes at D = 32)
 template <typename T>
 hipError_t launch_rts_smooth(const RtsSmoothArgs<T>& a, hipStream_t stream) {
-  if (a.rows <= 0) return hipSuccess;
-  if (a.d < 1 || a.d > kNewtonMaxD) return hipErrorInvalidValue;
-  const int per_wg = rts_rows_per_wg(a.d);
-  const long long blocks = (a.rows + per_wg - 1) / per_wg;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((rts_smooth_kernel<T>), dim3((unsigned)blocks), dim3(kRtsThreads), rts_lds_bytes(a.d), stream, a);
-  return hipGetLastError();
+  return launch_rows(rts_smooth_kernel<T>, a, rts_rows_per_wg(a.d), kRtsThreads, rts_lds_bytes(a.d), stream);
 }
 
 template hipError_t launch_newton_step<float>(const NewtonArgs<float>&, hipStream_t);

@@ -5,9 +5,9 @@
 // rts_smooth_kernel<T>, for every row m (D = n_inputs <= 32, a run-time argument):
 //
 //   A' = A[m] (+ P[m])                    the date's data-term matrix and the prior precision it was retrieved with
-//   C  = A'^-1                            filtered covariance     } prior_propagate_kernel as it is: newton_stage,
-//   S  = C + Q[m]                         predicted covariance    } post_cov_factor, post_cov_solve, prior_stage_noise --
-//   N  = S^-1                                                     } the same functions, so the same doubles
+//   C  = A'^-1                            filtered covariance     } what prior_propagate_kernel computes, by the same
+//   S  = C + Q[m]                         predicted covariance    } functions (dense_stage, dense_factor, dense_solve,
+//   N  = S^-1                                                     } dense_stage_noise), so the same doubles
 //   G  = C N                              smoother gain
 //   d  = x_next[m] - x[m]                 d_j one subtraction of the two inputs as doubles
 //   x_smooth[m] = clamp(x[m] + G d, lo, hi)        the step kernel's clamp on the double; without lo / hi x + G d
@@ -25,30 +25,29 @@
 // computed by its own sub-group from its own data only, so its result does not depend on the other rows, on its place in
 // the call or on the grid; two calls agree bit for bit, and so do stride 0 and repeated arrays (the same loads' values).
 //
-// Geometry: the covariance kernel's sub-group of G lanes per row (16 for D <= 16, 32 beyond: 4 or 2 rows per wave) and its
-// wave-level barriers only; ONE WAVE PER WORKGROUP (64 threads), a plain grid of ceil(rows / (64 / G)) workgroups: nothing
-// synchronises across waves, and the smaller workgroup lets the LDS of a CU be dealt out wave by wave.  In the
-// inversions lane j is the covariance kernel's lane j.  In the products lane i owns ROW i of G, of F and of K: G_i: and
-// F_i: are written and (F: only) read by lane i; what a chain takes from elsewhere (N_kj, Delta_lk, G_jk) is one address
-// for the whole sub-group, a broadcast.
+// Geometry: the sub-group of G lanes per row of gp_dense_device.hpp (4 or 2 rows per wave) and its wave-level barriers
+// only; ONE WAVE PER WORKGROUP (64 threads), a plain grid of ceil(rows / (64 / G)) workgroups: nothing synchronises across
+// waves, and the smaller workgroup lets the LDS of a CU be dealt out wave by wave.  In the inversions lane j is on matrix
+// row j, then on column j of the inverse.  In the products lane i owns ROW i of G, of F and of K: G_i: and F_i: are written
+// and (F: only) read by lane i; what a chain takes from elsewhere (N_kj, Delta_lk, G_jk) is one address for the whole
+// sub-group, a broadcast.
 //
-// LDS per row, doubles: two packed triangles at the covariance kernel's pitch S = newton_pitch(D) -- L (A', then S, then
-// their factors; after the second solve Delta; after F is formed C_s, from which the store mirrors) and W (C, kept to
-// the end) -- and two full matrices Gt, Ft at pitch FP = rts_full_pitch(D) >= S, stored TRANSPOSED and dense:
-// Gt[l * D + i] = G_il.  Both are free during the inversions and lend their space: Delta is formed while S is still
-// whole, as a packed triangle in Gt, and copied to L once the second factor is dead; the second inversion solves N as a
-// packed triangle into Ft, where it lives until F overwrites it (G is formed by then).  A wave keeps its rows' L
-// triangles together, then the W, the Gt and the Ft of its rows (neighbours of one kind keep that kind's pitch; N in Ft
-// has the pitch FP, 16 mod 32 as S is, so the covariance kernel's argument for W holds for it unchanged).
+// LDS per row, doubles: two packed triangles at the pitch S = dense_pitch(D) -- L (A', then S, then their factors; after
+// the second solve Delta; after F is formed C_s, from which the store mirrors) and W (C, kept to the end) -- and two full
+// matrices Gt, Ft at pitch FP = rts_full_pitch(D) >= S, stored TRANSPOSED and dense: Gt[l * D + i] = G_il.  Both are free
+// during the inversions and lend their space: Delta is formed while S is still whole, as a packed triangle in Gt, and
+// copied to L once the second factor is dead; the second inversion solves N as a packed triangle into Ft, where it lives
+// until F overwrites it (G is formed by then).  A wave keeps its rows' L triangles together, then the W, the Gt and the Ft
+// of its rows (neighbours of one kind keep that kind's pitch; N in Ft has the pitch FP, 16 mod 32 as S is, so the shared
+// header's argument for W holds for it unchanged).
 //
-// Banking (ds_read_b64: bank = double index mod 32, conflicts inside a 32-lane half): the triangles are read as the
-// covariance kernel reads them -- broadcasts, or C_ik over the lanes i at tri(max(i, k)) + min(i, k): a run of
-// consecutive doubles for i < k, then triangular numbers for i >= k (a permutation of the residues mod 32); the two runs
-// may meet 2-way, as in that kernel's store.  The full matrices are only ever touched as Gt[l * D + i] / Ft[k * D + i]
-// by the lanes i of a sub-group at one (l or k): D <= 32 consecutive doubles, so no two lanes of a matrix meet whatever D
-// is -- no padding inside a matrix -- or as G_jk at one address per sub-group.  Two 16-lane sub-groups share a half when
-// D <= 16: FP is padded to 16 mod 32 (FP = D^2 rounded up to that), as S is, so the neighbouring rows' runs of at most
-// 16 consecutive doubles, and their broadcast addresses, lie 16 banks apart and never meet.
+// Banking of what is this kernel's own (the triangles are read as gp_dense_device.hpp tells -- broadcasts, or C_ik over the
+// lanes i at tri(max(i, k)) + min(i, k): a run of consecutive doubles for i < k, then triangular numbers for i >= k, which
+// may meet 2-way, as in the store): the full matrices are only ever touched as Gt[l * D + i] / Ft[k * D + i] by the lanes
+// i of a sub-group at one (l or k): D <= 32 consecutive doubles, so no two lanes of a matrix meet whatever D is -- no
+// padding inside a matrix -- or as G_jk at one address per sub-group.  Two 16-lane sub-groups share a half when D <= 16:
+// FP is padded to 16 mod 32 (FP = D^2 rounded up to that), as S is, so the neighbouring rows' runs of at most 16
+// consecutive doubles, and their broadcast addresses, lie 16 banks apart and never meet.
 //
 //   D    S     FP    per row 2 S + 2 FP   rows / wave   LDS per workgroup   workgroups (= waves) per CU of 160 KB
 //   11   80    144   448 doubles          4             14,336 bytes        11
@@ -60,7 +59,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gp_prior_propagate_kernel.hpp"
+#include "gp_dense_device.hpp"
 
 namespace gpk {
 
@@ -86,20 +85,20 @@ struct RtsSmoothArgs {
   int d;
 };
 
-// pitch of one full D x D matrix in doubles: D^2 rounded up to 16 mod 32 (see above); never below newton_pitch(D)
+// pitch of one full D x D matrix in doubles: D^2 rounded up to 16 mod 32 (see above); never below dense_pitch(D)
 __host__ __device__ inline int rts_full_pitch(int d) {
   const int n = d * d;
   return n + ((16 - n % 32) + 32) % 32;
 }
-__host__ __device__ inline int rts_rows_per_wg(int d) { return kRtsThreads / newton_group(d); }
-__host__ __device__ inline int rts_row_doubles(int d) { return 2 * newton_pitch(d) + 2 * rts_full_pitch(d); }
+__host__ __device__ inline int rts_rows_per_wg(int d) { return kRtsThreads / dense_group(d); }
+__host__ __device__ inline int rts_row_doubles(int d) { return 2 * dense_pitch(d) + 2 * rts_full_pitch(d); }
 inline size_t rts_lds_bytes(int d) { return (size_t)rts_rows_per_wg(d) * rts_row_doubles(d) * sizeof(double); }
 
 template <typename T>
 __global__ __launch_bounds__(kRtsThreads) void rts_smooth_kernel(RtsSmoothArgs<T> p) {
   extern __shared__ double rts_smooth_lds[];
   const int D = p.d, DD = D * D;
-  const int G = newton_group(D), S = newton_pitch(D), FP = rts_full_pitch(D);
+  const int G = dense_group(D), S = dense_pitch(D), FP = rts_full_pitch(D);
   const int lane = threadIdx.x & 63;
   const int R = 64 / G;                                     // rows of the wave
   const long long row0 = (long long)blockIdx.x * R;
@@ -110,8 +109,8 @@ __global__ __launch_bounds__(kRtsThreads) void rts_smooth_kernel(RtsSmoothArgs<T
   double* Gw = Ww + R * S;                                  // its Gt matrices
   double* Fw = Gw + R * FP;                                 // its Ft matrices
 
-  newton_stage(Lw, p.A, p.prior_prec, p.prior_prec_stride, row0, nr, D, S, lane);
-  newton_wave_sync();
+  dense_stage(Lw, p.A, p.prior_prec, p.prior_prec_stride, row0, nr, D, S, lane);
+  dense_wave_sync();
 
   const int r = lane / G, j = lane - r * G;                 // lane j of the wave's row r: row / column j of its matrices
   const long long m = row0 + r;
@@ -123,11 +122,11 @@ __global__ __launch_bounds__(kRtsThreads) void rts_smooth_kernel(RtsSmoothArgs<T
   double* Ft = Fw + r * FP;
   double* V = Ft;                                           // N, a packed triangle, until F is formed
 
-  const int bad1 = post_cov_factor(L, D, G, j, act);
-  post_cov_solve(L, W, D, j, act, bad1);                    // W = C
-  newton_wave_sync();
+  const int bad1 = dense_factor(L, D, G, j, act);
+  dense_solve(L, W, D, j, act, bad1);                    // W = C
+  dense_wave_sync();
 
-  prior_stage_noise(Lw, Ww, p.noise, p.noise_stride, row0, nr, D, S, lane);      // S = C + Q over L
+  dense_stage_noise(Lw, Ww, p.noise, p.noise_stride, row0, nr, D, S, lane);      // S = C + Q over L
   // Delta = cov_next - S into Gt, packed as a triangle: every element by the lane that has just written its S
   {
     const T* Ng = p.cov_next + row0 * DD;
@@ -136,55 +135,55 @@ __global__ __launch_bounds__(kRtsThreads) void rts_smooth_kernel(RtsSmoothArgs<T
       const int rr = idx / DD, e = idx - rr * DD;
       const int i = e / D, c = e - i * D;
       if (c <= i) {
-        const int t = newton_tri(i) + c;
+        const int t = dense_tri(i) + c;
         Gw[rr * FP + t] = (double)Ng[idx] - Lw[rr * S + t];
       }
     }
   }
-  newton_wave_sync();
+  dense_wave_sync();
 
-  const int bad2 = post_cov_factor(L, D, G, j, act);
-  post_cov_solve(L, V, D, j, act, bad1 | bad2);             // V = N
+  const int bad2 = dense_factor(L, D, G, j, act);
+  dense_solve(L, V, D, j, act, bad1 | bad2);             // V = N
   const int bad = bad1 ? bad1 : (bad2 ? D + bad2 : 0);
-  newton_wave_sync();
+  dense_wave_sync();
 
   // the factor of S is dead: Delta over L, a plain copy of the wave's triangles
   for (int idx = lane; idx < R * S; idx += 64) {
     const int rr = idx / S;
     Lw[idx] = Gw[rr * FP + (idx - rr * S)];
   }
-  newton_wave_sync();
+  dense_wave_sync();
 
   const int i = j;                                          // from here on the lane's ROW
-  const int ti = newton_tri(i);
+  const int ti = dense_tri(i);
   if (act) {
     // G_i: = C_i: N
     for (int c = 0; c < D; ++c) {
-      const int tc = newton_tri(c);
+      const int tc = dense_tri(c);
       double s = 0.0;
       for (int k = 0; k < D; ++k) {
-        const double cik = k <= i ? W[ti + k] : W[newton_tri(k) + i];
-        const double nkc = k >= c ? V[newton_tri(k) + c] : V[tc + k];
+        const double cik = k <= i ? W[ti + k] : W[dense_tri(k) + i];
+        const double nkc = k >= c ? V[dense_tri(k) + c] : V[tc + k];
         s = fma(cik, nkc, s);
       }
       Gt[c * D + i] = s;
     }
   }
-  newton_wave_sync();
+  dense_wave_sync();
 
   if (act) {
     // F_i: = G_i: Delta
     for (int k = 0; k < D; ++k) {
-      const int tk = newton_tri(k);
+      const int tk = dense_tri(k);
       double s = 0.0;
       for (int l = 0; l < D; ++l) {
-        const double dlk = l >= k ? L[newton_tri(l) + k] : L[tk + l];
+        const double dlk = l >= k ? L[dense_tri(l) + k] : L[tk + l];
         s = fma(Gt[l * D + i], dlk, s);
       }
       Ft[k * D + i] = s;
     }
   }
-  newton_wave_sync();                                       // (Delta is dead)
+  dense_wave_sync();                                       // (Delta is dead)
   if (act) {
     // K_ic = F_i: . G_c: and C_s = C + K at c <= i, over Delta
     for (int c = 0; c < D; ++c) {
@@ -219,8 +218,8 @@ __global__ __launch_bounds__(kRtsThreads) void rts_smooth_kernel(RtsSmoothArgs<T
       for (int c = 0; c <= i; ++c) L[ti + c] = qnan;        // (a NaN N makes these NaN already; the payload is this one)
   }
   if (!p.cov_smooth) return;
-  newton_wave_sync();
-  post_cov_store(p.cov_smooth, Lw, row0, nr, D, S, lane);
+  dense_wave_sync();
+  dense_store(p.cov_smooth, Lw, row0, nr, D, S, lane);
 }
 
 }  // namespace gpk

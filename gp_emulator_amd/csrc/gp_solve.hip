@@ -1,0 +1,236 @@
+// The small dense solves on device buffers: damped Newton step, LM update, posterior covariance, prior propagation and
+// the smoother's backward step.  Device arrays in, device arrays out, no model.
+#include "gp_host.hpp"
+
+#include "gp_launchers.hpp"
+#include "gp_newton_kernel.hpp"
+#include "gp_posterior_cov_kernel.hpp"
+#include "gp_prior_propagate_kernel.hpp"
+#include "gp_rts_smooth_kernel.hpp"
+
+// what a launcher returned, as the entry's status
+static int launched(hipError_t e, const char* kernel) {
+  if (e != hipSuccess) return fail(GP_ERR_HIP, "%s kernel launch: %s", kernel, hipGetErrorString(e));
+  return GP_OK;
+}
+
+static int newton_sizes(int dtype, int64_t n_rows, int n_inputs) {
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_rows <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_inputs > gpk::kNewtonMaxD)
+    return fail(GP_ERR_UNSUPPORTED, "the Newton step kernels serve n_inputs <= %d", gpk::kNewtonMaxD);
+  // (16 or 8 rows per workgroup, 4 per workgroup in the update: the grids are numbered in 31 bits)
+  if (n_rows > (int64_t)0x7fffffff * 4) return fail(GP_ERR_INVALID, "n_rows too large for one launch");
+  return GP_OK;
+}
+
+// a row stride in elements: 0 (one array for all rows) or at least one row's elements; never without the pointer
+static int row_stride(const char* what, const void* ptr, int64_t stride, int64_t row_elems) {
+  if (stride != 0 && stride < row_elems)
+    return fail(GP_ERR_INVALID, "%s stride %lld is neither 0 nor >= %lld", what, (long long)stride, (long long)row_elems);
+  if (stride != 0 && !ptr) return fail(GP_ERR_INVALID, "%s stride without a pointer", what);
+  return GP_OK;
+}
+
+extern "C" {
+
+int gp_newton_step_rows_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
+                               const void* d_lambda, int damping, const void* d_prior_mean, const void* d_prior_prec,
+                               const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
+                               int64_t n_rows, int n_inputs, int64_t prior_mean_stride, int64_t prior_prec_stride) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_x || !d_grad || !d_A || !d_lambda || !d_status || (!d_step && !d_trial))
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (damping != GP_DAMP_DIAGONAL && damping != GP_DAMP_IDENTITY) return fail(GP_ERR_INVALID, "bad damping %d", damping);
+  if ((d_prior_mean != nullptr) != (d_prior_prec != nullptr))
+    return fail(GP_ERR_INVALID, "prior mean and prior precision go together");
+  if ((d_lo != nullptr) != (d_hi != nullptr)) return fail(GP_ERR_INVALID, "lower and upper bounds go together");
+  if (int rc = row_stride("prior mean", d_prior_mean, prior_mean_stride, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::NewtonArgs<T> a;
+    a.x = as<T>(d_x);
+    a.grad = as<T>(d_grad);
+    a.A = as<T>(d_A);
+    a.lambda = as<T>(d_lambda);
+    a.prior_mean = as<T>(d_prior_mean);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_mean_stride = prior_mean_stride;
+    a.prior_prec_stride = prior_prec_stride;
+    a.lo = as<T>(d_lo);
+    a.hi = as<T>(d_hi);
+    a.step = as<T>(d_step);
+    a.trial = as<T>(d_trial);
+    a.status = d_status;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    a.diagonal = damping == GP_DAMP_DIAGONAL ? 1 : 0;
+    return launched(gpk::launch_newton_step<T>(a, ctx->stream), "newton step");
+  });
+}
+
+int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
+                          const void* d_lambda, int damping, const void* d_prior_mean, const void* d_prior_prec,
+                          const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
+                          int64_t n_rows, int n_inputs) {
+  return gp_newton_step_rows_device(ctx, dtype, d_x, d_grad, d_A, d_lambda, damping, d_prior_mean, d_prior_prec, d_lo, d_hi,
+                                    d_step, d_trial, d_status, n_rows, n_inputs, 0, 0);
+}
+
+int gp_lm_update_rows_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost,
+                             const void* d_cost_trial, void* d_grad, const void* d_grad_trial, void* d_A,
+                             const void* d_A_trial, void* d_lambda, const int32_t* d_status, int32_t* d_state,
+                             int32_t* d_accepted, const void* d_prior_mean, const void* d_prior_prec, double down,
+                             double up, double lambda_min, double lambda_max, double ftol, double xtol,
+                             int64_t n_rows, int n_inputs, int64_t prior_mean_stride, int64_t prior_prec_stride) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_x || !d_trial || !d_cost || !d_cost_trial || !d_lambda || !d_status || !d_state)
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if ((d_grad != nullptr) != (d_grad_trial != nullptr) || (d_A != nullptr) != (d_A_trial != nullptr))
+    return fail(GP_ERR_INVALID, "grad / grad_trial and A / A_trial are given or left out as pairs");
+  if ((d_prior_mean != nullptr) != (d_prior_prec != nullptr))
+    return fail(GP_ERR_INVALID, "prior mean and prior precision go together");
+  if (int rc = row_stride("prior mean", d_prior_mean, prior_mean_stride, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::LmUpdateArgs<T> a;
+    a.x = as<T>(d_x);
+    a.trial = as<T>(d_trial);
+    a.cost = as<T>(d_cost);
+    a.cost_trial = as<T>(d_cost_trial);
+    a.grad = as<T>(d_grad);
+    a.grad_trial = as<T>(d_grad_trial);
+    a.A = as<T>(d_A);
+    a.A_trial = as<T>(d_A_trial);
+    a.lambda = as<T>(d_lambda);
+    a.status = d_status;
+    a.state = d_state;
+    a.accepted = d_accepted;
+    a.prior_mean = as<T>(d_prior_mean);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_mean_stride = prior_mean_stride;
+    a.prior_prec_stride = prior_prec_stride;
+    a.down = down;
+    a.up = up;
+    a.lambda_min = lambda_min;
+    a.lambda_max = lambda_max;
+    a.ftol = ftol;
+    a.xtol = xtol;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    return launched(gpk::launch_lm_update<T>(a, ctx->stream), "lm update");
+  });
+}
+
+int gp_lm_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost, const void* d_cost_trial,
+                        void* d_grad, const void* d_grad_trial, void* d_A, const void* d_A_trial,
+                        void* d_lambda, const int32_t* d_status, int32_t* d_state, int32_t* d_accepted,
+                        const void* d_prior_mean, const void* d_prior_prec, double down, double up,
+                        double lambda_min, double lambda_max, double ftol, double xtol,
+                        int64_t n_rows, int n_inputs) {
+  return gp_lm_update_rows_device(ctx, dtype, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A, d_A_trial,
+                                  d_lambda, d_status, d_state, d_accepted, d_prior_mean, d_prior_prec, down, up, lambda_min,
+                                  lambda_max, ftol, xtol, n_rows, n_inputs, 0, 0);
+}
+
+int gp_posterior_cov_rows_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, void* d_cov,
+                                 void* d_sigma, int32_t* d_status, int64_t n_rows, int n_inputs,
+                                 int64_t prior_prec_stride) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_A || !d_status || (!d_cov && !d_sigma)) return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::PosteriorCovArgs<T> a;
+    a.A = as<T>(d_A);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_prec_stride = prior_prec_stride;
+    a.cov = as<T>(d_cov);
+    a.sigma = as<T>(d_sigma);
+    a.status = d_status;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    return launched(gpk::launch_posterior_cov<T>(a, ctx->stream), "posterior covariance");
+  });
+}
+
+int gp_posterior_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, void* d_cov, void* d_sigma,
+                            int32_t* d_status, int64_t n_rows, int n_inputs) {
+  return gp_posterior_cov_rows_device(ctx, dtype, d_A, d_prior_prec, d_cov, d_sigma, d_status, n_rows, n_inputs, 0);
+}
+
+int gp_prior_propagate_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, int64_t prior_prec_stride,
+                              const void* d_noise, int64_t noise_stride, void* d_next_prec, int32_t* d_status,
+                              int64_t n_rows, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_A || !d_noise || !d_next_prec || !d_status) return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  if (int rc = row_stride("process noise", d_noise, noise_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::PriorPropagateArgs<T> a;
+    a.A = as<T>(d_A);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_prec_stride = prior_prec_stride;
+    a.noise = as<T>(d_noise);
+    a.noise_stride = noise_stride;
+    a.next_prec = as<T>(d_next_prec);
+    a.status = d_status;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    return launched(gpk::launch_prior_propagate<T>(a, ctx->stream), "prior propagation");
+  });
+}
+
+int gp_rts_smooth_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, int64_t prior_prec_stride,
+                         const void* d_noise, int64_t noise_stride, const void* d_x, const void* d_x_next,
+                         const void* d_cov_next, const void* d_lo, const void* d_hi, void* d_x_smooth, void* d_cov_smooth,
+                         void* d_sigma_smooth, int32_t* d_status, int64_t n_rows, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_A || !d_noise || !d_x || !d_x_next || !d_cov_next || !d_x_smooth || !d_status || (!d_cov_smooth && !d_sigma_smooth))
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if ((d_lo == nullptr) != (d_hi == nullptr)) return fail(GP_ERR_INVALID, "bounds need both lo and hi");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  if (int rc = row_stride("process noise", d_noise, noise_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  // a row's sub-group stores x_smooth before another wave has loaded its inputs: nothing may be smoothed in place
+  const void* ins[] = {d_A, d_prior_prec, d_noise, d_x, d_x_next, d_cov_next, d_lo, d_hi};
+  const void* outs[] = {d_x_smooth, d_cov_smooth, d_sigma_smooth, d_status};
+  for (const void* o : outs)
+    for (const void* in : ins)
+      if (o && o == in) return fail(GP_ERR_INVALID, "an output is an input");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::RtsSmoothArgs<T> a;
+    a.A = as<T>(d_A);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_prec_stride = prior_prec_stride;
+    a.noise = as<T>(d_noise);
+    a.noise_stride = noise_stride;
+    a.x = as<T>(d_x);
+    a.x_next = as<T>(d_x_next);
+    a.cov_next = as<T>(d_cov_next);
+    a.lo = as<T>(d_lo);
+    a.hi = as<T>(d_hi);
+    a.x_smooth = as<T>(d_x_smooth);
+    a.cov_smooth = as<T>(d_cov_smooth);
+    a.sigma_smooth = as<T>(d_sigma_smooth);
+    a.status = d_status;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    return launched(gpk::launch_rts_smooth<T>(a, ctx->stream), "smoother");
+  });
+}
+
+}  // extern "C"

@@ -493,11 +493,11 @@ def leg_registers(a):
         else:
             row[m.group(1)] = m.group(2)
     flush()
-    for D in (11, 16, 32):          # gp_newton_kernel.hpp: newton_rows_per_wg, newton_pitch
+    for D in (11, 16, 32):          # gp_newton_kernel.hpp: newton_rows_per_wg; gp_dense_device.hpp: dense_pitch
         rows, tri = (16 if D <= 16 else 8), D * (D + 1) // 2
         pitch = tri + (16 - tri % 32) % 32
         print("dynamic LDS of newton_step_kernel at D = %d: %d rows x %d doubles = %d bytes per workgroup" % (D, rows, pitch, rows * pitch * 8))
-    for D in (11, 16, 32):          # gp_posterior_cov_kernel.hpp: post_cov_rows_per_wg, two triangles per row
+    for D in (11, 16, 32):          # gp_posterior_cov_kernel.hpp, gp_prior_propagate_kernel.hpp: 128 threads, two triangles per row
         rows, tri = (8 if D <= 16 else 4), D * (D + 1) // 2
         pitch = tri + (16 - tri % 32) % 32
         print("dynamic LDS of posterior_cov_kernel and prior_propagate_kernel at D = %d: %d rows x 2 x %d doubles = %d bytes per workgroup"
