@@ -366,3 +366,34 @@ class GaussianProcess:
                 hess[:, d, d2] = np.sum(w * u[:, :, d] * u[:, :, d2], axis=0)
             hess[:, d, d] -= expX[d] * np.sum(w, axis=0)
         return hess
+
+    # ------------------------------------------------------------------ gradient of the variance
+    def variance_gradient(self, testing, is_gpu=False, precision=np.float64):
+        """``(var (nn,), dvar (nn, D))``: the predictive variance ``b - k^T invQ k`` and its gradient with respect to
+        the test row (not in the reference).  With ``W = ((invQ + invQ^T) k) * k``, valid for any ``invQ``:
+        ``var = b - sum_j W_j / 2`` and ``dvar[:, d] = -e_d sum_j W_j (x_jd - t_d)``.  ``is_gpu=True`` runs the HIP
+        kernel (``gp_predict_var_grad_device`` on the cached device model) in ``precision`` and returns float64; like
+        ``predict`` it never falls back to the CPU.  ``is_gpu=False`` is the explicit numpy branch: the difference form
+        in float64.  The sum cancels as heavily as the variance itself (a 1e-5 nugget leaves ``|dvar|`` 1e3 to 1e10
+        times below the sum of its terms' magnitudes), so float32 results are mostly rounding noise on such emulators."""
+        testing = np.asarray(testing)
+        (nn, D) = testing.shape
+        assert D == self.D
+        if is_gpu == True:  # noqa: E712
+            dt = np.dtype(precision)
+            if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+                raise TypeError("precision must be float32 or float64")
+            var, dvar = self.gpu_model(dt).predict_var_grad(np.ascontiguousarray(testing, dtype=dt))
+            return var.astype(np.float64, copy=False), dvar.astype(np.float64, copy=False)
+        expX = np.exp(self.theta)
+        s = np.sqrt(expX[:D])
+        testing = testing.astype(np.float64, copy=False)
+        k = expX[D] * np.exp(-0.5 * dist.cdist(s * self.inputs, s * testing, "sqeuclidean"))      # (n, nn)
+        invQ = np.asarray(self.invQ, dtype=np.float64)
+        W = np.dot(invQ + invQ.T, k) * k
+        var = expX[D] - 0.5 * np.sum(W, axis=0)
+        dvar = np.empty((nn, D))
+        for d in range(D):
+            aa = np.asarray(self.inputs)[:, d][:, None] - testing[:, d][None, :]
+            dvar[:, d] = -expX[d] * np.sum(W * aa, axis=0)
+        return var, dvar

@@ -60,6 +60,8 @@ SIGNATURES = {
     "gp_predict_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_i64, c_int, c_i64]),
     "gp_predict_mean_grad_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int]),
+    "gp_predict_var_grad_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int]),
+    "gp_model_var_grad_bytes": (c_int, [c_void_p, ctypes.POINTER(c_i64)]),
     "gp_predict_mean_grad_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_i64, c_int, c_i64]),
     "gp_ctx_host_threads": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
@@ -721,8 +723,10 @@ class Model:
         check(self.ctx.lib.gp_model_info(self.h, *[ctypes.byref(x) for x in v]))
         nk = c_int(0)
         check(self.ctx.lib.gp_kernel_ksteps(v[1].value, v[2].value, ctypes.byref(nk)))
+        vg = c_i64(0)      # the variance-gradient operand: 0 until the first ``predict_var_grad*`` call builds it
+        check(self.ctx.lib.gp_model_var_grad_bytes(self.h, ctypes.byref(vg)))
         return dict(dtype=v[0].value, n_train=v[1].value, n_inputs=v[2].value,
-                    kernel_d=v[3].value, kernel_nb=v[4].value, kernel_nk=nk.value)
+                    kernel_d=v[3].value, kernel_nb=v[4].value, kernel_nk=nk.value, var_grad_bytes=vg.value)
 
     def predict_device(self, d_testing, d_mu, d_var, d_deriv, n_predict,
                        deriv_layout=GP_DERIV_ROWMAJOR):
@@ -770,6 +774,51 @@ class Model:
                 self.ctx.h, self.h, _dtype_code(testing.dtype), _ptr(testing),
                 _ptr(mu), _ptr(deriv), M, int(deriv_layout), int(max_block_rows)), "gp_predict_mean_grad_host")
         return mu, deriv
+
+    def predict_var_grad_device(self, d_testing, d_var, d_dvar, n_predict, deriv_layout=GP_DERIV_ROWMAJOR):
+        """The variance and its gradient with respect to the test row (``gp_predict_var_grad_device``): asynchronous
+        on the context's stream; device pointers, var [E][M], dvar [E][M*D].  Always the throughput kernel.  The
+        model's first call builds the kernel's operand on the device (``info()["var_grad_bytes"]``)."""
+        check(self.ctx.lib.gp_predict_var_grad_device(self.ctx.h, self.h, d_testing, d_var, d_dvar,
+                                                      int(n_predict), int(deriv_layout)), "gp_predict_var_grad_device")
+
+    VAR_GRAD_BLOCK_ROWS = 1 << 20
+
+    def predict_var_grad(self, testing, deriv_layout=GP_DERIV_ROWMAJOR, out=None):
+        """``(var, dvar)`` for host rows (M, D): uploads, launches ``gp_predict_var_grad_device``, downloads, in row
+        blocks of at most 2^20 rows.  Rows and results have the model's dtype (rows are converted to it);
+        ``out=(var, dvar)`` supplies the output arrays.  Shapes as ``predict``'s var and deriv: (M,) and (M, D) or
+        (D, M), with a leading E for a batch."""
+        testing = np.ascontiguousarray(testing, dtype=self.dtype)
+        if testing.ndim != 2 or testing.shape[1] != self.n_inputs:
+            raise ValueError("testing must be (n_predict, %d)" % self.n_inputs)
+        M, D = testing.shape
+        E = getattr(self, "n_emulators", None)
+        lead, ne = (() if E is None else (E,)), (E or 1)
+        row_major = deriv_layout == GP_DERIV_ROWMAJOR
+        shapes = (lead + (M,), lead + ((M, D) if row_major else (D, M)))
+        if out is None:
+            out = tuple(np.empty(sh, self.dtype) for sh in shapes)
+        var, dvar = out
+        for a, shape in zip((var, dvar), shapes):
+            if (not isinstance(a, np.ndarray) or a.dtype != self.dtype or a.shape != shape
+                    or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]):
+                raise ValueError("out arrays must be writeable C-contiguous %s arrays of shapes %s, %s" % ((self.dtype,) + shapes))
+        v2, d3 = var.reshape(ne, M), dvar.reshape((ne, M, D) if row_major else (ne, D, M))
+        isz = self.dtype.itemsize
+        for lo in range(0, M, self.VAR_GRAD_BLOCK_ROWS):
+            n = min(self.VAR_GRAD_BLOCK_ROWS, M - lo)
+            with Scratch(self.ctx, self.dtype) as scratch:
+                d_t = scratch.up(testing[lo:lo + n])
+                d_var, d_dvar = scratch.alloc(ne * n * isz), scratch.alloc(ne * n * D * isz)
+                self.predict_var_grad_device(d_t, d_var, d_dvar, n, deriv_layout)
+                v2[:, lo:lo + n] = _download(self.ctx, d_var, (ne, n), self.dtype)
+                blk = _download(self.ctx, d_dvar, (ne, n, D) if row_major else (ne, D, n), self.dtype)
+                if row_major:
+                    d3[:, lo:lo + n] = blk
+                else:
+                    d3[:, :, lo:lo + n] = blk
+        return var, dvar
 
     def _host_call(self, testing, deriv_layout, out, with_var):
         """The rows as the library takes them and the output arrays ((mu, var, deriv), or (mu, deriv)
@@ -986,17 +1035,17 @@ class BatchModel(Model):
         return out
 
 
-GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM = 0, 1, 2, 3, 4, 5
+GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_VAR_GRAD = 0, 1, 2, 3, 4, 5, 6
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
                 6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
-                10: "misfit", 11: "mv_gram"}
+                10: "misfit", 11: "mv_gram", 12: "var_grad"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
-             "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM}
+             "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM, "var_grad": GP_OP_VAR_GRAD}
 
 
 def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_pcs=0, n_bands=0,
                 compute_units=256, aligned16=True):
-    """How the device call ``op`` ("predict", "mean_grad", "hessian", "reconstruct", "misfit", "mv_gram") on ``n_rows`` rows would be
+    """How the device call ``op`` ("predict", "mean_grad", "var_grad", "hessian", "reconstruct", "misfit", "mv_gram") on ``n_rows`` rows would be
     launched on a device of ``compute_units`` (``gp_launch_plan``: host arithmetic shared with the launch path, no
     GPU needed).  Returns dict(kernel, rows_per_item, items, workgroups, rest_items, rest_workgroups): the
     kernel family and instance (a ``PLAN_KERNELS`` name), the rows of one work item, and the work items and

@@ -118,11 +118,12 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
     for tname, ctype in (("f64", "double"), ("f32", "float")):
         t = ["-DGP_T=" + ctype]
         units += [("gp_kernels_tu.hip", "kern_%s_%d" % (tname, nk), t + ["-DGP_NK=%d" % nk]) for nk in kernel_sizes("NK")]
+        units += [("gp_var_grad_tu.hip", "vargrad_%s_%d" % (tname, nk), t + ["-DGP_NK=%d" % nk]) for nk in kernel_sizes("NK")]
         units += [("gp_hessian_win_tu.hip", "hessm_%s_%d" % (tname, nb), t + ["-DGP_NB=%d" % nb]) for nb in kernel_sizes("NB")]
         units += [("gp_generic_tu.hip", "generic_" + tname, t), ("gp_few_tu.hip", "few_" + tname, t),
                   ("gp_hessian_tu.hip", "hess_" + tname, t)]
     units += [("gp_reconstruct_tu.hip", "reconstruct", []), ("gp_misfit_tu.hip", "misfit", []),
-              ("gp_gram_tu.hip", "gram", []),
+              ("gp_gram_tu.hip", "gram", []), ("gp_var_grad_operand_tu.hip", "vargrad_operand", []),
               ("gp_band_misfit_tu.hip", "band_misfit", []), ("gp_newton_tu.hip", "newton", []),
               ("gp_train_tu.hip", "train", [])]
     # the host units (gp_host.hpp lists them)
@@ -135,8 +136,8 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
     # biggest kernels first so the pool drains evenly
     def weight(c):
         for a in c:
-            if a.startswith("-DGP_NK="):
-                return int(a[8:])
+            if a.startswith("-DGP_NK="):     # (var_grad_kernel unrolls twice predict's matrix instructions)
+                return int(a[8:]) * (2 if any(x.endswith("gp_var_grad_tu.hip") for x in c) else 1)
             if a.startswith("-DGP_NB="):
                 return 4 * int(a[8:])
         return 0

@@ -1,4 +1,4 @@
-// Launch sizing, and predict and Hessian on device buffers.
+// Launch sizing, and predict, the variance's gradient and the Hessian on device buffers.
 #include "gp_host.hpp"
 
 #include "gp_generic_kernel.hpp"
@@ -14,6 +14,15 @@ template <typename T>
 static hipError_t launch_predict_nk(int knk, int kd, const gpk::PredictArgs<T>& a, int grid, bool var, hipStream_t s) {
   switch (knk) {
 #define GP_CASE(nk) case nk: return gpk::launch_predict<T, nk>(kd, a, grid, var, s);
+    GP_FOR_EACH_KERNEL_NK(GP_CASE)
+#undef GP_CASE
+  }
+  return hipErrorInvalidValue;
+}
+template <typename T>
+static hipError_t launch_var_grad_nk(int knk, int kd, const gpk::PredictArgs<T>& a, int grid, hipStream_t s) {
+  switch (knk) {
+#define GP_CASE(nk) case nk: return gpk::launch_var_grad<T, nk>(kd, a, grid, s);
     GP_FOR_EACH_KERNEL_NK(GP_CASE)
 #undef GP_CASE
   }
@@ -130,6 +139,52 @@ int predict_device(gp_ctx* ctx, const gp_model* m, const void* d_testing, void* 
   return GP_OK;
 }
 
+// Variance and its gradient: var_grad_kernel whatever the size of the call (no few-rows form), predict_kernel's
+// geometry and persistent grid.
+static int check_var_grad_shape(int kernel_nb) {
+  if (kernel_nb > 0) return GP_OK;
+  return fail(GP_ERR_UNSUPPORTED, "the variance's gradient needs n_train <= %d and n_inputs <= %d (no general-shape kernel)",
+              16 * GP_MAX_KERNEL_NB, GP_MAX_KERNEL_D);
+}
+template <typename T>
+static PredictPlan plan_var_grad(int64_t M, int n_emulators, int compute_units) {
+  PredictPlan p = {false, false, gpk::Geo<T>::kRowsPerWG, {0, 0}};
+  p.too_large = (M + p.rows_per_item - 1) / p.rows_per_item > 0x7fffffffLL;
+  p.grid = gpk::plan_grid(M, p.rows_per_item, n_emulators, (int64_t)compute_units * gpk::Geo<T>::kWGPerCU);
+  return p;
+}
+template <typename T>
+int var_grad_device(gp_ctx* ctx, const gp_model* m, const void* d_testing, void* d_var, void* d_dvar, int64_t M, int layout,
+                    hipStream_t stream, int e0, int ne) {
+  if (!stream) stream = ctx->stream;
+  if (ne < 0) ne = m->n_emulators - e0;
+  if (e0 < 0 || ne < 1 || e0 + ne > m->n_emulators) return fail(GP_ERR_INVALID, "bad emulator range");
+  if (int rc = check_var_grad_shape(m->kernel_nb)) return rc;
+  const PredictPlan pp = plan_var_grad<T>(M, ne, ctx->compute_units);
+  if (pp.too_large) return fail(GP_ERR_INVALID, "n_predict too large for one launch");
+  if (int rc = ensure_var_grad_frags<T>(ctx, const_cast<gp_model*>(m), stream)) return rc;
+  gpk::PredictArgs<T> a;
+  a.xa = (const T*)m->d_xa + (size_t)e0 * m->xa_stride;
+  a.frags = (const T*)m->d_vfrags + (size_t)e0 * m->vfrags_stride;
+  a.sd = (const T*)m->d_sd + (size_t)e0 * m->sd_stride;
+  a.testing = (const T*)d_testing;
+  a.mu = nullptr;
+  a.var = (T*)d_var;
+  a.deriv = (T*)d_dvar;
+  a.M = M;
+  a.d_actual = m->n_inputs;
+  a.deriv_row_major = layout == GP_DERIV_ROWMAJOR;
+  a.n_emulators = ne;
+  a.xa_stride = m->xa_stride;
+  a.frags_stride = m->vfrags_stride;
+  a.sd_stride = m->sd_stride;
+  a.dbg = nullptr;
+  a.rows_prescaled = 0;
+  hipError_t e = launch_var_grad_nk<T>(m->kernel_nk, m->kernel_d, a, pp.grid.workgroups, stream);
+  if (e != hipSuccess) return fail(GP_ERR_HIP, "variance-gradient kernel launch: %s", hipGetErrorString(e));
+  return GP_OK;
+}
+
 static bool hessian_on_matrix_core(int kernel_d, int kernel_nb) {
   if (kernel_nb <= 0) return false;
   if (const char* ev = getenv("GP_HESS_VALU"))      // A/B switch: force the VALU kernel
@@ -223,7 +278,8 @@ int recon_wide(int dtype, int n_bands) {
 #define GP_INST(T)                                                                                                 \
   template int predict_device<T>(gp_ctx*, const gp_model*, const void*, void*, void*, void*, int64_t, int, hipStream_t, \
                                  bool, int, int, bool);                                                            \
-  template int hessian_device<T>(gp_ctx*, const gp_model*, const void*, void*, int64_t, hipStream_t, long long, int, int);
+  template int hessian_device<T>(gp_ctx*, const gp_model*, const void*, void*, int64_t, hipStream_t, long long, int, int); \
+  template int var_grad_device<T>(gp_ctx*, const gp_model*, const void*, void*, void*, int64_t, int, hipStream_t, int, int);
 GP_INST(float) GP_INST(double)
 #undef GP_INST
 
@@ -261,6 +317,16 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     k = GP_PLAN_MV_GRAM;
     rpi = gpk::mkRows;
     g = gpk::plan_misfit(n_rows, gpk::mkRows, gpk::gram_cap(compute_units, n_inputs, f64 ? 8 : 4));
+  } else if (op == GP_OP_VAR_GRAD) {
+    int kd, knb;
+    int rc = pick_kernel(n_train, n_inputs, &kd, &knb);
+    if (rc || (rc = check_var_grad_shape(knb))) return rc;
+    const PredictPlan pp = f64 ? plan_var_grad<double>(n_rows, n_emulators, compute_units)
+                               : plan_var_grad<float>(n_rows, n_emulators, compute_units);
+    if (pp.too_large) return fail(GP_ERR_INVALID, "n_predict too large for one launch");
+    k = GP_PLAN_VAR_GRAD;
+    rpi = pp.rows_per_item;
+    g = pp.grid;
   } else if (op == GP_OP_PREDICT || op == GP_OP_MEAN_GRAD || op == GP_OP_HESSIAN) {
     int kd, knb;
     int rc = pick_kernel(n_train, n_inputs, &kd, &knb);
@@ -339,6 +405,18 @@ int gp_predict_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
 int gp_predict_mean_grad_device(gp_ctx* ctx, const gp_model* model, const void* d_testing, void* d_mu,
                                 void* d_deriv, int64_t n_predict, int deriv_layout) {
   return predict_device_entry(ctx, model, d_testing, d_mu, nullptr, d_deriv, n_predict, deriv_layout, false);
+}
+
+int gp_predict_var_grad_device(gp_ctx* ctx, const gp_model* model, const void* d_testing, void* d_var, void* d_dvar,
+                               int64_t n_predict, int deriv_layout) {
+  int rc = check_call(ctx, model, n_predict);
+  if (rc || n_predict == 0) return rc;
+  if (!d_testing || !d_var || !d_dvar) return fail(GP_ERR_INVALID, "null device pointer");
+  if ((rc = check_layout(deriv_layout)) || (rc = check_model(ctx, model, kNeedVariance))) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(model->dtype, [&](auto t) {
+    return var_grad_device<GP_TAG_TYPE(t)>(ctx, model, d_testing, d_var, d_dvar, n_predict, deriv_layout);
+  });
 }
 
 int gp_hessian_device(gp_ctx* ctx, const gp_model* model, const void* d_testing, void* d_hess, int64_t n_predict) {

@@ -1,8 +1,8 @@
 // What the host units of libgp_predict_hip.so share: the objects behind the C ABI's handles, the error
 // plumbing, the dtype dispatch, the argument checks, and the functions one unit defines for another.
 //   gp_ctx.hip        the error buffer, contexts, device memory, events, the training objective
-//   gp_model.hip      kernel choice, packing, models and the context's model cache
-//   gp_device.hip     launch sizing; predict and Hessian on device buffers
+//   gp_model.hip      kernel choice, packing, models, the operands built on first use, the context's model cache
+//   gp_device.hip     launch sizing; predict, the variance's gradient and the Hessian on device buffers
 //   gp_solve.hip      the small dense solves on device buffers: Newton step, LM update, posterior covariance, prior
 //                     propagation, smoother (no model)
 //   gp_host_path.hip  predict and Hessian on host arrays: the slab pipeline, the pinned-array path
@@ -104,6 +104,10 @@ struct gp_model {
   std::mutex h_mutex;
   void* d_pfrags;                          // [n_emulators][pfrags_stride]
   long long pfrags_stride;
+  // Variance gradient (gp_var_grad_kernel.hpp): invQ + invQ^T in the full fragment order, built on the device from
+  // d_frags on the first variance-gradient call (under h_mutex); twice the bytes of d_frags, so not made before
+  void* d_vfrags;                          // [n_emulators][vfrags_stride]
+  long long vfrags_stride;
 };
 
 // Host-pointer path (predict_host): slabs of the caller's arrays flow through kPipeSlots slots,
@@ -194,6 +198,7 @@ int pick_kernel(int n_train, int n_inputs, int* kd, int* knb, int* knk = nullptr
 inline int rows_padded(int n_train, int knb) { return knb > 0 ? 16 * knb : 16 * ((n_train + 15) / 16); }
 inline int row_stride_of(int kd) { return gpk::row_stride(kd); }
 template <typename T> int ensure_hess_frags(gp_ctx* ctx, gp_model* m);
+template <typename T> int ensure_var_grad_frags(gp_ctx* ctx, gp_model* m, hipStream_t stream);
 template <typename T, typename TH>
 int cached_model(gp_ctx* ctx, const TH* expX, const TH* inputs, const TH* invQt, const TH* invQ, int N, int D, int theta_size, gp_model** out);
 
@@ -204,6 +209,10 @@ int predict_device(gp_ctx* ctx, const gp_model* m, const void* d_testing, void* 
 template <typename T>
 int hessian_device(gp_ctx* ctx, const gp_model* m, const void* d_testing, void* d_hess, int64_t M,
                    hipStream_t stream = nullptr, long long hess_stride = -1, int e0 = 0, int ne = -1);
+// var [ne][M] and dvar [ne][M * D] of emulators [e0, e0 + ne) (ne < 0: all of them); always the throughput kernel
+template <typename T>
+int var_grad_device(gp_ctx* ctx, const gp_model* m, const void* d_testing, void* d_var, void* d_dvar, int64_t M, int layout,
+                    hipStream_t stream = nullptr, int e0 = 0, int ne = -1);
 int recon_wide(int dtype, int n_bands);
 int ensure_scratch(gp_ctx* ctx, size_t bytes);      // gp_ctx.hip
 gph::ThreadPool& host_pool(gp_ctx* ctx);            // gp_host_path.hip

@@ -28,6 +28,11 @@ struct TrainArgs;
 template <typename T, int NK> hipError_t launch_predict(int kernel_d, const PredictArgs<T>&, int grid, bool var, hipStream_t);
 template <typename T> hipError_t launch_few(int kernel_d, const PredictArgs<T>&, int nb, int grid, bool var, hipStream_t);
 template <typename T> hipError_t launch_generic(const GenericArgs<T>&, int grid, hipStream_t);
+// var_grad_kernel<T, D, NK> for the compiled kernel_d (PredictArgs: frags = the symmetrised matrix in full fragment order,
+// deriv = the variance's gradient), and sym_frags_kernel, which builds that operand from predict's S' fragments
+template <typename T, int NK> hipError_t launch_var_grad(int kernel_d, const PredictArgs<T>&, int grid, hipStream_t);
+template <typename T> hipError_t launch_sym_frags(const T* sp, T* full, int nb, int n_emulators, long long sp_stride,
+                                                  long long full_stride, hipStream_t);
 
 template <typename T> hipError_t launch_hessian(int kernel_d, const HessianArgs<T>&, int grid, hipStream_t);      // the VALU kernel
 template <typename T, int NB> hipError_t launch_hessm(int kernel_d, const HessMfmaArgs<T>&, int grid, hipStream_t);

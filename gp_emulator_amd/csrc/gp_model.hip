@@ -5,6 +5,8 @@
 
 #include "gp_generic_kernel.hpp"
 #include "gp_hessian_win_kernel.hpp"
+#include "gp_launchers.hpp"
+#include "gp_var_grad_kernel.hpp"
 
 static const int kKernelD[] = {
 #define GP_V(d) d,
@@ -165,6 +167,8 @@ static int model_create(gp_ctx* ctx, int E, const TH* expX, const TH* inputs, co
   m->d_xa = m->d_frags = m->d_sd = nullptr;
   m->d_pfrags = nullptr;
   m->pfrags_stride = 0;
+  m->d_vfrags = nullptr;
+  m->vfrags_stride = 0;
   hipError_t e = hipMalloc(&m->d_xa, sizeof(T) * xa_len * E);
   if (e == hipSuccess && invQ) e = hipMalloc(&m->d_frags, sizeof(T) * fr_len * E);
   if (e == hipSuccess) e = hipMalloc(&m->d_sd, sizeof(T) * sd_len * E);
@@ -276,6 +280,31 @@ int ensure_hess_frags(gp_ctx* ctx, gp_model* m) {
   return GP_OK;
 }
 
+// The operand of var_grad_kernel, built once per model: B = invQ + invQ^T in the full fragment order (J, I, s),
+// full_frag_count_padded(NB, chunk) * 64 elements per emulator -- 4 NB^2 fragments against predict's 2 NB (NB + 1),
+// 0.8 MB in fp64 at N = 320.  It is made on the device from the S' fragments the model already holds (off-diagonal
+// blocks are invQ_IJ + invQ_JI^T already; sym_frags_kernel adds their transposes and S'_JJ + S'_JJ^T), on `stream`,
+// and published once that stream has finished: a model never asked for the variance's gradient never pays for it.
+template <typename T>
+int ensure_var_grad_frags(gp_ctx* ctx, gp_model* m, hipStream_t stream) {
+  std::lock_guard<std::mutex> lock(m->h_mutex);
+  if (m->d_vfrags) return GP_OK;
+  (void)ctx;
+  const size_t n = (size_t)gpk::full_frag_count_padded(m->kernel_nb, gpk::Geo<T>::kChunk) * 64;
+  void* dp = nullptr;
+  HIP_TRY(hipMalloc(&dp, sizeof(T) * n * m->n_emulators));
+  hipError_t e = gpk::launch_sym_frags<T>((const T*)m->d_frags, (T*)dp, m->kernel_nb, m->n_emulators, m->frags_stride,
+                                          (long long)n, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) {
+    (void)hipFree(dp);
+    return fail(GP_ERR_HIP, "variance-gradient operand: %s", hipGetErrorString(e));
+  }
+  m->vfrags_stride = (long long)n;
+  m->d_vfrags = dp;
+  return GP_OK;
+}
+
 // ---- the context's model cache (see gp_cached_model) ---------------------------------------
 template <typename T, typename TH>
 int cached_model(gp_ctx* ctx, const TH* expX, const TH* inputs, const TH* invQt, const TH* invQ,
@@ -325,6 +354,8 @@ int cached_model(gp_ctx* ctx, const TH* expX, const TH* inputs, const TH* invQt,
 
 template int ensure_hess_frags<float>(gp_ctx*, gp_model*);
 template int ensure_hess_frags<double>(gp_ctx*, gp_model*);
+template int ensure_var_grad_frags<float>(gp_ctx*, gp_model*, hipStream_t);
+template int ensure_var_grad_frags<double>(gp_ctx*, gp_model*, hipStream_t);
 #define GP_INST(T, TH) \
   template int cached_model<T, TH>(gp_ctx*, const TH*, const TH*, const TH*, const TH*, int, int, int, gp_model**);
 GP_INST(double, double) GP_INST(float, float) GP_INST(float, double)
@@ -403,6 +434,7 @@ int gp_model_destroy(gp_model* m) {
   if (m->d_frags) (void)hipFree(m->d_frags);
   if (m->d_sd) (void)hipFree(m->d_sd);
   if (m->d_pfrags) (void)hipFree(m->d_pfrags);
+  if (m->d_vfrags) (void)hipFree(m->d_vfrags);
   delete m;
   return GP_OK;
 }
@@ -414,6 +446,13 @@ int gp_model_info(const gp_model* m, int* dtype, int* n_train, int* n_inputs, in
   if (n_inputs) *n_inputs = m->n_inputs;
   if (kernel_d) *kernel_d = m->kernel_d;
   if (kernel_nb) *kernel_nb = m->kernel_nb;
+  return GP_OK;
+}
+
+int gp_model_var_grad_bytes(const gp_model* m, int64_t* bytes) {
+  if (!m || !bytes) return fail(GP_ERR_INVALID, "null pointer");
+  std::lock_guard<std::mutex> lock(const_cast<gp_model*>(m)->h_mutex);
+  *bytes = m->d_vfrags ? (int64_t)(m->dtype == GP_F64 ? 8 : 4) * m->vfrags_stride * m->n_emulators : 0;
   return GP_OK;
 }
 

@@ -91,6 +91,17 @@ def predict_bands(gps, testing, precision=np.float64, device=None, devices=None,
     return (mu, var, deriv) if do_unc else (mu, deriv)
 
 
+def variance_gradient_bands(gps, X, precision=np.float64, device=None):
+    """var (E, M) and dvar (E, M, D): the predictive variance of the E emulators in ``gps`` at the shared rows ``X``
+    (M, D) and its gradient with respect to the row, in one launch per 2^20 rows (``BatchModel.predict_var_grad``).
+    Arrays of ``precision``; emulator e bit for bit what ``Model.predict_var_grad`` of it gives."""
+    batch = make_batch(gps, precision, device)
+    try:
+        return batch.predict_var_grad(np.asarray(X))
+    finally:
+        batch.close()
+
+
 def hessian_bands(gps, testing, precision=np.float64, weights=None, device=None, devices=None, hessian_fn=None):
     """Hessians of the E emulators' means over shared test rows: ``(E, M, D, D)``, or with ``weights``
     ``(E, M)`` the weighted sum over the emulators ``sum_e weights[e, m] * H_e[m]``, ``(M, D, D)`` -- the

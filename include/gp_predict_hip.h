@@ -198,6 +198,22 @@ int gp_predict_mean_grad_device(gp_ctx* ctx, const gp_model* model, const void* 
 int gp_predict_mean_grad_host(gp_ctx* ctx, const gp_model* model, int host_dtype, const void* testing,
                               void* result, void* deriv, int64_t n_predict, int deriv_layout,
                               int64_t max_block_rows);
+/* ---- the predictive variance and its gradient --------------------------------------------
+ * var(x) = b - k(x)^T invQ k(x) and dvar/dx = -e_d sum_j W_j (x_jd - t_d), W = ((invQ + invQ^T) k) * k, for ANY invQ
+ * (symmetric or not), in one launch of var_grad_kernel on the context's stream (asynchronous).  DEVICE pointers of the
+ * model's dtype: testing [M*D] row-major, var [E][M], dvar [E][M*D] in deriv_layout, E = the model's emulators.
+ * Always the throughput kernel, whatever the size of the call; no atomics: a row's results depend on nothing but the
+ * row.  var agrees with gp_predict_device's to rounding, not bit for bit (the sum runs in another order).  With a
+ * nugget of 1e-5 the sum that forms dvar cancels as heavily as the variance's own: in float32 the result is mostly
+ * rounding noise on such emulators.
+ * The kernel's operand, invQ + invQ^T in matrix-core fragment order (twice the bytes of predict's), is built on the
+ * device on a model's first call, which therefore also waits for the stream; it is freed with the model and
+ * gp_model_var_grad_bytes reports its size (0 before the first call).
+ * GP_ERR_INVALID for a model created without invQ; GP_ERR_UNSUPPORTED for a shape on the general-shape kernel
+ * (n_train > 320 or n_inputs > 16). */
+int gp_predict_var_grad_device(gp_ctx* ctx, const gp_model* model, const void* d_testing,
+                               void* d_var, void* d_dvar, int64_t n_predict, int deriv_layout);
+int gp_model_var_grad_bytes(const gp_model* model, int64_t* bytes);
 /* number of host threads (caller included) the context uses for staging copies */
 int gp_ctx_host_threads(gp_ctx* ctx, int* n_threads);
 /* NUMA node the device is attached to (sysfs, by PCI bus id; -1 = unknown).  The context's helper
@@ -565,6 +581,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_RECONSTRUCT 3
 #define GP_OP_MISFIT 4             /* n_inputs is n_pcs and aux n_bands, as for GP_OP_RECONSTRUCT */
 #define GP_OP_MV_GRAM 5            /* gp_mv_weight_gram_device: n_inputs is n_pcs and aux n_bands */
+#define GP_OP_VAR_GRAD 6           /* gp_predict_var_grad_device */
 #define GP_PLAN_PREDICT_FEW 1      /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
@@ -576,6 +593,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_RECON_WIDE 9       /* reconstruct_kernel, 512 threads x 3 vectors */
 #define GP_PLAN_MISFIT 10          /* misfit_kernel: an item is 64 rows over all bands */
 #define GP_PLAN_MV_GRAM 11         /* weight_gram_kernel: an item is 64 rows over all bands; workgroups per CU by instance */
+#define GP_PLAN_VAR_GRAD 12        /* var_grad_kernel: predict_kernel's items and grid, whatever the size of the call */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
