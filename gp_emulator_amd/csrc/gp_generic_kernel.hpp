@@ -10,6 +10,12 @@
 // works for test row m and the training points i == jl (mod 16).  The 16 x N kernel-row tile
 // lives in LDS (row stride N + 1 reals, so the 16 rows start on different banks); invQ is read
 // as given (row-major, no folding) with 16 consecutive columns per 16-lane group.
+//
+// Far, infinite and NaN test rows (the rule beside Real<double>::kFarG): exp_clamped gives every k_i of a row that is
+// absurdly far away as exactly 0, so mu = 0, var = b, deriv = 0 come out by themselves; but it gives 0 for a NaN
+// argument too (fp64) and for -inf (both precisions), and a row holding a NaN or an infinity would come back as
+// "mean 0, prior variance" with NaN in one gradient component only.  So the row's `poison` = g - g, g = sum_d t''_d^2
+// (0 for a finite row, NaN otherwise), is added to every value stored for the row.
 #pragma once
 #include "gp_predict_kernel.hpp"
 
@@ -62,8 +68,14 @@ __global__ __launch_bounds__(gkThreads) void predict_generic_kernel(GenericArgs<
     const long long m = tile * 16 + ml;
     const long long mc = m < p.M ? m : p.M - 1;
     __syncthreads();   // previous tile's readers of s_k / s_t are done
-    for (int d = jl; d < p.D; d += 16)
-      s_t[ml * p.D + d] = p.sd[d] * (p.testing[mc * p.D + d] - p.sd[p.dk + d]);
+    T gm = T(0);
+    for (int d = jl; d < p.D; d += 16) {
+      const T td = p.sd[d] * (p.testing[mc * p.D + d] - p.sd[p.dk + d]);
+      s_t[ml * p.D + d] = td;
+      gm = fma(td, td, gm);
+    }
+    gm = row16_sum(gm);
+    const T poison = gm - gm;   // NaN for rows holding a NaN or an infinity (exp_clamped gives 0 there), else 0
     __syncthreads();
 
     // kernel row tile + mean
@@ -80,7 +92,7 @@ __global__ __launch_bounds__(gkThreads) void predict_generic_kernel(GenericArgs<
       s_k[ml * ns + i] = k;
       mu = fma(k, row[p.acol], mu);
     }
-    mu = row16_sum(mu);
+    mu = row16_sum(mu) + poison;
     if (jl == 0 && m < p.M) p.mu[m] = mu;
 
     // gradient, one input dimension at a time
@@ -90,7 +102,7 @@ __global__ __launch_bounds__(gkThreads) void predict_generic_kernel(GenericArgs<
         const T* row = &p.xa[(long long)i * p.ds];
         gsum = fma(s_k[ml * ns + i] * row[p.acol], row[d] - t[d], gsum);
       }
-      gsum = row16_sum(gsum) * p.sd[d];
+      gsum = fma(row16_sum(gsum), p.sd[d], poison);   // (the multiply's rounding: + 0 changes no finite row)
       if (jl == 0 && m < p.M) {
         if (p.deriv_row_major) p.deriv[m * p.D + d] = gsum;
         else p.deriv[(long long)d * p.M + m] = gsum;
@@ -108,7 +120,7 @@ __global__ __launch_bounds__(gkThreads) void predict_generic_kernel(GenericArgs<
       acc = fma(s, kr[j], acc);
     }
     acc = row16_sum(acc);
-    if (jl == 0 && m < p.M) p.var[m] = b - acc;
+    if (jl == 0 && m < p.M) p.var[m] = b - acc + poison;
   }
 }
 

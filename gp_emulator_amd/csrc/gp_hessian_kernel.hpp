@@ -18,6 +18,13 @@
 // per SIMD: up to 136 fp64 accumulators), are summed over the four lane groups at the end,
 // and each lane group writes a quarter of the rows of the (D, D) block.  The loop over
 // training points is a real loop (nothing is indexed by it), so the code stays small.
+//
+// Far, infinite and NaN test rows (the rule beside Real<double>::kFarG): exp_clamped gives w_i = 0 for a row that is
+// absurdly far away, and the matrix is exactly 0.  It gives 0 for a NaN argument too (fp64) and for -inf (both
+// precisions): only the bad coordinate's row and column of the matrix would then be NaN, the rest 0, where
+// hessian_win_kernel gives NaN throughout.  So each pass forms the row's `poison` = g - g, g = sum_d t''_d^2 (0 for
+// a finite row, NaN otherwise) after its loop, from registers that are live anyway, and carries it into every
+// element: in the scaling's place (an fma for the multiply) and, on the diagonal, through mu as well.
 #pragma once
 #include "gp_predict_kernel.hpp"
 
@@ -126,13 +133,18 @@ __device__ __forceinline__ void hessian_pass(const T* s_xa, const T* s_sd, const
   if (keep == T(-12345.678)) out[0] = keep;
   return;
 #endif
-  mu = xor_reduce_groups(mu);
+  T gm = T(0);
+#pragma unroll
+  for (int d = 0; d < D; ++d) gm = fma(t[d], t[d], gm);
+  const T poison = gm - gm;   // NaN for rows holding a NaN or an infinity (exp_clamped gives 0 there), else 0
+  mu = xor_reduce_groups(mu) + poison;
   int q = 0;
 #pragma unroll
   for (int d = LO; d < HI; ++d) {
 #pragma unroll
     for (int d2 = d; d2 < D; ++d2) {
-      T v = xor_reduce_groups(acc[q]) * (s_sd[d] * s_sd[d2]);
+      // (the multiply's rounding: + 0 changes no finite row)
+      T v = fma(xor_reduce_groups(acc[q]), s_sd[d] * s_sd[d2], poison);
       if (d2 == d) v = fma(-(s_sd[d] * s_sd[d]), mu, v);
       ++q;
 #if GP_HESS_ABLATE == 1   // diagnostic: reductions but no stores

@@ -222,8 +222,10 @@ template <> struct Real<double> {
   }
   // exp_ behind a lower clamp (one v_max_f64), for the kernels whose argument is -r^2/2 of an arbitrary row or that
   // have no row guard (general-shape, few-rows and Hessian kernels): the clamp keeps n inside int32 for absurdly
-  // distant points.  It would turn a NaN argument into exp(-1000) = 0, so those callers add the NaN back per test
-  // row (their `poison`).
+  // distant points.  It turns a NaN argument into exp(-1000) = 0, and -inf and anything below -745.2 give 0 as well
+  // (tests/test_exp_cpu.py), so EVERY caller adds the NaN of a row holding a NaN or an infinity back per test row
+  // (its `poison` = g - g, g the row's sum of squares): predict_few_kernel, predict_generic_kernel, hessian_kernel
+  // and, around exp_n, hessian_win_kernel (tests/test_far_rows_kernels_gpu.py, test_predict_far_rows_gpu.py).
   __host__ __device__ static inline double exp_clamped(double x) { return exp_(__builtin_fmax(x, -1000.0)); }
   // exp_clamped of GP values, written step by step across the values: GP independent dependency chains
   // side by side in program order (for kernels that run one wave per SIMD, where nothing else

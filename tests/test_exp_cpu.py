@@ -9,7 +9,8 @@ file's program and run on the same arguments: the new exp_'s maximum relative er
 most 1.2e-16, the one extra rounding a different n can cost on |r| <= ln2/2 + 2^-52 (the degree-10 interpolant does
 not degrade at that distance outside its interval).  The maximum is taken twice: over every argument with a non-zero
 reference, as stated, where a correctly rounded denormal decides it for both implementations alike, and over the
-normal results alone, where the bound bites.  Arguments below the underflow threshold give exactly 0."""
+normal results alone, where the bound bites.  Arguments below the underflow threshold give exactly 0, and so does
+exp_clamped for NaN, -inf and -1e300."""
 import os
 import shutil
 import subprocess
@@ -122,6 +123,10 @@ int main(int argc, char** argv) {
     printf("negative %ld\n", negative);
     printf("zeros %ld zeros_bad %ld\n", zeros, zeros_bad);
     printf("exp0 %.17g exp1 %.17g\n", gpk::Real<double>::exp_(0.0), gpk::Real<double>::exp_(1.0));
+    // exp_clamped where its callers need their `poison`: NaN, -inf and an absurdly distant point all give 0
+    printf("clamped nan %.17g ninf %.17g far %.17g zero %.17g\n", gpk::Real<double>::exp_clamped(NAN),
+           gpk::Real<double>::exp_clamped(-INFINITY), gpk::Real<double>::exp_clamped(-1e300),
+           gpk::Real<double>::exp_clamped(0.0));
     return 0;
 }
 """
@@ -157,6 +162,8 @@ def exp_report(tmp_path_factory):
             out["zeros"], out["zeros_bad"] = int(f[1]), int(f[3])
         elif f and f[0] == "exp0":
             out["exp0"], out["exp1"] = float(f[1]), float(f[3])
+        elif f and f[0] == "clamped":
+            out["clamped"] = {f[i]: float(f[i + 1]) for i in range(1, len(f), 2)}
     return out
 
 
@@ -187,3 +194,12 @@ def test_exact_zero_below_underflow(exp_report):
 def test_exact_points(exp_report):
     assert exp_report["exp0"] == 1.0
     assert abs(exp_report["exp1"] - 2.718281828459045) <= 4.5e-16
+
+
+def test_exp_clamped_turns_nan_and_infinity_into_zero(exp_report):
+    """exp_clamped(NaN), exp_clamped(-inf) and exp_clamped(-1e300) are exactly 0 (the clamp is a max with -1000, which
+    drops a NaN): the reason every caller adds its row `poison` (tests/test_far_rows_kernels_gpu.py)."""
+    c = exp_report["clamped"]
+    assert set(c) == {"nan", "ninf", "far", "zero"}
+    assert c["nan"] == 0.0 and c["ninf"] == 0.0 and c["far"] == 0.0
+    assert c["zero"] == 1.0
