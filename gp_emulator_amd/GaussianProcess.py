@@ -245,9 +245,8 @@ class GaussianProcess:
         It always runs on the resident model (the twelve-argument boundary has no variance-free
         form), works without ``invQ``, and ``out`` is then ``(mu, deriv)``.
         """
-        precision = np.dtype(precision)
-        if precision not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("precision must be float32 or float64, got %r" % (precision,))
+        from . import _lib
+        precision = _lib.precision_dtype(precision)
         n_predict, n_inputs = testing.shape
         assert n_inputs == self.D
         if not do_unc:
@@ -350,9 +349,8 @@ class GaussianProcess:
         (nn, D) = testing.shape
         assert D == self.D
         if is_gpu == True:  # noqa: E712
-            dt = np.dtype(precision)
-            if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-                raise TypeError("precision must be float32 or float64")
+            from . import _lib
+            dt = _lib.precision_dtype(precision)
             hess = self.gpu_model(dt).hessian(np.asarray(testing))
             return hess.astype(np.float64, copy=False)
         expX = np.exp(self.theta)
@@ -380,9 +378,8 @@ class GaussianProcess:
         (nn, D) = testing.shape
         assert D == self.D
         if is_gpu == True:  # noqa: E712
-            dt = np.dtype(precision)
-            if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-                raise TypeError("precision must be float32 or float64")
+            from . import _lib
+            dt = _lib.precision_dtype(precision)
             var, dvar = self.gpu_model(dt).predict_var_grad(np.ascontiguousarray(testing, dtype=dt))
             return var.astype(np.float64, copy=False), dvar.astype(np.float64, copy=False)
         expX = np.exp(self.theta)

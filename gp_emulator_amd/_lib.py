@@ -230,6 +230,26 @@ def _dtype_code(dtype):
     return GP_F64 if np.dtype(dtype) == np.float64 else GP_F32
 
 
+def precision_dtype(precision):
+    """``precision`` as the device dtype it names: float32 or float64, anything else is a ``TypeError``."""
+    dt = np.dtype(precision)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("precision must be float32 or float64, got %r" % (precision,))
+    return dt
+
+
+def _out_array(a, shape, dtype, pool=None):
+    """The array a host call writes its ``shape``, ``dtype`` result into: the caller's ``a`` once it is checked (an
+    ndarray of exactly that shape and dtype, C-contiguous and writeable -- the library writes through its pointer),
+    or with ``a`` None a fresh one, from ``pool`` (an ``OutputPool``) when given."""
+    if a is None:
+        return pool.take(shape, dtype) if pool is not None else np.empty(shape, dtype)
+    if (not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != shape
+            or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]):
+        raise ValueError("out must be a writeable C-contiguous %s %s array" % (shape, np.dtype(dtype)))
+    return a
+
+
 def _device_dtype(precision, a):
     """The device dtype of a host wrapper: ``precision`` when given, else float32 when ``a`` is float32, else float64."""
     return np.dtype(precision if precision is not None else (np.float32 if a.dtype == np.float32 else np.float64))
@@ -692,31 +712,44 @@ class Context:
 class Model:
     """Per-emulator constants packed and resident in HBM (gp_model)."""
 
+    n_emulators = None            # a BatchModel's E: then every result has a leading (E,)
+    _create = "gp_model_create"   # the C ABI's constructor, without its dtype suffix
+
     def __init__(self, ctx, expX, inputs, invQt, invQ, precision=np.float64):
         self.ctx = ctx
-        self.dtype = np.dtype(precision)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("precision must be float32 or float64, got %r" % (precision,))
+        self.dtype = precision_dtype(precision)
         # constants cross the boundary as float64 whatever the compute type: a float32 model is
         # packed from the float64 values and rounded once (gp_model_create_f32_h64)
         inputs = np.ascontiguousarray(inputs, dtype=np.float64)
         if inputs.ndim != 2:
             raise ValueError("inputs must be (n_train, n_inputs)")
         self.n_train, self.n_inputs = inputs.shape
-        expX = np.ascontiguousarray(expX, dtype=np.float64).ravel()
-        invQt = np.ascontiguousarray(invQt, dtype=np.float64).ravel()
+        expX = np.ascontiguousarray(expX, dtype=np.float64)
+        invQt = np.ascontiguousarray(invQt, dtype=np.float64)
+        if invQ is not None:             # None: no variance operand is packed or uploaded
+            invQ = np.ascontiguousarray(invQ, dtype=np.float64)
+        expX, invQt, lead = self._emulator_constants(expX, invQt, invQ)
+        fn = getattr(ctx.lib, self._create + ("_f64" if self.dtype == np.float64 else "_f32_h64"))
+        h = c_void_p()
+        check(fn(ctx.h, *lead, _ptr(expX), _ptr(inputs), _ptr(invQt), _ptr(invQ) if invQ is not None else None,
+                 self.n_train, self.n_inputs, expX.shape[-1], ctypes.byref(h)), self._create)
+        self.h = h
+
+    def _emulator_constants(self, expX, invQt, invQ):
+        """``(expX, invQt, lead)`` as the constructor's call takes them, the shapes checked; ``lead`` holds the
+        arguments in front of the arrays: none here, ``(E,)`` for a batch."""
+        expX, invQt = expX.ravel(), invQt.ravel()
         if invQt.size != self.n_train:
             raise ValueError("invQt size does not match n_train")
-        if invQ is not None:             # None: Hessian-only model (no variance operand)
-            invQ = np.ascontiguousarray(invQ, dtype=np.float64)
-            if invQ.size != self.n_train ** 2:
-                raise ValueError("invQ size does not match n_train")
-        fn = ctx.lib.gp_model_create_f64 if self.dtype == np.float64 else ctx.lib.gp_model_create_f32_h64
-        h = c_void_p()
-        check(fn(ctx.h, _ptr(expX), _ptr(inputs), _ptr(invQt),
-                 _ptr(invQ) if invQ is not None else None,
-                 self.n_train, self.n_inputs, expX.size, ctypes.byref(h)), "gp_model_create")
-        self.h = h
+        if invQ is not None and invQ.size != self.n_train ** 2:
+            raise ValueError("invQ size does not match n_train")
+        return expX, invQt, ()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def info(self):
         v = [c_int(0) for _ in range(5)]
@@ -793,17 +826,14 @@ class Model:
         if testing.ndim != 2 or testing.shape[1] != self.n_inputs:
             raise ValueError("testing must be (n_predict, %d)" % self.n_inputs)
         M, D = testing.shape
-        E = getattr(self, "n_emulators", None)
+        E = self.n_emulators
         lead, ne = (() if E is None else (E,)), (E or 1)
         row_major = deriv_layout == GP_DERIV_ROWMAJOR
         shapes = (lead + (M,), lead + ((M, D) if row_major else (D, M)))
-        if out is None:
-            out = tuple(np.empty(sh, self.dtype) for sh in shapes)
-        var, dvar = out
-        for a, shape in zip((var, dvar), shapes):
-            if (not isinstance(a, np.ndarray) or a.dtype != self.dtype or a.shape != shape
-                    or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]):
-                raise ValueError("out arrays must be writeable C-contiguous %s arrays of shapes %s, %s" % ((self.dtype,) + shapes))
+        var, dvar = (None, None) if out is None else out
+        if out is not None and (var is None or dvar is None):
+            raise ValueError("out must hold 2 arrays")
+        var, dvar = (_out_array(a, shape, self.dtype) for a, shape in zip((var, dvar), shapes))
         v2, d3 = var.reshape(ne, M), dvar.reshape((ne, M, D) if row_major else (ne, D, M))
         isz = self.dtype.itemsize
         for lo in range(0, M, self.VAR_GRAD_BLOCK_ROWS):
@@ -834,7 +864,7 @@ class Model:
         M, D = testing.shape
         if D != self.n_inputs:
             raise ValueError("testing has %d columns, model has %d inputs" % (D, self.n_inputs))
-        E = getattr(self, "n_emulators", None)
+        E = self.n_emulators
         lead = () if E is None else (E,)
         dshape = lead + ((M, D) if deriv_layout == GP_DERIV_ROWMAJOR else (D, M))
         nv = 2 if with_var else 1
@@ -848,34 +878,38 @@ class Model:
             outs += (flat[nv * n_e:].reshape(dshape),)
         else:
             outs = tuple(out)
-            if len(outs) != nv + 1:
+            if len(outs) != nv + 1 or any(a is None for a in outs):
                 raise ValueError("out must hold %d arrays" % (nv + 1))
-            for a, shape in zip(outs, shapes):
-                if (not isinstance(a, np.ndarray) or a.dtype != hdt or a.shape != shape
-                        or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]):
-                    raise ValueError("out arrays must be writeable C-contiguous %s arrays of shapes "
-                                     "%s" % (hdt, ", ".join(str(x) for x in shapes)))
+            outs = tuple(_out_array(a, shape, hdt) for a, shape in zip(outs, shapes))
         return testing, outs
 
     def hessian_device(self, d_testing, d_hess, n_predict):
-        """Asynchronous Hessian launch; device pointers, hess is (n_predict, D, D)."""
+        """Asynchronous Hessian launch; device pointers, hess is (n_predict, D, D) -- for a batch
+        (E, n_predict, D, D), the whole batch in the one launch: emulator e bit for bit what a ``Model``
+        of it gives on the same rows."""
         check(self.ctx.lib.gp_hessian_device(self.ctx.h, self.h, d_testing, d_hess,
                                              int(n_predict)), "gp_hessian_device")
 
-    def hessian(self, testing, out=None):
-        """(M, D, D) Hessian of the mean for host rows, through the slab pipeline.  Rows of the
-        model's dtype give matrices of that dtype; float64 rows on a float32 model are converted
-        while they are staged and the matrices come back as float64 (``gp_hessian_host_h64``)."""
+    def _hessian_rows(self, testing):
+        """The rows as the library takes them, their dtype and whether the float64-rows-on-a-float32-model
+        entry point serves the call (rules of ``hessian``)."""
         testing = np.asarray(testing)
         h64 = testing.dtype == np.float64 and self.dtype != np.float64
         hdt = np.dtype(np.float64) if h64 else self.dtype
         testing = np.ascontiguousarray(testing, dtype=hdt)
+        if testing.ndim != 2 or testing.shape[1] != self.n_inputs:
+            raise ValueError("testing must be (n_predict, %d)" % self.n_inputs)
+        return testing, hdt, h64
+
+    def hessian(self, testing, out=None):
+        """(M, D, D) Hessian of the mean for host rows, through the slab pipeline -- for a batch
+        (E, M, D, D), one launch per slab for all emulators.  Rows of the
+        model's dtype give matrices of that dtype; float64 rows on a float32 model are converted
+        while they are staged and the matrices come back as float64 (``gp_hessian_host_h64``)."""
+        testing, hdt, h64 = self._hessian_rows(testing)
         M, D = testing.shape
-        if D != self.n_inputs:
-            raise ValueError("testing has %d columns, model has %d inputs" % (D, self.n_inputs))
-        hess = self.ctx.out_pool.take((M, D, D), hdt) if out is None else out
-        if hess.shape != (M, D, D) or hess.dtype != hdt or not hess.flags["C_CONTIGUOUS"]:
-            raise ValueError("out must be a C-contiguous (M, D, D) %s array" % hdt)
+        lead = () if self.n_emulators is None else (self.n_emulators,)
+        hess = _out_array(out, lead + (M, D, D), hdt, self.ctx.out_pool)
         if M:
             fn = self.ctx.lib.gp_hessian_host_h64 if h64 else self.ctx.lib.gp_hessian_host
             check(fn(self.ctx.h, self.h, _ptr(testing), _ptr(hess), M), "gp_hessian_host")
@@ -901,58 +935,15 @@ class BatchModel(Model):
     misfit summed over the emulators: cost (M,), grad (M, D) and the second-order terms (M, D, D).
     """
 
-    def __init__(self, ctx, expX, inputs, invQt, invQ, precision=np.float64):
-        self.ctx = ctx
-        self.dtype = np.dtype(precision)
-        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise TypeError("precision must be float32 or float64, got %r" % (precision,))
-        inputs = np.ascontiguousarray(inputs, dtype=np.float64)
-        self.n_train, self.n_inputs = inputs.shape
-        expX = np.ascontiguousarray(expX, dtype=np.float64)
+    _create = "gp_batch_create"
+
+    def _emulator_constants(self, expX, invQt, invQ):
         if expX.ndim != 2:
             raise ValueError("expX must be (n_emulators, theta_size)")
         self.n_emulators = E = expX.shape[0]
-        invQt = np.ascontiguousarray(invQt, dtype=np.float64)
-        if invQ is not None:
-            invQ = np.ascontiguousarray(invQ, dtype=np.float64)
         if invQt.shape != (E, self.n_train) or (invQ is not None and invQ.shape != (E, self.n_train, self.n_train)):
             raise ValueError("invQt must be (E, N) and invQ (E, N, N)")
-        fn = ctx.lib.gp_batch_create_f64 if self.dtype == np.float64 else ctx.lib.gp_batch_create_f32_h64
-        h = c_void_p()
-        check(fn(ctx.h, E, _ptr(expX), _ptr(inputs), _ptr(invQt), _ptr(invQ) if invQ is not None else None,
-                 self.n_train, self.n_inputs, expX.shape[1], ctypes.byref(h)), "gp_batch_create")
-        self.h = h
-
-    def hessian_device(self, d_testing, d_hess, n_predict):
-        """Asynchronous Hessian launch for the whole batch; device pointers, hess is
-        (E, n_predict, D, D): emulator e bit for bit what a ``Model`` of it gives on the same rows."""
-        Model.hessian_device(self, d_testing, d_hess, n_predict)
-
-    def _hessian_rows(self, testing):
-        """The rows as the library takes them, their dtype and whether the float64-rows-on-a-float32-model
-        entry point serves the call (rules of ``Model.hessian``)."""
-        testing = np.asarray(testing)
-        h64 = testing.dtype == np.float64 and self.dtype != np.float64
-        hdt = np.dtype(np.float64) if h64 else self.dtype
-        testing = np.ascontiguousarray(testing, dtype=hdt)
-        if testing.ndim != 2 or testing.shape[1] != self.n_inputs:
-            raise ValueError("testing must be (n_predict, %d)" % self.n_inputs)
-        return testing, hdt, h64
-
-    def hessian(self, testing, out=None):
-        """(E, M, D, D) Hessians of the E means for host rows (``gp_hessian_host`` on the batch: one
-        launch per slab for all emulators).  dtype rules of ``Model.hessian``."""
-        testing, hdt, h64 = self._hessian_rows(testing)
-        M, D = testing.shape
-        shape = (self.n_emulators, M, D, D)
-        hess = self.ctx.out_pool.take(shape, hdt) if out is None else out
-        if (not isinstance(hess, np.ndarray) or hess.shape != shape or hess.dtype != hdt
-                or not hess.flags["C_CONTIGUOUS"] or not hess.flags["WRITEABLE"]):
-            raise ValueError("out must be a writeable C-contiguous %s %s array" % (shape, hdt))
-        if M:
-            fn = self.ctx.lib.gp_hessian_host_h64 if h64 else self.ctx.lib.gp_hessian_host
-            check(fn(self.ctx.h, self.h, _ptr(testing), _ptr(hess), M), "gp_hessian_host")
-        return hess
+        return expX, invQt, (E,)
 
     def hessian_weighted_device(self, d_testing, d_weights, d_out, n_predict):
         """Asynchronous ``out[m] = sum_e weights[e][m] * H_e[m]``; device pointers of the model's dtype,
@@ -969,11 +960,7 @@ class BatchModel(Model):
         weights = np.ascontiguousarray(weights, dtype=hdt)
         if weights.shape != (self.n_emulators, M):
             raise ValueError("weights must be (%d, %d)" % (self.n_emulators, M))
-        shape = (M, D, D)
-        res = self.ctx.out_pool.take(shape, hdt) if out is None else out
-        if (not isinstance(res, np.ndarray) or res.shape != shape or res.dtype != hdt
-                or not res.flags["C_CONTIGUOUS"] or not res.flags["WRITEABLE"]):
-            raise ValueError("out must be a writeable C-contiguous %s %s array" % (shape, hdt))
+        res = _out_array(out, (M, D, D), hdt, self.ctx.out_pool)
         if M:
             check(self.ctx.lib.gp_hessian_weighted_host(
                 self.ctx.h, self.h, _dtype_code(hdt), _ptr(testing), _ptr(weights),

@@ -42,7 +42,7 @@ def source_digest():
             if os.path.isfile(p) and name.endswith((".hip", ".hpp", ".h", ".cpp")):
                 h.update(name.encode())
                 h.update(open(p, "rb").read())
-    h.update(" ".join(FLAGS).encode())
+    h.update(" ".join(FLAGS).replace(ROOT, ".").encode())    # (the stamp travels with the .so: no absolute path in it)
     return h.hexdigest()
 
 

@@ -15,6 +15,7 @@ likelihood kernel (they share the training inputs), or the GPU training objectiv
 """
 import numpy as np
 
+from . import _lib
 from .GaussianProcess import GaussianProcess
 
 __all__ = ["MultivariateEmulator"]
@@ -94,7 +95,6 @@ class MultivariateEmulator(object):
         self.hyperparams[:, :] = np.asarray(hyperparams)[:, :self.n_pcs]
         if is_gpu and self.n_pcs > 0:
             # the emulators differ in targets and theta only: one launch, one workgroup each
-            from . import _lib
             cost, grad, invQ, invQt = _lib.default_context().likelihood_batch(
                 self.hyperparams.T, np.atleast_2d(y), train_data, want_inverse=True)
             bad = np.flatnonzero(~np.isfinite(cost))
@@ -161,7 +161,7 @@ class MultivariateEmulator(object):
         digest is re-taken on EVERY call -- inside the library call, while the device works and the calling
         thread would only wait (``gp_mv_predict_host_checked``), so the latency path pays nothing for it; a
         mismatch discards that call's results, rebuilds the state and calls again."""
-        from . import _lib, perband
+        from . import perband
         cache = self.__dict__.setdefault("_gpu", {})
         key = (dt.str, _lib.default_device())
         arrays = self._host_arrays()
@@ -187,7 +187,6 @@ class MultivariateEmulator(object):
     def _rebuilt_gpu_state(self, dt, st):
         """The host arrays were edited in place since the resident copy ``st`` was made: discard it and build the
         state again from what they hold now."""
-        from . import _lib
         self._release(st)
         del self.__dict__["_gpu"][(dt.str, _lib.default_device())]
         return self._gpu_state(dt)
@@ -224,7 +223,6 @@ class MultivariateEmulator(object):
                 return fwd
             grads = np.stack([o[2] for o in out])                  # (P, M, D)
             return fwd, np.einsum("pmd,pb->mdb", grads, self.basis_functions)
-        from . import _lib
         dt = np.dtype(precision)
         st = self._gpu_state(dt)
         ctx = st["ctx"]
@@ -239,20 +237,32 @@ class MultivariateEmulator(object):
         else:
             fwd = ctx.out_pool.take((M, B), dt)
             jac = ctx.out_pool.take((M, D, B), dt) if do_deriv else None
+
+        def call(st, ctx, blocks, r0, r1):
+            return ctx.lib.gp_mv_predict_host_checked(ctx.h, st["batch"].h, st["d_basis"], _lib._ptr(Yc[r0:r1]), r1 - r0, B,
+                                                      _lib._ptr(fwd[r0:r1]), _lib._ptr(jac[r0:r1]) if do_deriv else None,
+                                                      blocks.ptrs, blocks.lens, blocks.n, blocks.expected)
+        self._checked_row_blocks(dt, st, M, step, "gp_mv_predict_host_checked", call)
+        return (fwd, jac) if do_deriv else fwd
+
+    def _checked_row_blocks(self, dt, st, M, step, name, call, unpack=None):
+        """The M rows of a checked library call on the resident state ``st``, in blocks ``[r0, r1)`` of at most ``step``
+        rows: ``call(st, ctx, blocks, r0, r1)`` makes the call with the state's host-array table ``blocks``, refreshed,
+        and returns its status; ``unpack(r0, r1)`` then takes the block's results.  On ``GP_STALE`` -- the host arrays
+        were edited in place -- the state is rebuilt and the same rows run again: nothing of the stale call is kept.
+        Returns the state as it is after the last block."""
         r0 = 0
         while r0 < M:
             r1 = min(M, r0 + step)
-            blocks = st["blocks"].refresh()
-            rc = ctx.lib.gp_mv_predict_host_checked(ctx.h, st["batch"].h, st["d_basis"], _lib._ptr(Yc[r0:r1]), r1 - r0, B,
-                                                    _lib._ptr(fwd[r0:r1]), _lib._ptr(jac[r0:r1]) if do_deriv else None,
-                                                    blocks.ptrs, blocks.lens, blocks.n, blocks.expected)
+            rc = call(st, st["ctx"], st["blocks"].refresh(), r0, r1)
             if rc == _lib.GP_STALE:
-                st = self._rebuilt_gpu_state(dt, st)      # and run the same rows again: nothing of the stale call is kept
-                ctx = st["ctx"]
+                st = self._rebuilt_gpu_state(dt, st)
                 continue
-            _lib.check(rc, "gp_mv_predict_host_checked")
+            _lib.check(rc, name)
+            if unpack is not None:
+                unpack(r0, r1)
             r0 = r1
-        return (fwd, jac) if do_deriv else fwd
+        return st
 
     # ---- observation misfit: the data term of a variational retrieval -------------------------------
     def _misfit_args(self, Y, obs, weights, gauss_newton):
@@ -315,11 +325,9 @@ class MultivariateEmulator(object):
             cost, coef, _, grad, gn = self._data_term_numpy(Y, obs, weights, do_deriv, A)
             res = [cost] + [a for a, asked in ((grad, do_deriv), (gn, gauss_newton), (coef, return_coef)) if asked]
             return tuple(res) if len(res) > 1 else cost
-        from . import _lib
         dt = np.dtype(precision)
         isz = dt.itemsize
         st = self._gpu_state(dt)
-        ctx = st["ctx"]
         Yc = np.ascontiguousarray(Y, dtype=dt)
         obs_c = np.ascontiguousarray(obs, dtype=dt)
         w_c = None if weights is None else np.ascontiguousarray(weights, dtype=dt)
@@ -336,28 +344,23 @@ class MultivariateEmulator(object):
         coef = np.empty((M, P), dt)
         gn = np.empty((M, D, D), dt) if gauss_newton else None
         buf = np.empty(min(M, step) * n_row, dt)
-        r0 = 0
-        while r0 < M:
-            r1 = min(M, r0 + step)
-            n = r1 - r0
-            blocks = st["blocks"].refresh()
-            rc = ctx.lib.gp_mv_misfit_host_checked(
+
+        def call(st, ctx, blocks, r0, r1):
+            return ctx.lib.gp_mv_misfit_host_checked(
                 ctx.h, st["batch"].h, st["d_basis"], _lib._ptr(Yc[r0:r1]), D,
                 _lib._ptr(obs_c[r0:r1] if per_obs else obs_c), B if per_obs else 0,
                 None if w_c is None else _lib._ptr(w_c[r0:r1] if per_w else w_c), B if per_w else 0,
-                None if A_c is None else _lib._ptr(A_c), n, B, _lib._ptr(buf),
+                None if A_c is None else _lib._ptr(A_c), r1 - r0, B, _lib._ptr(buf),
                 blocks.ptrs, blocks.lens, blocks.n, blocks.expected)
-            if rc == _lib.GP_STALE:
-                st = self._rebuilt_gpu_state(dt, st)      # and run the same rows again (as predict_many)
-                ctx = st["ctx"]
-                continue
-            _lib.check(rc, "gp_mv_misfit_host_checked")
+
+        def unpack(r0, r1):
+            n = r1 - r0
             cost[r0:r1] = buf[:n]
             grad[r0:r1] = buf[n:n * (1 + D)].reshape(n, D)
             coef[r0:r1] = buf[n * (1 + D):n * (1 + D + P)].reshape(P, n).T
             if gauss_newton:
                 gn[r0:r1] = buf[n * (1 + D + P):n * n_row].reshape(n, D, D)
-            r0 = r1
+        self._checked_row_blocks(dt, st, M, step, "gp_mv_misfit_host_checked", call, unpack)
         res = [cost]
         if do_deriv:
             res.append(grad)
@@ -396,17 +399,13 @@ class MultivariateEmulator(object):
         ctx = st["ctx"]
         out = np.empty((M, P, P), dt)
         step = max(1, (1 << 30) // (B * isz))                  # at most 1 GiB of weights on the device
-        d_w = ctx.malloc(max(1, min(M, step) * B * isz))
-        d_g = ctx.malloc(max(1, min(M, step) * P * P * isz))
-        try:
+        with _lib.Scratch(ctx, dt) as scratch:
+            d_w, d_g = scratch.alloc(min(M, step) * B * isz), scratch.alloc(min(M, step) * P * P * isz)
             for r0 in range(0, M, step):
                 n = min(M, r0 + step) - r0
                 ctx.h2d(d_w, np.ascontiguousarray(weights[r0:r0 + n], dtype=dt))
                 ctx.mv_weight_gram_device(dt, st["d_basis"], d_w, B, d_g, n, P, B)
                 out[r0:r0 + n] = ctx.to_host(d_g, (n, P, P), dt)
-        finally:
-            ctx.free(d_w)
-            ctx.free(d_g)
         return out
 
     @staticmethod
@@ -445,9 +444,8 @@ class MultivariateEmulator(object):
         out = np.empty((M, D, D), dt)
         step = max(1, (1 << 30) // (max(B, P * D, D * D) * isz))      # at most 1 GiB per device array
         n0 = min(M, step)
-        held = [ctx.malloc(max(1, n0 * k * isz)) for k in (D, B, P, P * D, P * P, D * D)]
-        d_y, d_w, d_mu, d_der, d_g, d_gn = held
-        try:
+        with _lib.Scratch(ctx, dt) as scratch:
+            d_y, d_w, d_mu, d_der, d_g, d_gn = [scratch.alloc(n0 * k * isz) for k in (D, B, P, P * D, P * P, D * D)]
             for r0 in range(0, M, step):
                 n = min(M, r0 + step) - r0
                 ctx.h2d(d_y, Yc[r0:r0 + n])
@@ -456,9 +454,6 @@ class MultivariateEmulator(object):
                 ctx.mv_weight_gram_device(dt, st["d_basis"], d_w, B, d_g, n, P, B)
                 ctx.mv_gauss_newton_rows_device(dt, d_der, d_g, P * P, d_gn, n, P, D)
                 out[r0:r0 + n] = ctx.to_host(d_gn, (n, D, D), dt)
-        finally:
-            for p_ in held:
-                ctx.free(p_)
         return out
 
     def _data_term_numpy(self, Y, obs, weights, do_deriv=True, G=None):
@@ -525,7 +520,7 @@ class MultivariateEmulator(object):
 
         ``return_A=True`` appends, as the last element, the loop's final data-term matrix ``A (M, D, D)`` (the
         Gauss-Newton term whose ``(A + P)^-1`` is ``cov``), as ``retrieve_bands`` does.  With ``False`` nothing changes."""
-        from . import _lib, _retrieve
+        from . import _retrieve
         Y0 = np.asarray(Y0)
         if Y0.ndim != 2:
             raise ValueError("Y0 must be (n_rows, n_inputs)")
@@ -645,7 +640,6 @@ class MultivariateEmulator(object):
             if coef is None:
                 return np.einsum("pmde,pb->mdeb", hp, basis)
             return np.einsum("pmde,pm->mde", hp, coef)
-        from . import _lib
         dt = np.dtype(precision)
         st = self._fresh_gpu_state(dt)
         ctx, batch = st["ctx"], st["batch"]
@@ -656,10 +650,9 @@ class MultivariateEmulator(object):
         # rows per round: at most 1 GiB of results on the device (as gp_mv_predict_host)
         step = max(1, (1 << 30) // (D * D * B * isz))
         out = ctx.out_pool.take((M, D, D, B), dt)
-        d_y = ctx.malloc(max(1, min(M, step) * D * isz))
-        d_h = ctx.malloc(max(1, P * min(M, step) * D * D * isz))
-        d_o = ctx.malloc(max(1, min(M, step) * D * D * B * isz))
-        try:
+        n0 = min(M, step)
+        with _lib.Scratch(ctx, dt) as scratch:
+            d_y, d_h, d_o = [scratch.alloc(n0 * k * isz) for k in (D, P * D * D, D * D * B)]
             for r0 in range(0, M, step):
                 n = min(M, r0 + step) - r0
                 ctx.h2d(d_y, Yc[r0:r0 + n])
@@ -667,7 +660,4 @@ class MultivariateEmulator(object):
                 ctx.reconstruct_device(dt, st["d_basis"], d_h, d_o, n * D * D, P, B)
                 _lib.check(ctx.lib.gp_memcpy_d2h(ctx.h, _lib._ptr(out[r0:r0 + n]), d_o, n * D * D * B * isz),
                            "gp_memcpy_d2h")
-        finally:
-            for p_ in (d_y, d_h, d_o):
-                ctx.free(p_)
         return out

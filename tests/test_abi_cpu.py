@@ -41,6 +41,26 @@ def test_library_on_disk_is_built_from_these_sources():
         "libgp_predict_hip.so is stale (sources changed, or the last build failed): python -m gp_emulator_amd.build"
 
 
+def test_source_digest_does_not_depend_on_where_the_tree_lies(tmp_path):
+    """The stamp travels with the .so to wherever the tree is copied: the same sources under another root give the
+    same digest (the flags' include paths enter it relative to the root), and an edited source gives another."""
+    import importlib.util
+    import shutil
+    from gp_emulator_amd import build as gpbuild
+    pkg = tmp_path / "elsewhere" / "gp_emulator_amd"
+    shutil.copytree(gpbuild.CSRC, pkg / "csrc", ignore=shutil.ignore_patterns("_obj"))
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "elsewhere" / "include")
+    shutil.copy(gpbuild.__file__, pkg / "build.py")
+    spec = importlib.util.spec_from_file_location("gp_build_elsewhere", str(pkg / "build.py"))
+    moved = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(moved)
+    assert moved.ROOT == str(tmp_path / "elsewhere") and moved.FLAGS != gpbuild.FLAGS
+    assert moved.source_digest() == gpbuild.source_digest()
+    with open(pkg / "csrc" / "gp_dispatch.hpp", "a") as fh:
+        fh.write("\n")
+    assert moved.source_digest() != gpbuild.source_digest()
+
+
 def test_header_is_plain_c_and_links_from_c(tmp_path):
     """The boundary is a C ABI: include/gp_predict_hip.h compiles as strict C99 and a C program
     links against the library and calls it (device count, error string, version) -- no C++, no
@@ -383,3 +403,56 @@ def test_content_digest_sees_every_byte_and_host_blocks_follow_edits():
     assert hb.unchanged()
     lst[2] = 4.0
     assert not hb.unchanged()
+
+
+def test_out_array_takes_only_what_the_library_may_write_through():
+    """``_lib._out_array``, the one check of every ``out=`` array (predict, variance gradient, Hessians): the caller's
+    array itself when it fits, a ``ValueError`` for anything the library could not write through its pointer -- a
+    read-only array among them, which ``Model.hessian(out=)`` used to hand on -- and a fresh array for None."""
+    shape, dt = (3, 4), np.dtype(np.float32)
+    good = np.zeros(shape, dt)
+    assert _lib._out_array(good, shape, dt) is good
+    frozen = np.zeros(shape, dt)
+    frozen.setflags(write=False)
+    misses = {"a list": good.tolist(), "dtype": np.zeros(shape, np.float64), "shape": np.zeros((4, 3), dt),
+              "not contiguous": np.zeros((4, 3), dt).T, "read-only": frozen}
+    assert misses["not contiguous"].shape == shape and not misses["not contiguous"].flags["C_CONTIGUOUS"]
+    for why, a in misses.items():
+        with pytest.raises(ValueError):
+            _lib._out_array(a, shape, dt)
+            pytest.fail("accepted: " + why)
+    for pool in (None, _lib.OutputPool()):
+        fresh = _lib._out_array(None, shape, dt, pool)
+        assert isinstance(fresh, np.ndarray) and fresh.shape == shape and fresh.dtype == dt
+        assert fresh.flags["C_CONTIGUOUS"] and fresh.flags["WRITEABLE"]
+    big = _lib._out_array(None, (1 << 18, 2), np.float64, _lib.OutputPool())       # 4 MB: the pool's own memory
+    assert big.shape == (1 << 18, 2) and big.dtype == np.float64 and big.base is not None
+
+
+def test_hessian_refuses_a_read_only_out_array():
+    """The Hessian path's ``out=`` goes through the same check on a single model and on a batch: a read-only array
+    is refused before any library call (no device is needed to get that far)."""
+    class NoDevice(_lib.Model):
+        class ctx:
+            out_pool = _lib.OutputPool()
+
+        def __init__(self, E=None):
+            self.dtype, self.n_inputs, self.n_train, self.n_emulators, self.h = np.dtype(np.float64), 3, 10, E, None
+    rows = np.zeros((5, 3))
+    for E in (None, 2):
+        out = np.zeros(((E,) if E else ()) + (5, 3, 3))
+        out.setflags(write=False)
+        with pytest.raises(ValueError):
+            NoDevice(E).hessian(rows, out=out)
+        with pytest.raises(ValueError):
+            NoDevice(E).hessian(rows, out=np.zeros((5, 3, 3) if E else (2, 5, 3, 3)))    # the other class's shape
+
+
+def test_precision_dtype_names_float32_or_float64_only():
+    for given, dt in ((np.float32, np.float32), (np.float64, np.float64), (np.dtype(np.float32), np.float32),
+                      (np.dtype(np.float64), np.float64), ("float32", np.float32), ("float64", np.float64)):
+        got = _lib.precision_dtype(given)
+        assert isinstance(got, np.dtype) and got == np.dtype(dt)
+    for bad in (np.float16, int):
+        with pytest.raises(TypeError):
+            _lib.precision_dtype(bad)
