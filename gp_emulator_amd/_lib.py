@@ -73,6 +73,8 @@ SIGNATURES = {
     "gp_hessian_weighted_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_band_misfit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
+    "gp_band_misfit_unc_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_band_misfit_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_i64,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64]),
     "gp_newton_step_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 7 + [c_i64, c_int]),
@@ -1019,6 +1021,77 @@ class BatchModel(Model):
             out += (second,)
         if return_residual:
             out += (wr,)
+        return out
+
+    def misfit_unc_device(self, d_testing, d_obs, obs_strides, d_weights, w_strides, d_cost, d_grad, n_rows,
+                          d_wr=None, d_weff=None, d_gn=None):
+        """Asynchronous observation misfit with the emulators' predictive variance in the data term
+        (``gp_band_misfit_unc_device``: the formulas); device pointers of the model's dtype, strides as
+        ``misfit_device``'s.  cost (n_rows), grad (n_rows, D) and, when their pointers are given, wr and weff
+        (E, n_rows) and gn (n_rows, D, D).  The batch must hold invQ."""
+        ws = w_strides if d_weights is not None else (0, 0)
+        check(self.ctx.lib.gp_band_misfit_unc_device(
+            self.ctx.h, self.h, d_testing, d_obs, int(obs_strides[0]), int(obs_strides[1]), d_weights, int(ws[0]),
+            int(ws[1]), d_cost, d_grad, d_wr, d_weff, d_gn, int(n_rows)), "gp_band_misfit_unc_device")
+
+    MISFIT_UNC_BLOCK_ROWS = 1 << 20
+
+    def misfit_unc(self, testing, obs, weights=None, second_order=None, return_residual=False):
+        """``misfit`` with the emulators' own variance ``v_e(x_m)`` added to the observation's: per emulator and row
+        ``weff = w / (1 + w v)``, ``cost = 1/2 sum_e [weff r^2 + log1p(w v)]``, ``grad`` its gradient (through the mean
+        AND the variance), and with ``second_order="gauss_newton"`` the Fisher matrix ``gn = sum_e [weff dmu dmu^T +
+        1/2 weff^2 dv dv^T]``; a variance that is not > 0 counts as 0 (``gp_band_misfit_unc_device`` has the exact
+        formulas and rules).  Returns ``cost (M,), grad (M, D)[, gn (M, D, D)][, wr (E, M), weff (E, M)]`` with
+        ``wr = weff r``.  Uploads, launches and downloads in row blocks of at most 2^20 rows.  Rows, ``obs`` and
+        ``weights`` are CONVERTED TO THE MODEL'S DTYPE BY PLAIN ROUNDING (float64 arrays on a float32 model lose
+        their low bits before anything is formed from them), and the results have the model's dtype.  There is no
+        ``"full"``: it would need the Hessian of the variance."""
+        if second_order == "full":
+            raise ValueError("second_order='full' needs the Hessian of the variance: not available with the emulator variance")
+        if second_order not in (None, "gauss_newton"):
+            raise ValueError("second_order must be None or 'gauss_newton'")
+        dt = self.dtype
+        testing = np.ascontiguousarray(testing, dtype=dt)
+        if testing.ndim != 2 or testing.shape[1] != self.n_inputs:
+            raise ValueError("testing must be (n_rows, %d)" % self.n_inputs)
+        M, D = testing.shape
+        E = self.n_emulators
+        obs, os_ = self._em_array(obs, M, dt, "obs")
+        if weights is not None:
+            weights, ws = self._em_array(weights, M, dt, "weights")
+        cost, grad = np.empty((M,), dt), np.empty((M, D), dt)
+        gn = np.empty((M, D, D), dt) if second_order else None
+        wr, weff = (np.empty((E, M), dt), np.empty((E, M), dt)) if return_residual else (None, None)
+        isz = dt.itemsize
+
+        def rows_of(a, strides, lo, n):          # a block of rows of an (E,) or (E, M) array and its strides
+            return (a, strides) if strides[1] == 0 else (a[:, lo:lo + n], (n, 1))
+        for lo in range(0, M, self.MISFIT_UNC_BLOCK_ROWS):
+            n = min(self.MISFIT_UNC_BLOCK_ROWS, M - lo)
+            with Scratch(self.ctx, dt) as scratch:
+                d_t = scratch.up(testing[lo:lo + n])
+                o_blk, o_st = rows_of(obs, os_, lo, n)
+                d_o = scratch.up(o_blk)
+                d_w, w_st = None, (0, 0)
+                if weights is not None:
+                    w_blk, w_st = rows_of(weights, ws, lo, n)
+                    d_w = scratch.up(w_blk)
+                d_c, d_g = scratch.alloc(n * isz), scratch.alloc(n * D * isz)
+                d_gn = scratch.alloc(n * D * D * isz) if second_order else None
+                d_wr, d_we = (scratch.alloc(E * n * isz), scratch.alloc(E * n * isz)) if return_residual else (None, None)
+                self.misfit_unc_device(d_t, d_o, o_st, d_w, w_st, d_c, d_g, n, d_wr=d_wr, d_weff=d_we, d_gn=d_gn)
+                cost[lo:lo + n] = _download(self.ctx, d_c, (n,), dt)
+                grad[lo:lo + n] = _download(self.ctx, d_g, (n, D), dt)
+                if second_order:
+                    gn[lo:lo + n] = _download(self.ctx, d_gn, (n, D, D), dt)
+                if return_residual:
+                    wr[:, lo:lo + n] = _download(self.ctx, d_wr, (E, n), dt)
+                    weff[:, lo:lo + n] = _download(self.ctx, d_we, (E, n), dt)
+        out = (cost, grad)
+        if second_order:
+            out += (gn,)
+        if return_residual:
+            out += (wr, weff)
         return out
 
 

@@ -124,7 +124,8 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
                   ("gp_hessian_tu.hip", "hess_" + tname, t)]
     units += [("gp_reconstruct_tu.hip", "reconstruct", []), ("gp_misfit_tu.hip", "misfit", []),
               ("gp_gram_tu.hip", "gram", []), ("gp_var_grad_operand_tu.hip", "vargrad_operand", []),
-              ("gp_band_misfit_tu.hip", "band_misfit", []), ("gp_newton_tu.hip", "newton", []),
+              ("gp_band_misfit_tu.hip", "band_misfit", []), ("gp_band_unc_tu.hip", "band_unc", []),
+              ("gp_newton_tu.hip", "newton", []),
               ("gp_train_tu.hip", "train", [])]
     # the host units (gp_host.hpp lists them)
     units += [("gp_%s.hip" % u, "gp_" + u, []) for u in ("ctx", "model", "device", "solve", "host_path", "folds", "mv")]

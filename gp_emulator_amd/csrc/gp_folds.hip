@@ -2,6 +2,7 @@
 #include "gp_host.hpp"
 
 #include "gp_band_misfit_kernel.hpp"
+#include "gp_band_unc_kernel.hpp"
 #include "gp_hessian_combine_kernel.hpp"
 #include "gp_launchers.hpp"
 
@@ -365,6 +366,84 @@ static int band_misfit_host(gp_ctx* ctx, const gp_model* m, const TH* testing, c
   return GP_OK;
 }
 
+// ---- the same data term with the emulators' predictive variance in it (gp_band_unc_kernel.hpp: the formulas) ----
+// The pattern of band_misfit_slab: per chunk of emulators two launches fill the slab -- the mean+gradient instance
+// of predict_kernel (mu, deriv) and var_grad_kernel (var, dvar), both on the emulator range, both the throughput
+// kernels whatever the size of the call -- and band_unc_fold_kernel folds it.  The slab is bit for bit what
+// gp_predict_mean_grad_* (GP_NO_FEW=1) and gp_predict_var_grad_device give.  Scratch under GP_HESS_WEIGHTED_MB: per
+// row and emulator of a chunk 2 (1 + D) elements, per row the chains' running sums in double.
+template <typename T>
+struct BandUncWork {
+  int64_t slab;
+  int ec;
+  size_t bytes, slab_off;
+  int n_out;            // chains per row: 1 + D (+ D (D + 1) / 2 with gn)
+};
+template <typename T>
+static BandUncWork<T> band_unc_cut(const gp_model* m, int64_t M, bool want_gn) {
+  const size_t D = (size_t)m->n_inputs;
+  BandUncWork<T> w;
+  w.n_out = (int)(1 + D + (want_gn ? D * (D + 1) / 2 : 0));
+  const size_t row = 2 * (1 + D) * sizeof(T), extra = (size_t)w.n_out * sizeof(double);
+  weighted_cut(m, M, row, extra, &w.slab, &w.ec);
+  w.slab_off = ((size_t)w.slab * extra + 255) / 256 * 256;
+  w.bytes = w.slab_off + (size_t)w.ec * w.slab * row;
+  return w;
+}
+template <typename T>
+static int band_unc_device(gp_ctx* ctx, const gp_model* m, const T* d_rows, const T* d_obs, long long o_es, long long o_ms,
+                           const T* d_w, long long w_es, long long w_ms, T* d_cost, T* d_grad, T* d_wr, T* d_weff, T* d_gn,
+                           int64_t M) {
+  const int D = m->n_inputs, E = m->n_emulators;
+  const BandUncWork<T> work = band_unc_cut<T>(m, M, d_gn != nullptr);
+  int rc = ensure_scratch(ctx, work.bytes);
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  double* carry = (double*)ctx->scratch;
+  T* slab = (T*)((char*)ctx->scratch + work.slab_off);
+  for (int64_t s0 = 0; s0 < M; s0 += work.slab) {
+    const int64_t n = s0 + work.slab <= M ? work.slab : M - s0;
+    const T* rows = d_rows + s0 * D;
+    for (int e0 = 0; e0 < E; e0 += work.ec) {
+      const int ne = e0 + work.ec <= E ? work.ec : E - e0;
+      T* mu = slab;
+      T* var = mu + (size_t)ne * n;
+      T* deriv = var + (size_t)ne * n;
+      T* dvar = deriv + (size_t)ne * n * D;
+      rc = predict_device<T>(ctx, m, rows, mu, nullptr, deriv, n, GP_DERIV_ROWMAJOR, st, false, e0, ne, /*allow_few=*/false);
+      if (rc) return rc;
+      rc = var_grad_device<T>(ctx, m, rows, var, dvar, n, GP_DERIV_ROWMAJOR, st, e0, ne);
+      if (rc) return rc;
+      gpk::BandUncArgs<T> a;
+      a.mu = mu;
+      a.deriv = deriv;
+      a.var = var;
+      a.dvar = dvar;
+      a.obs = d_obs + s0 * o_ms + (long long)e0 * o_es;
+      a.weights = d_w ? d_w + s0 * w_ms + (long long)e0 * w_es : nullptr;
+      a.cost = d_cost + s0;
+      a.grad = d_grad + s0 * D;
+      a.gn = d_gn ? d_gn + s0 * D * D : nullptr;
+      a.wr = d_wr ? d_wr + s0 + (long long)e0 * M : nullptr;
+      a.weff = d_weff ? d_weff + s0 + (long long)e0 * M : nullptr;
+      a.carry = carry;
+      a.rows = n;
+      a.obs_es = o_es;
+      a.obs_ms = o_ms;
+      a.w_es = w_es;
+      a.w_ms = w_ms;
+      a.out_es = M;
+      a.d = D;
+      a.n_emulators = ne;
+      a.first = e0 == 0 ? 1 : 0;
+      a.last = e0 + ne == E ? 1 : 0;
+      hipError_t e = gpk::launch_band_unc_fold<T>(a, st);
+      if (e != hipSuccess) return fail(GP_ERR_HIP, "band misfit (emulator variance) fold kernel launch: %s", hipGetErrorString(e));
+    }
+  }
+  return GP_OK;
+}
+
 extern "C" {
 
 int gp_hessian_weighted_device(gp_ctx* ctx, const gp_model* model, const void* d_testing, const void* d_weights,
@@ -414,6 +493,22 @@ int gp_band_misfit_device(gp_ctx* ctx, const gp_model* batch, const void* d_test
   return guarded([&] { return for_dtype(batch->dtype, [&](auto t) {
     return band_misfit_device<GP_TAG_TYPE(t)>(ctx, batch, d_testing, d_obs, obs_estride, obs_mstride, d_weights, w_estride,
                                               w_mstride, d_cost, d_grad, d_wr, d_gn, d_hess, n_rows);
+  }); });
+}
+int gp_band_misfit_unc_device(gp_ctx* ctx, const gp_model* batch, const void* d_testing, const void* d_obs,
+                              int64_t obs_estride, int64_t obs_mstride, const void* d_weights, int64_t w_estride,
+                              int64_t w_mstride, void* d_cost, void* d_grad, void* d_wr, void* d_weff, void* d_gn,
+                              int64_t n_rows) {
+  int rc = band_misfit_args(ctx, batch, d_testing, d_obs, obs_estride, obs_mstride, d_weights, w_estride, w_mstride, d_cost,
+                            d_grad, false, n_rows);
+  if (rc) return rc;
+  if ((rc = check_model(ctx, batch, kNeedVariance)) || n_rows == 0) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return guarded([&] { return for_dtype(batch->dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    return band_unc_device<T>(ctx, batch, (const T*)d_testing, (const T*)d_obs, obs_estride, obs_mstride,
+                              (const T*)d_weights, w_estride, w_mstride, (T*)d_cost, (T*)d_grad, (T*)d_wr, (T*)d_weff,
+                              (T*)d_gn, n_rows);
   }); });
 }
 int gp_band_misfit_host(gp_ctx* ctx, const gp_model* batch, int host_dtype, const void* testing, const void* obs,

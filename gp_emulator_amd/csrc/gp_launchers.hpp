@@ -13,6 +13,7 @@ template <typename T> struct HessianArgs;
 template <typename T> struct HessMfmaArgs;
 template <typename T> struct HessCombineArgs;
 template <typename T> struct BandMisfitArgs;
+template <typename T> struct BandUncArgs;
 template <typename T> struct NewtonArgs;
 template <typename T> struct LmUpdateArgs;
 template <typename T> struct PosteriorCovArgs;
@@ -39,6 +40,7 @@ template <typename T, int NB> hipError_t launch_hessm(int kernel_d, const HessMf
 template <typename T> hipError_t launch_hess_combine(const HessCombineArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_band_misfit_fold(const BandMisfitArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_band_misfit_add(const T* gn, T* hess, long long n, hipStream_t);
+template <typename T> hipError_t launch_band_unc_fold(const BandUncArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_newton_step(const NewtonArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_lm_update(const LmUpdateArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_posterior_cov(const PosteriorCovArgs<T>&, hipStream_t);

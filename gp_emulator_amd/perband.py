@@ -211,8 +211,48 @@ def _misfit_numpy(gps, X, obs, weights, second_order, return_residual):
     return out
 
 
+def _misfit_unc_numpy(gps, X, obs, weights, second_order, return_residual):
+    """The data term with the emulators' variance (``misfit_bands(emulator_unc=True)``: the formulas) in float64, emulator
+    after emulator, from ``cpu_predict(do_unc=True)`` and ``variance_gradient(is_gpu=False)``."""
+    E, (M, D) = len(gps), X.shape
+    cost, grad = np.zeros(M), np.zeros((M, D))
+    gn = np.zeros((M, D, D)) if second_order else None
+    wr, weffs = (np.empty((E, M)), np.empty((E, M))) if return_residual else (None, None)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for e, gp in enumerate(gps):
+            mu, v, deriv = gp.cpu_predict(X, do_unc=True)
+            dv = gp.variance_gradient(X, is_gpu=False)[1]
+            w = np.broadcast_to(weights[e], (M,)) if weights is not None else np.ones(M)
+            r = mu - np.broadcast_to(obs[e], (M,))
+            clamp = v <= 0                                  # (False for a NaN v: it goes through every formula)
+            vp = np.where(clamp, 0.0, v)
+            dvp = np.where(clamp[:, None], 0.0, dv)
+            weff = w / (1.0 + w * vp)
+            a = weff * r
+            c = np.where(clamp, 0.0, 0.5 * weff * (1.0 - a * r))
+            q = np.where(clamp, 0.0, 0.5 * weff * weff)
+            cost += a * r + np.log1p(w * vp)
+            grad += a[:, None] * deriv + c[:, None] * dvp
+            if second_order:
+                gn += weff[:, None, None] * (deriv[:, :, None] * deriv[:, None, :])      # (exactly symmetric)
+                gn += q[:, None, None] * (dvp[:, :, None] * dvp[:, None, :])
+            if return_residual:
+                wr[e], weffs[e] = a, weff
+    out = (0.5 * cost, grad)
+    if second_order:
+        out += (gn,)
+    if return_residual:
+        out += (wr, weffs)
+    return out
+
+
+def _check_unc_order(second_order):
+    if second_order == "full":
+        raise ValueError("second_order='full' needs the Hessian of the variance: not available with emulator_unc=True")
+
+
 def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=False, is_gpu=True,
-                 precision=np.float64, device=None, devices=None, misfit_fn=None):
+                 precision=np.float64, device=None, devices=None, misfit_fn=None, emulator_unc=False):
     """Data term of a variational retrieval on E per-band emulators over shared rows ``X`` (M, D):
 
         r[e, m] = mu_e(x_m) - obs[e, m]            w = 1 without ``weights``
@@ -228,9 +268,27 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
 
     ``devices`` shards the EMULATORS like ``hessian_bands``: every device returns the partial sums of its block and
     they are added on the host in device order (``wr`` rows are the blocks' own).  ``misfit_fn(device, gps_block, X,
-    obs_block, weights_block, second_order, return_residual)`` replaces the HIP path in the CPU tests of that logic."""
+    obs_block, weights_block, second_order, return_residual)`` replaces the HIP path in the CPU tests of that logic.
+
+    ``emulator_unc=True`` adds each emulator's own predictive variance ``v_e(x)`` to the observation's ``1 / w``
+    (``weights`` must then be inverse variances, >= 0).  With ``vp = v if v > 0 else 0`` (and ``dvp = dv/dx`` likewise):
+
+        weff = w / (1 + w vp)                      a = weff r        c = 1/2 weff (1 - a r)      q = 1/2 weff^2
+        cost[m] = 1/2 sum_e [a r + log1p(w vp)]    grad[m] = sum_e [a dmu_e/dx + c dvp]
+        gn[m]   = sum_e [weff dmu dmu^T + q dvp dvp^T]       (c = q = 0 where v <= 0: the plain term with weff = w)
+
+    the Gaussian negative log-likelihood without the constant ``-log w`` and, for ``gn``, the Fisher information of a
+    Gaussian whose mean and variance both depend on x.  ``second_order`` is None or "gauss_newton" ("full" would need
+    the Hessian of the variance: ``ValueError``); ``return_residual`` appends ``wr = weff r`` AND ``weff``, both
+    ``(E, M)``.  On the GPU (``BatchModel.misfit_unc``, ``gp_band_misfit_unc_device``) the batch is built WITH invQ and
+    arrays are converted to ``precision``; ``is_gpu=False`` is the explicit numpy branch from ``cpu_predict(do_unc=True)``
+    and ``variance_gradient(is_gpu=False)``; never a fallback.  ``devices=`` shards as above (every sum is additive
+    over blocks of emulators); ``misfit_fn`` then also receives ``emulator_unc=True`` as a keyword.  With ``False``
+    every path makes exactly the calls it always made."""
     if second_order not in (None, "gauss_newton", "full"):
         raise ValueError("second_order must be None, 'gauss_newton' or 'full'")
+    if emulator_unc:
+        _check_unc_order(second_order)
     X, inputs = _rows_and_inputs(gps, X, "X")
     E, M = len(gps), X.shape[0]
     obs = _em_broadcast(obs, E, M, "obs")
@@ -243,24 +301,27 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
         return a[e0:e1, 0] if a.shape[1] == 1 and M != 1 else a[e0:e1]
 
     def hook(dev, e0, e1):
+        kw = {"emulator_unc": True} if emulator_unc else {}
         return tuple(misfit_fn(dev, gps[e0:e1], X, block(obs, e0, e1), block(weights, e0, e1), second_order,
-                               return_residual))
+                               return_residual, **kw))
 
     def on_device(batch, e0, e1):
-        return batch.misfit(X, block(obs, e0, e1), block(weights, e0, e1), second_order, return_residual)
+        call = batch.misfit_unc if emulator_unc else batch.misfit
+        return call(X, block(obs, e0, e1), block(weights, e0, e1), second_order, return_residual)
 
     if devices is None:
         if misfit_fn is not None:
             return hook(device, 0, E)
         if not is_gpu:
-            return _misfit_numpy(gps, np.asarray(X, dtype=np.float64), obs, weights, second_order, return_residual)
-        with _batch_model(_lib.default_context(device), gps, inputs, precision, False) as batch:
+            numpy_form = _misfit_unc_numpy if emulator_unc else _misfit_numpy
+            return numpy_form(gps, np.asarray(X, dtype=np.float64), obs, weights, second_order, return_residual)
+        with _batch_model(_lib.default_context(device), gps, inputs, precision, bool(emulator_unc)) as batch:
             return on_device(batch, 0, E)
     if len(devices) < 1:
         raise ValueError("devices must name at least one device")
     if not is_gpu and misfit_fn is None:
         raise ValueError("devices= shards the GPU path; the numpy branch runs in the calling thread")
-    partial = _on_shards(gps, devices, inputs, precision, False, on_device, hook if misfit_fn else None)
+    partial = _on_shards(gps, devices, inputs, precision, bool(emulator_unc), on_device, hook if misfit_fn else None)
     parts = [p for p in partial if p is not None]          # device order
     n_sum = 3 if second_order else 2
     total = [np.array(a) for a in parts[0][:n_sum]]
@@ -268,13 +329,14 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
         for acc, a in zip(total, p[:n_sum]):
             acc += a
     if return_residual:
-        total.append(np.concatenate([p[n_sum] for p in parts], axis=0))
+        for k in range(n_sum, n_sum + (2 if emulator_unc else 1)):          # wr (and weff): the blocks' own rows
+            total.append(np.concatenate([p[k] for p in parts], axis=0))
     return tuple(total)
 
 
 def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prior=None, bounds=None, lam0=1e-2,
                    max_iter=20, down=1.0 / 3.0, up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64,
-                   device=None, step_fn=None, return_cov=False, next_prior=None, return_A=False):
+                   device=None, step_fn=None, return_cov=False, next_prior=None, return_A=False, emulator_unc=False):
     """Levenberg-Marquardt retrieval of M state vectors at once on E per-band emulators: minimises, row by row,
 
         F(x) = 1/2 sum_e w (mu_e(x) - obs[e])^2  (+ 1/2 (x - x0)^T P (x - x0) with ``prior=(x0 (D,), P (D, D))``)
@@ -323,9 +385,17 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
 
     ``return_A=True`` appends, as the last element, the loop's final data-term matrix ``A (M, D, D)``: the matrix whose
     ``(A + P)^-1`` is ``cov``, which the backward pass of a smoothed series reads (on the GPU one more download).  With
-    ``False`` nothing changes."""
+    ``False`` nothing changes.
+
+    ``emulator_unc=True`` minimises the data term of ``misfit_bands(emulator_unc=True)`` instead: every emulator's
+    predictive variance widens its observation's, ``A`` is the Fisher matrix, and ``cov``, ``sigma``, ``next_prec``, ``A``
+    and the smoother of ``retrieve_bands_series`` then carry the emulators' share of the error.  The loop is the same;
+    only the misfit it calls differs (``misfit_unc_device`` on a batch built with invQ; ``_misfit_unc_numpy``).
+    ``second_order="full"`` raises ``ValueError``.  With ``False`` nothing changes."""
     if second_order not in ("gauss_newton", "full"):
         raise ValueError("second_order must be 'gauss_newton' or 'full'")
+    if emulator_unc:
+        _check_unc_order(second_order)
     X0, inputs = _rows_and_inputs(gps, X0, "X0")
     E, (M, D) = len(gps), X0.shape
     obs = _em_broadcast(obs, E, M, "obs")
@@ -337,20 +407,23 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     if step_fn is not None or not is_gpu:
         step = step_fn if step_fn is not None else (
             lambda x, g, A, lam: _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds))
-        return _retrieve.lm_numpy(lambda X: _misfit_numpy(gps, X, obs, weights, second_order, False), step, X0, lam0,
+        numpy_form = _misfit_unc_numpy if emulator_unc else _misfit_numpy
+        return _retrieve.lm_numpy(lambda X: numpy_form(gps, X, obs, weights, second_order, False), step, X0, lam0,
                                   max_iter, down, up, ftol, xtol, prior, return_cov, next_prior, return_A)
 
     ctx = _lib.default_context(device)
 
     def strides(a):
         return (1, 0) if a.shape[1] == 1 and M != 1 else (M, 1)
-    with _batch_model(ctx, gps, inputs, precision, False) as batch, \
+    with _batch_model(ctx, gps, inputs, precision, bool(emulator_unc)) as batch, \
             _retrieve.Scratch(ctx, np.dtype(precision)) as scratch:
         d_obs = scratch.up(obs)
         d_w = scratch.up(weights) if weights is not None else None
         os_, ws = strides(obs), strides(weights) if weights is not None else (0, 0)
 
         def misfit(d_rows, c, g, a):
+            if emulator_unc:
+                return batch.misfit_unc_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a)
             batch.misfit_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a if second_order == "gauss_newton" else None,
                                 d_hess=a if second_order == "full" else None)
         return _retrieve.lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,

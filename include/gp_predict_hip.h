@@ -391,6 +391,36 @@ int gp_band_misfit_host(gp_ctx* ctx, const gp_model* batch, int host_dtype, cons
                         int64_t obs_estride, int64_t obs_mstride, const void* weights, int64_t w_estride,
                         int64_t w_mstride, void* cost, void* grad, void* wr, void* gn, void* hess, int64_t n_rows);
 
+/* The same data term with the emulators' own predictive variance in it: the observation's variance 1 / w is widened
+ * by v_e(x_m), the variance the emulator reports at the row.  `batch` must have been created WITH invQ.  Per row m and
+ * emulator e, w = w[e][m] (1 when d_weights is NULL; must be >= 0, not checked), r = mu_e(x_m) - obs[e][m],
+ * v = var_e(x_m):
+ *   vp  = v if v > 0 else 0             dvp = dvar_e/dx if v > 0 else 0        (a NaN v stays NaN in both)
+ *   weff = w / (1 + w vp)               = 1 / (sigma_obs^2 + v)
+ *   a = weff r       c = 1/2 weff (1 - a r), 0 where v <= 0       q = 1/2 weff^2, 0 where v <= 0
+ *   cost[m]        = 1/2 sum_e [ a r + log1p(w vp) ]                     d_cost [n_rows]    (>= 0: the Gaussian
+ *                                                       -log-likelihood without the constant -log w)
+ *   grad[m][d]     = sum_e [ a dmu_e/dx_d + c dvp_d ]                    d_grad [n_rows][n_inputs]
+ *   gn[m][d][d2]   = sum_e [ weff dmu_d dmu_d2 + q dvp_d dvp_d2 ]        d_gn   [n_rows][n_inputs][n_inputs] (nullable)
+ *                    the Fisher information of a Gaussian whose mean and variance both depend on x: PSD
+ *   wr[e][m] = a,  weff[e][m] = weff                                     d_wr, d_weff [n_emulators][n_rows] (nullable)
+ * Four rules hold exactly.  (1) w = 0 on finite values contributes exactly 0 to every sum: a masked band.  (2) v <= 0
+ * (a cancelled variance, an invQ that is no inverse) makes the term gp_band_misfit_device's, weff = w.  (3) A far row
+ * (mu = 0, v = b, both gradients 0) has grad = 0 and gn = 0 exactly and
+ * cost = 1/2 sum_e [ w obs^2 / (1 + w b) + log1p(w b) ].  (4) A row holding a NaN or an infinity is NaN in every
+ * element of every output, and every other row is bit for bit what the call without those rows gives.
+ * There is no full second-order term: it would need the Hessian of the variance.
+ * Strides, argument checks and the scratch budget are gp_band_misfit_device's.  Per chunk of emulators the slab is
+ * filled by the throughput kernels of gp_predict_mean_grad_device and gp_predict_var_grad_device on the emulator range
+ * (2 (1 + n_inputs) elements per row and emulator) and folded in ascending emulator order, in double in both
+ * precisions, one rounding on store; no atomics, bit-identical however the call is cut, gn exactly symmetric.
+ * GP_ERR_INVALID for a batch without invQ, GP_ERR_UNSUPPORTED beyond gp_predict_var_grad_device's shapes (n_train >
+ * 320 or n_inputs > 16).  Device pointers of the model's dtype, asynchronous on the context's stream. */
+int gp_band_misfit_unc_device(gp_ctx* ctx, const gp_model* batch, const void* d_testing, const void* d_obs,
+                              int64_t obs_estride, int64_t obs_mstride, const void* d_weights, int64_t w_estride,
+                              int64_t w_mstride, void* d_cost, void* d_grad, void* d_wr, void* d_weff, void* d_gn,
+                              int64_t n_rows);
+
 /* ---- damped Newton step and Levenberg-Marquardt update ----------------------------------------------
  * What consumes cost, grad and gn / hess of the misfit entries above without their leaving the device; the two
  * entries do not know where d_grad and d_A came from.  For each of n_rows rows, D = n_inputs,
