@@ -98,6 +98,8 @@ SIGNATURES = {
     "gp_mv_gauss_newton_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
     "gp_mv_weight_gram_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int]),
     "gp_mv_gauss_newton_rows_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int]),
+    "gp_mv_misfit_unc_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64] + [c_void_p] * 8
+                                + [c_i64, c_int, c_int]),
     "gp_mv_misfit_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                   c_void_p, c_i64, c_int, c_void_p]),
     "gp_mv_misfit_host_checked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
@@ -491,6 +493,16 @@ class Context:
         matrix for all rows, which is ``mv_gauss_newton_device``."""
         check(self.lib.gp_mv_gauss_newton_rows_device(self.h, _dtype_code(dtype), d_deriv, d_gram, int(gram_stride), d_gn, int(n_rows),
                                                       int(n_pcs), int(n_inputs)), "gp_mv_gauss_newton_rows_device")
+
+    def mv_misfit_unc_device(self, dtype, d_cost0, d_coef, d_gram, gram_stride, d_var, d_deriv, d_dvar, d_cost, d_grad,
+                             d_gn, n_rows, n_pcs, n_inputs, d_ceff=None, d_geff=None):
+        """The per-PC emulators' variance in the data term (asynchronous; ``gp_mv_misfit_unc_device``: the formulas): from
+        ``mv_misfit_device``'s cost0 [M] and coef [P][M], the matrix ``basis diag(w) basis^T`` at ``d_gram + m *
+        gram_stride`` elements (0 = one for all rows), var [P][M], deriv and dvar [P][M][D], the cost [M] (may be
+        ``d_cost0``) and, each optional, grad [M][D], gn [M][D][D], ceff [P][M], geff [M][P][P]."""
+        check(self.lib.gp_mv_misfit_unc_device(self.h, _dtype_code(dtype), d_cost0, d_coef, d_gram, int(gram_stride), d_var,
+                                               d_deriv, d_dvar, d_cost, d_grad, d_gn, d_ceff, d_geff, int(n_rows), int(n_pcs),
+                                               int(n_inputs)), "gp_mv_misfit_unc_device")
 
     def newton_step_device(self, dtype, d_x, d_grad, d_A, d_lambda, d_step, d_trial, d_status, n_rows, n_inputs,
                            damping="diagonal", d_prior_mean=None, d_prior_prec=None, d_lo=None, d_hi=None):

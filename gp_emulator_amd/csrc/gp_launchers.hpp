@@ -22,6 +22,7 @@ template <typename T> struct RtsSmoothArgs;
 template <typename T> struct ReconArgs;
 template <typename T> struct MisfitArgs;
 template <typename T> struct GramArgs;
+template <typename T> struct MvUncArgs;
 struct TrainArgs;
 
 #pragma GCC visibility push(hidden)      // (the launchers are the library's own)
@@ -51,6 +52,7 @@ template <typename T> hipError_t launch_misfit(const MisfitArgs<T>&, int cus, hi
 template <typename T> hipError_t launch_gauss_newton(const T* deriv, const T* A, T* gn, long long M, int P, int D, int cus, hipStream_t);
 template <typename T> hipError_t launch_gauss_newton_rows(const T* deriv, const T* A, long long a_stride, T* gn, long long M, int P, int D, int cus, hipStream_t);
 template <typename T> hipError_t launch_weight_gram(const GramArgs<T>&, int cus, hipStream_t);
+template <typename T> hipError_t launch_mv_unc(const MvUncArgs<T>&, hipStream_t);
 
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);      // fp64 only
 #pragma GCC visibility pop

@@ -4,6 +4,7 @@
 #include "gp_gram_kernel.hpp"
 #include "gp_launchers.hpp"
 #include "gp_misfit_kernel.hpp"
+#include "gp_mv_unc_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
 
 // out[r][band] = sum_p coef[p][r] basis[p][band] on `stream` (gp_reconstruct_kernel.hpp)
@@ -168,6 +169,25 @@ static int gauss_newton_rows_args(const gp_ctx* ctx, int dtype, const void* d_de
   return GP_OK;
 }
 
+// ---- the emulators' variance in the data term (gp_mv_unc_kernel.hpp) -----------------------------------------------
+static int misfit_unc_args(const gp_ctx* ctx, int dtype, const void* d_cost0, const void* d_coef, const void* d_gram,
+                           int64_t gram_stride, const void* d_var, const void* d_deriv, const void* d_dvar,
+                           const void* d_cost, const void* d_grad, const void* d_gn, int64_t n_rows, int n_pcs,
+                           int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_cost0 || !d_coef || !d_gram || !d_var || !d_cost) return fail(GP_ERR_INVALID, "null device pointer");
+  if ((d_grad || d_gn) && (!d_deriv || !d_dvar)) return fail(GP_ERR_INVALID, "the gradient and gn need d_deriv and d_dvar");
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_rows <= 0 || n_pcs <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_pcs > gpk::kMvUncMax) return fail(GP_ERR_UNSUPPORTED, "the variance term's kernel serves n_pcs <= %d", gpk::kMvUncMax);
+  if (n_inputs > gpk::kMvUncMax) return fail(GP_ERR_UNSUPPORTED, "the variance term's kernel serves n_inputs <= %d", gpk::kMvUncMax);
+  if (gram_stride < 0 || (gram_stride != 0 && gram_stride < (int64_t)n_pcs * n_pcs))
+    return fail(GP_ERR_INVALID, "gram_stride is 0 (one matrix for all rows) or >= n_pcs^2");
+  // (8 rows per workgroup: the grid is numbered in 31 bits)
+  if (n_rows > (int64_t)0x7fffffff * gpk::kMvUncRowsPerWg) return fail(GP_ERR_INVALID, "n_rows too large for one launch");
+  return GP_OK;
+}
+
 // rows of `width` reals, `stride` reals apart on the host, packed on the device
 template <typename T>
 static hipError_t upload_rows(T* dst, const T* src, int64_t stride, int64_t rows, int64_t width, hipStream_t st) {
@@ -321,6 +341,24 @@ int gp_mv_gauss_newton_rows_device(gp_ctx* ctx, int dtype, const void* d_deriv, 
     const hipError_t e = gpk::launch_gauss_newton_rows<T>(as<T>(d_deriv), as<T>(d_gram), gram_stride, as<T>(d_gn), n_rows,
                                                           n_pcs, n_inputs, ctx->compute_units, ctx->stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "gauss-newton kernel launch: %s", hipGetErrorString(e));
+    return GP_OK;
+  });
+}
+
+int gp_mv_misfit_unc_device(gp_ctx* ctx, int dtype, const void* d_cost0, const void* d_coef, const void* d_gram,
+                            int64_t gram_stride, const void* d_var, const void* d_deriv, const void* d_dvar, void* d_cost,
+                            void* d_grad, void* d_gn, void* d_ceff, void* d_geff, int64_t n_rows, int n_pcs, int n_inputs) {
+  if (int rc = misfit_unc_args(ctx, dtype, d_cost0, d_coef, d_gram, gram_stride, d_var, d_deriv, d_dvar, d_cost, d_grad,
+                               d_gn, n_rows, n_pcs, n_inputs))
+    return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) -> int {
+    using T = GP_TAG_TYPE(t);
+    gpk::MvUncArgs<T> a{as<T>(d_cost0), as<T>(d_coef), as<T>(d_gram), gram_stride, as<T>(d_var), as<T>(d_deriv),
+                        as<T>(d_dvar), as<T>(d_cost), as<T>(d_grad), as<T>(d_gn), as<T>(d_ceff), as<T>(d_geff), n_rows,
+                        n_pcs, n_inputs};
+    const hipError_t e = gpk::launch_mv_unc<T>(a, ctx->stream);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "mv variance term kernel launch: %s", hipGetErrorString(e));
     return GP_OK;
   });
 }

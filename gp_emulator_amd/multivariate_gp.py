@@ -286,7 +286,7 @@ class MultivariateEmulator(object):
         return (b64 if weights is None else b64 * np.asarray(weights, dtype=np.float64)) @ b64.T
 
     def misfit(self, y, obs, weights=None, is_gpu=False, precision=np.float64, do_deriv=True, gauss_newton=False,
-               return_coef=False):
+               return_coef=False, emulator_unc=False):
         """``misfit_many`` at ONE state vector ``y`` -- the call an optimiser makes per iteration: the scalar
         cost, then (when asked for) ``grad (N_params,)``, ``gn (N_params, N_params)`` and ``coef (n_pcs,)``."""
         y = np.atleast_2d(y)
@@ -295,14 +295,119 @@ class MultivariateEmulator(object):
         B = self.basis_functions.shape[1]
         if np.shape(obs) != (B,) or (weights is not None and np.shape(weights) != (B,)):
             raise ValueError("obs and weights must be (%d,)" % B)
+        more = dict(emulator_unc=True) if emulator_unc else {}
         out = self.misfit_many(y, obs, weights=weights, is_gpu=is_gpu, precision=precision, do_deriv=do_deriv,
-                               gauss_newton=gauss_newton, return_coef=return_coef)
+                               gauss_newton=gauss_newton, return_coef=return_coef, **more)
         if isinstance(out, tuple):
             return tuple(o[0] for o in out)
         return out[0]
 
+    # ---- the emulators' own variance in the data term -------------------------------------------------
+    @staticmethod
+    def _unc_term_numpy(J0, c, G, v, dmu, dv, do_deriv=True, gauss_newton=True):
+        """The data term with the per-PC emulators' variance from the plain term's ``J0 (M,)`` and ``c = basis (w o r)
+        (M, P)``, ``G = basis diag(w) basis^T`` (P, P) or per row (M, P, P) (the lower triangle is read), the per-PC
+        variances ``v (P, M)`` and the gradients ``dmu``, ``dv`` ``(P, M, D)``, in float64 -- exactly the formulas of
+        ``misfit_many(emulator_unc=True)``.  Returns ``(cost (M,), ceff (M, P), Geff (M, P, P), grad (M, D) or None, gn
+        (M, D, D) or None)``; a row whose ``K`` has a pivot that is not > 0 or not finite is NaN throughout."""
+        from . import _dense_numpy
+        J0, c = np.asarray(J0, dtype=np.float64), np.asarray(c, dtype=np.float64)
+        v, dmu, dv = (np.asarray(a, dtype=np.float64) for a in (v, dmu, dv))
+        M, P = c.shape
+        idx = np.arange(P)
+        Gm = _dense_numpy._mirror_lower(np.array(np.broadcast_to(np.asarray(G, dtype=np.float64), (M, P, P))))
+        with np.errstate(all="ignore"):
+            clamp = v <= 0                                      # (False for a NaN v: it goes through every formula)
+            s = np.sqrt(np.where(clamp, 0.0, v)).T              # (M, P)
+            dvp = np.where(clamp[:, :, None], 0.0, dv)
+            K = s[:, :, None] * Gm * s[:, None, :]
+            K[:, idx, idx] += 1.0
+            Kinv, status = _dense_numpy._cholesky_inverse_numpy(K)      # (K now holds L)
+            Kinv = _dense_numpy._mirror_lower(Kinv)
+            z = s * c
+            a = np.einsum("mij,mj->mi", Kinv, z)
+            cost = J0 - 0.5 * np.sum(z * a, axis=1) + np.sum(np.log(K[:, idx, idx]), axis=1)
+            ceff = c - np.einsum("mij,mj->mi", Gm, s * a)
+            SG = s[:, :, None] * Gm                             # diag(s) G
+            Geff = _dense_numpy._mirror_lower(Gm - np.einsum("mki,mkl,mlj->mij", SG, Kinv, SG))
+            h = 0.5 * (Geff[:, idx, idx] - ceff * ceff)
+            grad = gn = None
+            if do_deriv:
+                grad = np.einsum("mp,pmd->md", ceff, dmu) + np.einsum("mp,pmd->md", h, dvp)
+            if gauss_newton:
+                gn = (MultivariateEmulator._contract_numpy(dmu, Geff)
+                      + MultivariateEmulator._contract_numpy(dvp, 0.5 * Geff * Geff))
+        bad = status != 0
+        for out in (cost, ceff, Geff, grad, gn):
+            if out is not None:
+                out[bad] = np.nan
+        return cost, ceff, Geff, grad, gn
+
+    def _data_term_unc_numpy(self, Y, obs, weights, G, do_deriv=True, gauss_newton=True):
+        """The numpy branch of ``emulator_unc=True``: ``(cost, grad, gn)`` (None where not asked for) in float64 from
+        ``cpu_predict(do_unc=True)`` and ``variance_gradient(is_gpu=False)`` of the per-PC emulators, ``G`` as
+        ``_unc_term_numpy`` takes it."""
+        basis = np.asarray(self.basis_functions, dtype=np.float64)
+        Y = np.asarray(Y, dtype=np.float64)
+        with np.errstate(all="ignore"):
+            mu, v, dmu = (np.stack(a) for a in zip(*[gp.cpu_predict(Y, do_unc=True) for gp in self.emulators]))
+            dv = np.stack([gp.variance_gradient(Y, is_gpu=False)[1] for gp in self.emulators])
+            r = mu.T @ basis - obs
+            wr = r if weights is None else weights * r
+            J0 = 0.5 * np.sum(wr * r, axis=1)
+            c = wr @ basis.T
+        cost, _, _, grad, gn = self._unc_term_numpy(J0, c, G, v, dmu, dv, do_deriv, gauss_newton)
+        return cost, grad, gn
+
+    def _misfit_unc_gpu(self, Y, obs, weights, dt, do_deriv, gauss_newton):
+        """The device path of ``misfit_many(emulator_unc=True)``: ``[cost, grad or None, gn or None]`` in ``dt``."""
+        M, D = Y.shape
+        P, B = self.n_pcs, self.basis_functions.shape[1]
+        isz = dt.itemsize
+        st = self._fresh_gpu_state(dt)
+        ctx, batch, d_basis = st["ctx"], st["batch"], st["d_basis"]
+        with np.errstate(over="ignore"):                   # (a far row may be infinite in float32: it comes out NaN)
+            Yc = np.ascontiguousarray(Y, dtype=dt)
+        per_obs, per_w = obs.ndim == 2, weights is not None and weights.ndim == 2
+        step = max(1, (1 << 30) // (max(B, P * D, D * D, P * P) * isz))        # at most 1 GiB per device array
+        n0 = min(M, step)
+        cost = np.empty(M, dt)
+        grad = np.empty((M, D), dt) if do_deriv else None
+        gn = np.empty((M, D, D), dt) if gauss_newton else None
+        with _lib.Scratch(ctx, dt) as scratch:
+            up, alloc = scratch.up, scratch.alloc
+            d_y = alloc(n0 * D * isz)
+            d_obs = alloc(n0 * B * isz) if per_obs else up(obs)
+            d_w = alloc(n0 * B * isz) if per_w else up(weights)
+            d_G = alloc(n0 * P * P * isz) if per_w else up(self._gauss_newton_matrix(weights))
+            d_mu, d_der, d_var, d_dvar = [alloc(n0 * k * isz) for k in (P, P * D, P, P * D)]
+            d_cost, d_coef = alloc(n0 * isz), alloc(n0 * P * isz)
+            d_grad = alloc(n0 * D * isz) if do_deriv else None
+            d_gn = alloc(n0 * D * D * isz) if gauss_newton else None
+            for r0 in range(0, M, step):
+                n = min(M, r0 + step) - r0
+                ctx.h2d(d_y, Yc[r0:r0 + n])
+                if per_obs:
+                    ctx.h2d(d_obs, np.ascontiguousarray(obs[r0:r0 + n], dtype=dt))
+                if per_w:
+                    ctx.h2d(d_w, np.ascontiguousarray(weights[r0:r0 + n], dtype=dt))
+                batch.predict_mean_grad_device(d_y, d_mu, d_der, n)
+                batch.predict_var_grad_device(d_y, d_var, d_dvar, n)
+                ctx.mv_misfit_device(dt, d_basis, d_mu, d_der, d_obs, B if per_obs else 0, d_w, B if per_w else 0, d_cost,
+                                     d_coef, None, n, P, B, D)
+                if per_w:
+                    ctx.mv_weight_gram_device(dt, d_basis, d_w, B, d_G, n, P, B)
+                ctx.mv_misfit_unc_device(dt, d_cost, d_coef, d_G, P * P if per_w else 0, d_var, d_der, d_dvar, d_cost,
+                                         d_grad, d_gn, n, P, D)
+                cost[r0:r0 + n] = ctx.to_host(d_cost, (n,), dt)
+                if do_deriv:
+                    grad[r0:r0 + n] = ctx.to_host(d_grad, (n, D), dt)
+                if gauss_newton:
+                    gn[r0:r0 + n] = ctx.to_host(d_gn, (n, D, D), dt)
+        return [cost, grad, gn]
+
     def misfit_many(self, Y, obs, weights=None, is_gpu=True, precision=np.float64, do_deriv=True, gauss_newton=False,
-                    return_coef=False):
+                    return_coef=False, emulator_unc=False):
         """Observation misfit ``J(y) = 1/2 sum_b w_b (f_b(y) - obs_b)^2`` of the reconstructed output ``f`` for M
         input rows: ``cost (M,)`` and then, in this order and when asked for, its gradient ``grad (M, N_params)``
         (``do_deriv``) ``= Jac (w * r)`` with ``r = f - obs``, the Gauss-Newton term ``gn (M, N_params, N_params)
@@ -316,10 +421,46 @@ class MultivariateEmulator(object):
         sum_p coef[p] dmu_p/dy_d``.  The numpy branch states exactly that on the per-PC ``gp.predict`` outputs.  On
         the GPU a call is one library call (``gp_mv_misfit_host_checked``) on the device-resident emulator: rows,
         observations and weights up, the mean+gradient predict, the misfit kernel, ``1 + N_params + n_pcs``
-        numbers per row down."""
-        Y, obs, weights = self._misfit_args(Y, obs, weights, gauss_newton)
+        numbers per row down.
+
+        ``emulator_unc=True`` adds the per-PC emulators' own predictive variances ``v_p(y)`` to the data term.  The
+        PCs are shared by all bands, so the emulator's error is correlated across the spectrum with rank ``n_pcs``:
+        ``obs = basis^T mu + eps``, ``eps ~ N(0, C)``, ``C = diag(1 / w) + basis^T diag(vp) basis``, and the term is
+        the exact Gaussian one, ``cost = 1/2 r^T C^-1 r + 1/2 log det(C diag(w))`` (>= 0 up to rounding).  With ``J0``,
+        ``c = basis (w * r)`` and ``G = basis diag(w) basis^T`` of the plain term, ``dmu`` and ``dv`` the gradients of the
+        per-PC means and variances:
+
+            vp = v if v > 0 else 0,  dvp = dv if v > 0 else 0  (a NaN v stays NaN),  s = sqrt(vp)
+            K = I + diag(s) G diag(s) = L L^T,  z = s * c,  a = K^-1 z
+            cost = J0 - 1/2 z^T a + sum_p log L_pp
+            ceff = c - G (s * a),  Geff = G - (G diag(s)) K^-1 (diag(s) G),  h_p = 1/2 (Geff_pp - ceff_p^2)
+            grad[d]  = sum_p ceff_p dmu[p][d] + sum_p h_p dvp[p][d]
+            gn[d][e] = sum_pq dmu[p][d] Geff_pq dmu[q][e] + 1/2 sum_pq dvp[p][d] Geff_pq^2 dvp[q][e]
+
+        ``gn`` is then the Fisher information matrix (positive semi-definite) and is offered with per-row weights too;
+        the returns are ``cost``, then ``grad`` (``do_deriv``), then ``gn`` (``gauss_newton``).  ``return_coef=True``
+        raises ``ValueError``: the full second order would need the Hessian of the variance.  A PC whose variance is
+        not > 0 drops out exactly, and a row where that holds for every PC is the plain term's.  On the GPU, in row
+        blocks on the device-resident emulator: rows, observations and weights up, ``predict_mean_grad_device``,
+        ``predict_var_grad_device``, ``mv_misfit_device`` (``J0`` and ``c``), ``G`` from ``mv_weight_gram_device`` (per-row
+        weights) or the host's matrix uploaded once, ``mv_misfit_unc_device``, results down.  ``is_gpu=False`` is the
+        explicit float64 numpy branch of the same formulas from ``cpu_predict(do_unc=True)`` and
+        ``variance_gradient(is_gpu=False)``; never a fallback.  With ``False`` nothing changes."""
+        if emulator_unc and return_coef:
+            raise ValueError("return_coef=True needs the Hessian of the variance: not available with emulator_unc=True")
+        Y, obs, weights = self._misfit_args(Y, obs, weights, gauss_newton and not emulator_unc)
         M, D = Y.shape
         P, B = self.n_pcs, self.basis_functions.shape[1]
+        if emulator_unc:
+            per_w = weights is not None and weights.ndim == 2
+            if not is_gpu:
+                w64 = None if weights is None else np.asarray(weights, dtype=np.float64)
+                G = self.weight_gram(w64, is_gpu=False) if per_w else self._gauss_newton_matrix(w64)
+                res = self._data_term_unc_numpy(Y, np.asarray(obs, dtype=np.float64), w64, G, do_deriv, gauss_newton)
+            else:
+                res = self._misfit_unc_gpu(Y, obs, weights, np.dtype(precision), do_deriv, gauss_newton)
+            res = [a for a in res if a is not None]
+            return tuple(res) if len(res) > 1 else res[0]
         A = self._gauss_newton_matrix(weights) if gauss_newton else None
         if not is_gpu:
             cost, coef, _, grad, gn = self._data_term_numpy(Y, obs, weights, do_deriv, A)
@@ -473,7 +614,7 @@ class MultivariateEmulator(object):
 
     def retrieve_many(self, Y0, obs, weights=None, prior=None, bounds=None, lam0=1e-2, max_iter=20, down=1.0 / 3.0,
                       up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False, next_prior=None,
-                      return_A=False):
+                      return_A=False, emulator_unc=False):
         """Levenberg-Marquardt retrieval of M state vectors at once on this emulator: minimises, row by row,
 
             F(y) = 1/2 sum_b w_b (f_b(y) - obs_b)^2  (+ 1/2 (y - y0)^T P (y - y0) with ``prior=(y0 (D,), P (D, D))``)
@@ -519,7 +660,15 @@ class MultivariateEmulator(object):
         branch ``_lib.prior_propagate_numpy``.  With ``None`` nothing changes.
 
         ``return_A=True`` appends, as the last element, the loop's final data-term matrix ``A (M, D, D)`` (the
-        Gauss-Newton term whose ``(A + P)^-1`` is ``cov``), as ``retrieve_bands`` does.  With ``False`` nothing changes."""
+        Gauss-Newton term whose ``(A + P)^-1`` is ``cov``), as ``retrieve_bands`` does.  With ``False`` nothing changes.
+
+        ``emulator_unc=True`` minimises the data term of ``misfit_many(emulator_unc=True)`` instead: the per-PC emulators'
+        predictive variances enter the observation's covariance with their rank-``n_pcs`` correlation across the bands, and
+        ``A`` is that term's Fisher matrix, so ``cov``, ``sigma``, ``next_prec`` and the returned ``A`` include the
+        emulators' share of the error.  On the GPU an iteration is then ``predict_mean_grad_device``,
+        ``predict_var_grad_device``, ``mv_misfit_device`` (cost and ``basis (w * r)``, no gradient) and
+        ``mv_misfit_unc_device`` with the matrix formed once before the loop, then the same update and step; the numpy
+        branch hands the loop the numpy form of that term.  With ``False`` nothing changes."""
         from . import _retrieve
         Y0 = np.asarray(Y0)
         if Y0.ndim != 2:
@@ -539,6 +688,8 @@ class MultivariateEmulator(object):
             G = self.weight_gram(w64, is_gpu=False) if per_row else self._gauss_newton_matrix(w64)
 
             def data_term(X):
+                if emulator_unc:
+                    return self._data_term_unc_numpy(X, obs64, w64, G)
                 cost, _, _, grad, gn = self._data_term_numpy(X, obs64, w64, True, G)
                 return cost, grad, gn
 
@@ -561,6 +712,14 @@ class MultivariateEmulator(object):
                 ctx.mv_weight_gram_device(dt, d_basis, d_w, B, d_G, M, P, B)
             else:
                 d_G = scratch.up(self._gauss_newton_matrix(weights))
+            if emulator_unc:
+                d_var, d_dvar, d_coef = scratch.alloc(P * M * isz), scratch.alloc(P * M * D * isz), scratch.alloc(P * M * isz)
+
+            def misfit_unc(d_rows, c, g, a):
+                batch.predict_mean_grad_device(d_rows, d_mu, d_der, M)
+                batch.predict_var_grad_device(d_rows, d_var, d_dvar, M)
+                ctx.mv_misfit_device(dt, d_basis, d_mu, d_der, d_obs, os_, d_w, ws, c, d_coef, None, M, P, B, D)
+                ctx.mv_misfit_unc_device(dt, c, d_coef, d_G, P * P if per_row else 0, d_var, d_der, d_dvar, c, g, a, M, P, D)
 
             def misfit(d_rows, c, g, a):
                 batch.predict_mean_grad_device(d_rows, d_mu, d_der, M)
@@ -570,13 +729,14 @@ class MultivariateEmulator(object):
                 else:
                     ctx.mv_gauss_newton_device(dt, d_der, d_G, a, M, P, D)
             return _retrieve.lm_device(scratch, M, D, Y0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                       misfit, next_prior, return_A)
+                                       misfit_unc if emulator_unc else misfit, next_prior, return_A)
 
     def retrieve_series(self, Y0, obs, weights, prior, noise, smooth=False, **loop_args):
         """A time series of ``retrieve_many`` on this emulator: ``obs`` (T, N_full) or (T, M, N_full) and ``weights``
         the same or None, one retrieval per date, the posterior of a date propagated by the process noise ``noise``
         (D, D) or (M, D, D) into the prior of the next (``_retrieve.retrieve_series``: what it returns, and why
-        ``prior`` is required).  ``loop_args`` are ``retrieve_many``'s other keywords.
+        ``prior`` is required).  ``loop_args`` are ``retrieve_many``'s other keywords, ``emulator_unc=True`` among them:
+        every date's retrieval, and with it the propagated prior and the smoother, then carries the emulators' variance.
 
         ``smooth=True`` appends the Rauch-Tung-Striebel smoothed trajectory ``X_s (T, M, D)``, ``sigma_s (T, M, D)``
         and ``smooth_status (T, M)``, as ``perband.retrieve_bands_series`` does: on the GPU one ``rts_smooth_device``

@@ -340,6 +340,31 @@ int gp_mv_weight_gram_device(gp_ctx* ctx, int dtype, const void* d_basis, const 
                              void* d_gram, int64_t n_rows, int n_pcs, int n_bands);
 int gp_mv_gauss_newton_rows_device(gp_ctx* ctx, int dtype, const void* d_deriv, const void* d_gram, int64_t gram_stride,
                                    void* d_gn, int64_t n_rows, int n_pcs, int n_inputs);
+/* The per-PC emulators' own predictive variance in the data term.  The PCs are shared by all bands, so
+ * the observation model is obs = B^T mu + eps, eps ~ N(0, diag(1 / w) + B^T diag(vp) B): an error of rank n_pcs that is
+ * correlated across the spectrum.  Per row m, from the plain term's cost0 [n_rows] and coef [n_pcs][n_rows]
+ * (gp_mv_misfit_device), the row's matrix G = basis diag(w) basis^T at d_gram + m * gram_stride (elements; >= n_pcs^2,
+ * or 0 = one matrix for all rows; only the LOWER triangle is read), var [n_pcs][n_rows] and dvar
+ * [n_pcs][n_rows][n_inputs] (gp_predict_var_grad_device) and deriv [n_pcs][n_rows][n_inputs]:
+ *   vp = var > 0 ? var : 0,  dvp = var > 0 ? dvar : 0   (selected; a NaN var stays NaN),   s = sqrt(vp)
+ *   K = I + diag(s) G diag(s) = L L^T,   a = K^-1 (s o coef)
+ *   cost = cost0 - 1/2 (s o coef)^T a + sum_p log L_pp
+ *   ceff = coef - G (s o a)                 Geff = G - G diag(s) K^-1 diag(s) G           h_p = 1/2 (Geff_pp - ceff_p^2)
+ *   grad[m][d]    = sum_p ceff_p deriv[p][m][d] + sum_p h_p dvp[p][m][d]
+ *   gn[m][d][e]   = sum_pq deriv[p][m][d] Geff_pq deriv[q][m][e] + 1/2 sum_pq dvp[p][m][d] Geff_pq^2 dvp[q][m][e]
+ * gn is the Fisher information matrix (positive semi-definite), symmetric bit for bit.  A row whose variances are all
+ * <= 0 gives the plain term: cost0, and in double the bits of gp_mv_misfit_device's gradient and of
+ * gp_mv_gauss_newton[_rows]_device's matrix (for a symmetric G).  A failed pivot of K -- a NaN or infinity in the row,
+ * or negative weights -- makes every output of that row quiet NaN.  All arithmetic is in double, one rounding to `dtype`
+ * per output; no atomics; a row's results depend on its own data only and agree bit for bit wherever the row sits and
+ * across calls.  d_grad, d_gn (then d_deriv and d_dvar may be NULL too), d_ceff [n_pcs][n_rows] and d_geff
+ * [n_rows][n_pcs][n_pcs] are optional.  d_cost may be d_cost0.  Device pointers of `dtype`, asynchronous on the
+ * context's stream; every argument is checked before the device is touched: GP_ERR_INVALID for a null required
+ * pointer, n_rows <= 0 or a stride that is neither 0 nor >= n_pcs^2, GP_ERR_UNSUPPORTED for n_pcs > 16 or
+ * n_inputs > 16. */
+int gp_mv_misfit_unc_device(gp_ctx* ctx, int dtype, const void* d_cost0, const void* d_coef, const void* d_gram,
+                            int64_t gram_stride, const void* d_var, const void* d_deriv, const void* d_dvar, void* d_cost,
+                            void* d_grad, void* d_gn, void* d_ceff, void* d_geff, int64_t n_rows, int n_pcs, int n_inputs);
 /* The whole data term in one call, the counterpart of gp_mv_predict_host[_checked]: `model` is the batch of the
  * n_pcs per-PC emulators, d_basis their basis on the device, y / obs / weights host rows of the model's dtype with
  * row strides in elements (y_stride >= n_inputs; obs_stride and weights_stride 0 or >= n_bands; weights may be

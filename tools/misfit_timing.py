@@ -320,9 +320,11 @@ def unit_registers(unit):
             continue
         if m.group(1) == "Function Name":
             flush()
-            t = re.search(r"(misfit_kernel|weight_gram_kernel)I([fd])Li(\d)E|(gauss_newton_kernel)I([fd])Lb([01])E", m.group(2))
+            t = re.search(r"(misfit_kernel|weight_gram_kernel)I([fd])Li(\d)E|(gauss_newton_kernel)I([fd])Lb([01])E|"
+                          r"(mv_unc_kernel)I([fd])E", m.group(2))
             real = {"f": "float", "d": "double"}
             name = ("%s<%s,%s>" % (t.group(1), real[t.group(2)], t.group(3)) if t.group(1)
+                    else "%s<%s>" % (t.group(7), real[t.group(8)]) if t.group(7)
                     else "%s<%s,%s>" % (t.group(4), real[t.group(5)], "per_row" if t.group(6) == "1" else "shared"))
             row = {}
         else:
