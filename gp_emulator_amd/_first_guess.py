@@ -1,0 +1,127 @@
+"""The first guess of a retrieval and the multi-start wrappers: what ``perband.first_guess_bands`` and
+``MultivariateEmulator.first_guess_many`` share.  The callers build the table (the emulators' means at the candidate
+states, on the device or in numpy) and lay out ``obs`` and ``weights``; the prior's offset, the search call, the gather
+of the starting rows and the selection among several starts are stated here once."""
+import numpy as np
+
+from . import _lib, _retrieve
+
+
+def shared_prior(prior, D):
+    """``prior`` as float64 ``(x0 (D,), P (D, D))`` or None.  A per-row prior is a ``ValueError``: the search ranks by
+    one offset per candidate."""
+    if prior is None:
+        return None
+    x0, P = np.asarray(prior[0], dtype=np.float64), np.asarray(prior[1], dtype=np.float64)
+    if x0.shape != (D,) or P.shape != (D, D):
+        raise ValueError("the first guess takes a prior shared by the rows, x0 (%d,) and P (%d, %d): a per-row prior "
+                         "is not an offset per candidate" % (D, D, D))
+    return x0, P
+
+
+def prior_offset(candidates, prior):
+    """``a[l] = 1/2 (c_l - x0)^T P (c_l - x0)`` in float64 on the host (L D^2 operations), summed as the loop sums its
+    prior term; None without a prior."""
+    if prior is None:
+        return None
+    return _retrieve._prior_term(np.asarray(candidates, dtype=np.float64), prior)
+
+
+def check_candidates(candidates, D):
+    c = np.asarray(candidates, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != D:
+        raise ValueError("candidates must be (n_candidates, %d), got %s" % (D, c.shape))
+    return c
+
+
+def gather_starts(candidates, index, n_best):
+    """``candidates[index]``, NaN where ``index`` is -1: (M, D) for ``n_best`` 1, else (M, n_best, D)."""
+    X0 = candidates[np.maximum(index, 0)]
+    X0[index < 0] = np.nan
+    return X0[:, 0] if n_best == 1 else X0
+
+
+class DeviceTable(object):
+    """A table of candidate means resident on the device: what ``candidate_table`` of either emulator type hands to
+    ``table=``.  ``d_table`` holds element (term k, candidate l) at ``k * strides[0] + l * strides[1]``; ``close()``
+    (or leaving the ``with`` block) frees it."""
+
+    def __init__(self, ctx, dtype, d_table, strides, n_terms, candidates, owner):
+        self.ctx, self.dtype, self.d_table, self.strides = ctx, np.dtype(dtype), d_table, strides
+        self.n_terms, self.candidates, self.owner = n_terms, candidates, owner
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.d_table is not None:
+            self.ctx.free(self.d_table)
+            self.d_table = None
+
+    def check(self, owner, dtype, n_terms):
+        if self.d_table is None:
+            raise ValueError("the candidate table has been closed")
+        if self.owner is not owner or self.dtype != np.dtype(dtype) or self.n_terms != n_terms:
+            raise ValueError("table= was built for other emulators or another precision")
+
+
+def search_table(tb, obs, obs_strides, weights, w_strides, offset, M, n_best):
+    """The search of ``M`` rows against the device table ``tb``: ``obs`` and ``weights`` (host arrays laid out as
+    their strides say) go up once, only ``index`` and ``cost`` come back."""
+    ctx, dt = tb.ctx, tb.dtype
+    with _lib.Scratch(ctx, dt) as scratch:
+        d_o, d_w, d_a = scratch.up(obs), scratch.up(weights), scratch.up(offset)
+        d_i, d_c = scratch.alloc(M * n_best * 4), scratch.alloc(M * n_best * dt.itemsize)
+        ctx.lut_search_device(dt, tb.d_table, tb.strides, d_a, d_o, obs_strides, d_w, w_strides, d_i, d_c, M,
+                              tb.candidates.shape[0], tb.n_terms, n_best)
+        return _lib._download(ctx, d_i, (M, n_best), np.int32), _lib._download(ctx, d_c, (M, n_best), dt)
+
+
+def check_n_best(n_best, L):
+    n_best = int(n_best)
+    if not 1 <= n_best <= 8 or n_best > L:
+        raise ValueError("n_best / n_starts must be in 1..8 and at most the %d candidates" % L)
+    return n_best
+
+
+def select_starts(flat, M, n_starts, prior):
+    """Among the ``n_starts`` retrievals of every pixel (rows m * n_starts + s of every array of ``flat``, the tuple a
+    retrieval returns) the one of lowest ``F = cost + prior term``: ties go to the lower start, a non-finite F loses.
+    Returns ``(results, start (M,) int32)``, every array of ``results`` gathered from the chosen starts."""
+    X, cost = np.asarray(flat[0], dtype=np.float64), np.asarray(flat[1], dtype=np.float64)
+    F = cost + _retrieve._prior_term(X, prior)
+    F = np.where(np.isfinite(F), F, np.inf).reshape(M, n_starts)
+    start = np.argmin(F, axis=1).astype(np.int32)            # (the first of equal minima)
+    pick = np.arange(M) * n_starts + start
+    return tuple(np.asarray(a)[pick] for a in flat), start
+
+
+def multistart(first_guess, retrieve, obs_axis, obs, weights, n_starts, D, loop_args):
+    """The multi-start retrieval both emulator types offer.  ``first_guess(prior, n_best) -> (X0, cost0, index)``
+    ranks the candidates with the loop's shared prior; the ``M n_starts`` starting rows, clipped to ``bounds``, go
+    through ONE call of ``retrieve(X0, obs, weights, **loop_args)`` with the row-shaped ``obs``, ``weights`` and
+    ``next_prior`` repeated (``obs_axis``: the axis of ``obs`` / ``weights`` the rows lie along when they are 2-D);
+    ``select_starts`` keeps one start per pixel.  Returns ``(results, start (M,) int32, cost0 (M, n_starts))``."""
+    if loop_args.get("emulator_unc"):
+        raise ValueError("emulator_unc is not offered with multi-start: the first guess ranks by the plain data term")
+    if loop_args.get("step_fn") is not None:
+        raise ValueError("step_fn is not offered with multi-start")
+    prior = shared_prior(loop_args.get("prior"), D)
+    X0, cost0, index = first_guess(prior, n_starts)
+    M = index.shape[0]
+    X0 = X0.reshape(M * n_starts, D)
+    bounds = loop_args.get("bounds")
+    if bounds is not None:
+        X0 = np.clip(X0, np.asarray(bounds[0], dtype=np.float64).reshape(D), np.asarray(bounds[1], dtype=np.float64).reshape(D))
+    obs, weights = np.asarray(obs), None if weights is None else np.asarray(weights)
+    obs_r = np.repeat(obs, n_starts, axis=obs_axis) if obs.ndim == 2 else obs
+    w_r = np.repeat(weights, n_starts, axis=obs_axis) if weights is not None and weights.ndim == 2 else weights
+    args = dict(loop_args)
+    if args.get("next_prior") is not None and np.ndim(args["next_prior"]) == 3:
+        args["next_prior"] = np.repeat(np.asarray(args["next_prior"]), n_starts, axis=0)
+    flat = retrieve(X0, obs_r, w_r, **args)
+    results, start = select_starts(flat, M, n_starts, prior)
+    return results, start, cost0.reshape(M, n_starts)

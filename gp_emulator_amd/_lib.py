@@ -14,6 +14,7 @@ import numpy as np
 
 from ._dense_numpy import (DAMPINGS, newton_step_numpy, posterior_cov_numpy, prec_rows, prior_propagate_numpy,  # noqa: F401
                            prior_rows, row_strides, rts_smooth_numpy, _cholesky_inverse_numpy, _mirror_lower)
+from ._lut_numpy import lut_search_numpy  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_PREDICT_LIB lets tools/ab_bench.py time differently-built variants of the library on
@@ -85,6 +86,9 @@ SIGNATURES = {
     "gp_posterior_cov_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_i64, c_int, c_i64]),
     "gp_prior_propagate_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int]),
     "gp_rts_smooth_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 9 + [c_i64, c_int]),
+    "gp_lut_search_device": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
+                                     c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int]),
+    "gp_lut_search_geometry": (c_int, [ctypes.POINTER(c_int)] * 3),
     "gp_hessian_f64": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_hessian_f32": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_reconstruct_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
@@ -683,6 +687,53 @@ class Context:
             return (_download(self, d_step, (M, D), dt), _download(self, d_trial, (M, D), dt),
                     _download(self, d_status, (M,), np.int32))
 
+    def lut_search_device(self, dtype, d_table, table_strides, d_offset, d_obs, obs_strides, d_weights, w_strides, d_index,
+                          d_cost, n_rows, n_candidates, n_terms, n_best, n_slices=0):
+        """Asynchronous look-up-table search on the device (``gp_lut_search_device``): per row the ``n_best`` candidates
+        of lowest ``J[m, l] = a[l] + 1/2 sum_k w[m, k] (S[l, k] - o[m, k])^2`` into ``d_index`` (int32) and ``d_cost``,
+        both ``[n_rows][n_best]``, ascending by (cost, index); -1 / NaN where no candidate has a comparable J.
+        Device pointers of ``dtype``; ``d_offset`` and ``d_weights`` may be None.  The strides are element pairs
+        ``(per term, per candidate or row)``: ``(L, 1)`` / ``(M, 1)`` for term-major arrays, ``(1, K)`` for row-major
+        ones, ``(1, 0)`` for one vector shared by the rows.  ``n_slices`` 0 leaves the slicing of the candidate range
+        to the launch plan; the result does not depend on it."""
+        check(self.lib.gp_lut_search_device(self.h, _dtype_code(dtype), d_table, int(table_strides[0]), int(table_strides[1]),
+                                            d_offset, d_obs, int(obs_strides[0]), int(obs_strides[1]), d_weights,
+                                            int(w_strides[0]), int(w_strides[1]), d_index, d_cost, int(n_rows),
+                                            int(n_candidates), int(n_terms), int(n_best), int(n_slices)),
+              "gp_lut_search_device")
+
+    def lut_search(self, table, obs, weights=None, offset=None, n_best=1, precision=None, is_gpu=True, n_slices=0):
+        """``(index (M, n_best) int32, cost (M, n_best))`` of the look-up-table search for the host arrays ``table``
+        (L, K), ``obs`` (K,) or (M, K), ``weights`` None, (K,) or (M, K) and ``offset`` None or (L,): uploads, launches
+        ``gp_lut_search_device``, downloads.  ``precision`` is the device dtype (default: float32 when ``table`` is
+        float32, else float64).  ``is_gpu=False`` is the explicit numpy branch (``lut_search_numpy``: the same search
+        in float64); never a fallback."""
+        if not is_gpu:
+            return lut_search_numpy(table, obs, weights, offset, n_best)
+        table = np.asarray(table)
+        if table.ndim != 2:
+            raise ValueError("table must be (n_candidates, n_terms)")
+        dt = _device_dtype(precision, table)
+        L, K = table.shape
+        obs = np.asarray(obs)
+        weights = None if weights is None else np.asarray(weights)
+        for name, a in (("obs", obs), ("weights", weights)):
+            if a is not None and (a.ndim not in (1, 2) or a.shape[-1] != K):
+                raise ValueError("%s must be (%d,) or (n_rows, %d), got %s" % (name, K, K, a.shape))
+        rows = [a.shape[0] for a in (obs, weights) if a is not None and a.ndim == 2]
+        M = rows[0] if rows else 1
+        if any(r != M for r in rows):
+            raise ValueError("obs and weights disagree on the number of rows")
+
+        def strides(a):
+            return (1, K) if a.ndim == 2 else (1, 0)
+        with Scratch(self, dt) as scratch:
+            d_t, d_o, d_w, d_a = scratch.up(table), scratch.up(obs), scratch.up(weights), scratch.up(offset)
+            d_i, d_c = scratch.alloc(M * n_best * 4), scratch.alloc(M * n_best * dt.itemsize)
+            self.lut_search_device(dt, d_t, (1, K), d_a, d_o, strides(obs), d_w, strides(weights) if weights is not None else (0, 0),
+                                   d_i, d_c, M, L, K, n_best, n_slices)
+            return _download(self, d_i, (M, n_best), np.int32), _download(self, d_c, (M, n_best), dt)
+
     def likelihood_batch(self, thetas, inputs, targets, want_inverse=False):
         """cost (E,), grad (E, D+2) [and invQ (E, N, N), invQt (E, N)] of the training
         objective for E hyper-parameter sets; targets (N,) shared or (E, N)."""
@@ -1108,24 +1159,39 @@ class BatchModel(Model):
 
 
 GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_VAR_GRAD = 0, 1, 2, 3, 4, 5, 6
+GP_OP_LUT_SEARCH = 7
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
                 6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
-                10: "misfit", 11: "mv_gram", 12: "var_grad"}
+                10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
-             "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM, "var_grad": GP_OP_VAR_GRAD}
+             "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM, "var_grad": GP_OP_VAR_GRAD,
+             "lut_search": GP_OP_LUT_SEARCH}
+
+
+def lut_search_geometry():
+    """``dict(rows_per_item, candidate_tile, term_chunk)`` of ``lut_search_kernel``: the rows of a work item, the
+    candidates of a register tile and the terms of a staged chunk (``gp_lut_search_geometry``; no GPU needed)."""
+    r, t, c = c_int(0), c_int(0), c_int(0)
+    check(load().gp_lut_search_geometry(ctypes.byref(r), ctypes.byref(t), ctypes.byref(c)), "gp_lut_search_geometry")
+    return dict(rows_per_item=r.value, candidate_tile=t.value, term_chunk=c.value)
 
 
 def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_pcs=0, n_bands=0,
-                compute_units=256, aligned16=True):
+                compute_units=256, aligned16=True, n_terms=0, n_candidates=0):
     """How the device call ``op`` ("predict", "mean_grad", "var_grad", "hessian", "reconstruct", "misfit", "mv_gram") on ``n_rows`` rows would be
     launched on a device of ``compute_units`` (``gp_launch_plan``: host arithmetic shared with the launch path, no
     GPU needed).  Returns dict(kernel, rows_per_item, items, workgroups, rest_items, rest_workgroups): the
     kernel family and instance (a ``PLAN_KERNELS`` name), the rows of one work item, and the work items and
     workgroups of the launch (``rest_*``: the windowed Hessian's second launch for the rows behind the last whole
     64-row group).  ``items > workgroups``: workgroups run several items.  ``aligned16``: a Hessian call's row and
-    output pointers are 16-byte aligned.  reconstruct, misfit and mv_gram take ``n_pcs`` and ``n_bands``."""
+    output pointers are 16-byte aligned.  reconstruct, misfit and mv_gram take ``n_pcs`` and ``n_bands``.
+    "lut_search" takes ``n_terms`` and ``n_candidates``: an item is ``rows_per_item`` rows against one slice of the
+    candidates, and the dict also holds ``slices`` (the slices chosen: items = row tiles x slices), ``candidate_tile``
+    and ``term_chunk`` (``lut_search_geometry``)."""
     code = _PLAN_OPS[op]
-    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM)
+    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_LUT_SEARCH)
+    if code == GP_OP_LUT_SEARCH:
+        n_pcs, n_bands = n_terms, n_candidates
     k, wg, rwg, rpi = c_int(0), c_int(0), c_int(0), c_int(0)
     items, ritems = c_i64(0), c_i64(0)
     check(load().gp_launch_plan(
@@ -1133,6 +1199,11 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
         int(n_emulators), int(n_rows), int(n_bands if recon else 0), int(compute_units), int(bool(aligned16)),
         ctypes.byref(k), ctypes.byref(items), ctypes.byref(wg), ctypes.byref(ritems), ctypes.byref(rwg),
         ctypes.byref(rpi)), "gp_launch_plan")
+    if code == GP_OP_LUT_SEARCH:         # (rest_items carries the slices: there is no second launch of the search)
+        geo = lut_search_geometry()
+        return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
+                    rest_items=0, rest_workgroups=0, slices=ritems.value, candidate_tile=geo["candidate_tile"],
+                    term_chunk=geo["term_chunk"])
     return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
                 rest_items=ritems.value, rest_workgroups=rwg.value)
 

@@ -6,6 +6,7 @@
 #include "gp_hessian_win_kernel.hpp"
 #include "gp_launch_plan.hpp"
 #include "gp_launchers.hpp"
+#include "gp_lut_search_kernel.hpp"
 #include "gp_misfit_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
 
@@ -317,6 +318,15 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     k = GP_PLAN_MV_GRAM;
     rpi = gpk::mkRows;
     g = gpk::plan_misfit(n_rows, gpk::mkRows, gpk::gram_cap(compute_units, n_inputs, f64 ? 8 : 4));
+  } else if (op == GP_OP_LUT_SEARCH) {
+    // (n_inputs = n_terms here; aux = n_candidates; rest_items reports the slices)
+    if (n_inputs <= 0 || aux <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    const gpk::LutPlan lp = gpk::plan_lut_search(n_rows, aux, gpk::lkRows, gpk::lkTile,
+                                                 gpk::lut_cap(compute_units, gpk::lkWGPerCU), 0);
+    k = GP_PLAN_LUT_SEARCH;
+    rpi = gpk::lkRows;
+    g = lp.grid;
+    rest.items = lp.n_slices;
   } else if (op == GP_OP_VAR_GRAD) {
     int kd, knb;
     int rc = pick_kernel(n_train, n_inputs, &kd, &knb);

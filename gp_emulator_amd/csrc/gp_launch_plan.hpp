@@ -104,4 +104,38 @@ inline long long gram_cap(int compute_units, int n_pcs, int elem_bytes) {
   return (long long)compute_units * gram_wgs_per_cu(gram_blocks(n_pcs), elem_bytes);
 }
 
+// lut_search_kernel: items = row tiles x slices of the candidate range (whole candidate tiles).  Row tiles alone
+// fill the chip evenly only when they are several rounds of it: fewer are multiplied by slices, as many as fill one
+// round (down to one candidate tile per slice) or, where the candidates allow, four rounds with at least four tiles
+// per slice -- a single round of fewer items than the cap leaves some compute units one workgroup and others two.
+// forced > 0: that many slices (tests), cut the same way.  Slices that would stay empty are not planned: n_slices is
+// what the kernel is launched with.
+struct LutPlan {
+  long long row_tiles, cand_tiles, tiles_per_slice;
+  int n_slices;
+  GridPlan grid;
+};
+inline LutPlan plan_lut_search(long long n_rows, long long n_candidates, int rows_per_item, int cand_tile, long long cap,
+                               int forced) {
+  LutPlan p;
+  p.row_tiles = (n_rows + rows_per_item - 1) / rows_per_item;
+  p.cand_tiles = (n_candidates + cand_tile - 1) / cand_tile;
+  long long s = forced;
+  if (forced <= 0) {
+    const long long one = (cap + p.row_tiles - 1) / p.row_tiles, four = (4 * cap + p.row_tiles - 1) / p.row_tiles;
+    const long long s1 = one < p.cand_tiles ? one : p.cand_tiles;
+    const long long s4 = four < p.cand_tiles / 4 ? four : p.cand_tiles / 4;
+    s = s1 > s4 ? s1 : s4;
+  }
+  if (s > p.cand_tiles) s = p.cand_tiles;
+  if (s < 1) s = 1;
+  if (s > 0x7fff) s = 0x7fff;
+  p.tiles_per_slice = (p.cand_tiles + s - 1) / s;
+  p.n_slices = (int)((p.cand_tiles + p.tiles_per_slice - 1) / p.tiles_per_slice);
+  p.grid.items = p.row_tiles * p.n_slices;
+  p.grid.workgroups = (int)(p.grid.items < cap ? p.grid.items : cap);
+  return p;
+}
+inline long long lut_cap(int compute_units, int wgs_per_cu) { return (long long)compute_units * wgs_per_cu; }
+
 }  // namespace gpk

@@ -23,6 +23,7 @@ template <typename T> struct ReconArgs;
 template <typename T> struct MisfitArgs;
 template <typename T> struct GramArgs;
 template <typename T> struct MvUncArgs;
+template <typename T> struct LutArgs;
 struct TrainArgs;
 
 #pragma GCC visibility push(hidden)      // (the launchers are the library's own)
@@ -53,6 +54,8 @@ template <typename T> hipError_t launch_gauss_newton(const T* deriv, const T* A,
 template <typename T> hipError_t launch_gauss_newton_rows(const T* deriv, const T* A, long long a_stride, T* gn, long long M, int P, int D, int cus, hipStream_t);
 template <typename T> hipError_t launch_weight_gram(const GramArgs<T>&, int cus, hipStream_t);
 template <typename T> hipError_t launch_mv_unc(const MvUncArgs<T>&, hipStream_t);
+// lut_search_kernel on `grid` workgroups, then lut_merge_kernel when the call is sliced
+template <typename T> hipError_t launch_lut_search(const LutArgs<T>&, int grid, hipStream_t);
 
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);      // fp64 only
 #pragma GCC visibility pop

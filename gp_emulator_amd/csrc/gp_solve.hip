@@ -1,8 +1,11 @@
 // The small dense solves on device buffers: damped Newton step, LM update, posterior covariance, prior propagation and
-// the smoother's backward step.  Device arrays in, device arrays out, no model.
+// the smoother's backward step; and the look-up-table search that starts a retrieval.  Device arrays in, device arrays
+// out, no model.
 #include "gp_host.hpp"
 
+#include "gp_launch_plan.hpp"
 #include "gp_launchers.hpp"
+#include "gp_lut_search_kernel.hpp"
 #include "gp_newton_kernel.hpp"
 #include "gp_posterior_cov_kernel.hpp"
 #include "gp_prior_propagate_kernel.hpp"
@@ -230,6 +233,56 @@ int gp_rts_smooth_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_
     a.rows = n_rows;
     a.d = n_inputs;
     return launched(gpk::launch_rts_smooth<T>(a, ctx->stream), "smoother");
+  });
+}
+
+int gp_lut_search_geometry(int* rows_per_item, int* candidate_tile, int* term_chunk) {
+  if (rows_per_item) *rows_per_item = gpk::lkRows;
+  if (candidate_tile) *candidate_tile = gpk::lkTile;
+  if (term_chunk) *term_chunk = gpk::lkChunk;
+  return GP_OK;
+}
+
+int gp_lut_search_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t table_kstride, int64_t table_lstride,
+                         const void* d_offset, const void* d_obs, int64_t obs_kstride, int64_t obs_mstride,
+                         const void* d_weights, int64_t w_kstride, int64_t w_mstride, int32_t* d_index, void* d_cost,
+                         int64_t n_rows, int64_t n_candidates, int n_terms, int n_best, int n_slices) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (!d_table || !d_obs || !d_index || !d_cost) return fail(GP_ERR_INVALID, "null device pointer");
+  if (n_rows <= 0 || n_candidates <= 0 || n_terms <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_candidates > 0x7fffffffLL) return fail(GP_ERR_INVALID, "n_candidates too large for an int32 index");
+  if (n_best < 1 || n_best > gpk::lkMaxBest) return fail(GP_ERR_INVALID, "n_best %d is not in 1..%d", n_best, gpk::lkMaxBest);
+  if (n_best > n_candidates) return fail(GP_ERR_INVALID, "n_best %d exceeds the %lld candidates", n_best, (long long)n_candidates);
+  if (n_slices < 0) return fail(GP_ERR_INVALID, "negative n_slices");
+  if (table_kstride < 0 || table_lstride < 0 || obs_kstride < 0 || obs_mstride < 0 || w_kstride < 0 || w_mstride < 0)
+    return fail(GP_ERR_INVALID, "negative stride");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const gpk::LutPlan plan = gpk::plan_lut_search(n_rows, n_candidates, gpk::lkRows, gpk::lkTile,
+                                                 gpk::lut_cap(ctx->compute_units, gpk::lkWGPerCU), n_slices);
+  const int nb = gpk::lut_list_size(n_best);
+  const size_t isz = dtype == GP_F64 ? 8 : 4;
+  const size_t n_part = plan.n_slices > 1 ? (size_t)plan.n_slices * (size_t)n_rows * nb : 0;
+  if (n_part)
+    if (int rc = ensure_scratch(ctx, n_part * (isz + 4))) return rc;
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::LutArgs<T> a;
+    a.table = as<T>(d_table);
+    a.offset = as<T>(d_offset);
+    a.obs = as<T>(d_obs);
+    a.weights = as<T>(d_weights);
+    a.index = d_index;
+    a.cost = as<T>(d_cost);
+    a.part_cost = n_part ? (T*)ctx->scratch : nullptr;          // costs first: they carry the alignment
+    a.part_index = n_part ? (int*)((T*)ctx->scratch + n_part) : nullptr;
+    a.t_ks = table_kstride, a.t_ls = table_lstride;
+    a.o_ks = obs_kstride, a.o_ms = obs_mstride;
+    a.w_ks = w_kstride, a.w_ms = w_mstride;
+    a.M = n_rows, a.L = n_candidates;
+    a.tiles_per_slice = plan.tiles_per_slice;
+    a.K = n_terms, a.n_best = n_best, a.n_slices = plan.n_slices;
+    return launched(gpk::launch_lut_search<T>(a, plan.grid.workgroups, ctx->stream), "lut search");
   });
 }
 

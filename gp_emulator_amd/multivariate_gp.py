@@ -731,6 +731,92 @@ class MultivariateEmulator(object):
             return _retrieve.lm_device(scratch, M, D, Y0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
                                        misfit_unc if emulator_unc else misfit, next_prior, return_A)
 
+    # ---- the first guess: look-up-table search in band space --------------------------------------
+    def candidate_table(self, candidates, precision=np.float64):
+        """The device table of ``first_guess_many``: the spectra of the ``candidates`` (L, D), row-major
+        ``(L, N_full)``, from ``predict_mean_grad_device`` and ``gp_reconstruct_device`` on the resident emulator; it
+        never crosses PCIe.  A context manager (``_first_guess.DeviceTable``): pass it as ``table=`` so that repeated
+        calls (dates, tiles) do not compute the spectra again; leaving the block frees it."""
+        from . import _first_guess
+        dt = _lib.precision_dtype(precision)
+        cand = _first_guess.check_candidates(candidates, self.emulators[0].inputs.shape[1])
+        st = self._fresh_gpu_state(dt)
+        ctx, batch, d_basis = st["ctx"], st["batch"], st["d_basis"]
+        P, B, (L, D) = self.n_pcs, self.basis_functions.shape[1], cand.shape
+        d_table = ctx.malloc(L * B * dt.itemsize)
+        try:
+            with _lib.Scratch(ctx, dt) as scratch:
+                d_mu = scratch.alloc(P * L * dt.itemsize)
+                batch.predict_mean_grad_device(scratch.up(cand), d_mu, scratch.alloc(P * L * D * dt.itemsize), L)
+                ctx.reconstruct_device(dt, d_basis, d_mu, d_table, L, P, B)
+                ctx.synchronize()
+        except Exception:
+            ctx.free(d_table)
+            raise
+        return _first_guess.DeviceTable(ctx, dt, d_table, (1, B), B, cand, self)
+
+    def first_guess_many(self, candidates, obs, weights=None, prior=None, n_best=1, is_gpu=True, precision=np.float64,
+                         table=None):
+        """The starting states of ``retrieve_many`` by look-up-table search in band space: among the ``candidates``
+        (L, D) per row the ``n_best`` (1..8) of lowest
+
+            J[m, l] = a[l] + 1/2 sum_b w[m, b] (f_b(c_l) - obs[m, b])^2,     a[l] = 1/2 (c_l - y0)^T P (c_l - y0)
+
+        with ``obs`` ``(N_full,)`` or ``(M, N_full)``, ``weights`` None, ``(N_full,)`` or ``(M, N_full)`` (M is 1 when
+        neither has rows) and ``prior=(y0 (D,), P (D, D))`` shared by the rows (a per-row prior is a ``ValueError``).
+        Returns ``(Y0, cost0, index)`` exactly as ``perband.first_guess_bands`` does, with its tie, zero-weight and NaN
+        rules.  On the GPU the table is the candidates' spectra on the device (``candidate_table``; ``table=`` reuses
+        one, ``candidates`` may then be None), ``obs`` and ``weights`` go up once and only ``index`` and ``cost`` come
+        back.  ``is_gpu=False`` is the explicit numpy branch (``predict_many(is_gpu=False)`` and
+        ``_lib.lut_search_numpy``); never a fallback."""
+        from . import _first_guess
+        D, B = self.emulators[0].inputs.shape[1], self.basis_functions.shape[1]
+        cand = table.candidates if table is not None and candidates is None else _first_guess.check_candidates(candidates, D)
+        n_best = _first_guess.check_n_best(n_best, cand.shape[0])
+        obs = np.asarray(obs, dtype=np.float64)
+        weights = None if weights is None else np.asarray(weights, dtype=np.float64)
+        for name, a in (("obs", obs), ("weights", weights)):
+            if a is not None and (a.ndim not in (1, 2) or a.shape[-1] != B):
+                raise ValueError("%s must be (%d,) or (n_rows, %d), got %s" % (name, B, B, a.shape))
+        rows = [a.shape[0] for a in (obs, weights) if a is not None and a.ndim == 2]
+        M = rows[0] if rows else 1
+        if any(r != M for r in rows):
+            raise ValueError("obs and weights disagree on the number of rows")
+        prior = _first_guess.shared_prior(prior, D)
+        offset = _first_guess.prior_offset(cand, prior)
+        if not is_gpu:
+            index, cost = _lib.lut_search_numpy(self.predict_many(cand, is_gpu=False), obs, weights, offset, n_best)
+        else:
+            tb = table if table is not None else self.candidate_table(cand, precision)
+            try:
+                tb.check(self, precision, B)
+                if tb.candidates.shape != cand.shape or (tb.candidates is not cand and not np.array_equal(tb.candidates, cand)):
+                    raise ValueError("table= was built for other candidates")
+
+                def strides(a):
+                    return (1, B) if a.ndim == 2 else (1, 0)
+                index, cost = _first_guess.search_table(tb, obs, strides(obs), weights,
+                                                        strides(weights) if weights is not None else (0, 0), offset, M, n_best)
+            finally:
+                if table is None:
+                    tb.close()
+        return _first_guess.gather_starts(cand, index, n_best), cost, index
+
+    def retrieve_many_multistart(self, candidates, obs, weights=None, n_starts=4, table=None, **loop_args):
+        """``retrieve_many`` from several starts per pixel, as ``perband.retrieve_bands_multistart``: ``first_guess_many``
+        with ``n_best = n_starts`` ranked with the loop's shared ``prior``, the starts clipped to ``bounds``, ONE
+        ``retrieve_many`` call on the ``M n_starts`` rows (row-shaped ``obs``, ``weights`` and ``next_prior`` repeated),
+        per pixel the start of lowest ``F = cost + prior term`` kept (ties to the lower start, a non-finite F loses).
+        Returns ``(results, start (M,) int32, cost0 (M, n_starts))``, ``results`` exactly the tuple ``retrieve_many``
+        returns for M rows.  ``emulator_unc`` and per-row priors are not offered."""
+        from . import _first_guess
+        D = self.emulators[0].inputs.shape[1]
+        fg = {k: loop_args[k] for k in ("is_gpu", "precision") if k in loop_args}
+
+        def first_guess(prior, n_best):
+            return self.first_guess_many(candidates, obs, weights, prior, n_best, table=table, **fg)
+        return _first_guess.multistart(first_guess, self.retrieve_many, 0, obs, weights, n_starts, D, loop_args)
+
     def retrieve_series(self, Y0, obs, weights, prior, noise, smooth=False, **loop_args):
         """A time series of ``retrieve_many`` on this emulator: ``obs`` (T, N_full) or (T, M, N_full) and ``weights``
         the same or None, one retrieval per date, the posterior of a date propagated by the process noise ``noise``

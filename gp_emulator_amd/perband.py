@@ -8,7 +8,7 @@ of the fused kernel (BASELINE config 3: 2101 bands x N_train=250 x D=11, shared 
 """
 import numpy as np
 
-from . import _lib, _retrieve, multi_gpu
+from . import _first_guess, _lib, _retrieve, multi_gpu
 from ._retrieve import LAMBDA_MAX, LAMBDA_MIN, _lm_update_numpy, _prior_term     # noqa: F401  (their names here)
 from .perband_train import (learn_bands, _driver_probe, _lockstep_driver, _lockstep_processes,     # noqa: F401  (training
                             _Population, _probe_setulb, _worker_main)                              # many bands at once)
@@ -428,6 +428,108 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
                                 d_hess=a if second_order == "full" else None)
         return _retrieve.lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
                                    misfit, next_prior, return_A)
+
+
+def candidate_table(gps, candidates=None, precision=np.float64, device=None):
+    """The device table of ``first_guess_bands``: the E emulators' means at the ``candidates`` (L, D) -- None: the
+    emulators' shared training inputs -- as the term-major ``(E, L)`` array ``predict_mean_grad_device`` writes, kept on
+    the device.  A context manager (``_first_guess.DeviceTable``): pass it as ``table=`` so that repeated calls (dates,
+    tiles) do not compute the means again; leaving the block frees it.  One ``BatchModel`` without invQ is built for the
+    call and closed again; the candidates' gradients, which the kernel writes beside the means, are dropped."""
+    inputs = _check_shared_inputs(gps)
+    cand = _first_guess.check_candidates(inputs if candidates is None else candidates, inputs.shape[1])
+    ctx, dt = _lib.default_context(device), _lib.precision_dtype(precision)
+    E, (L, D) = len(gps), cand.shape
+    d_mu = ctx.malloc(E * L * dt.itemsize)
+    try:
+        with _batch_model(ctx, gps, inputs, dt, False) as batch, _lib.Scratch(ctx, dt) as scratch:
+            batch.predict_mean_grad_device(scratch.up(cand), d_mu, scratch.alloc(E * L * D * dt.itemsize), L)
+            ctx.synchronize()
+    except Exception:
+        ctx.free(d_mu)
+        raise
+    return _first_guess.DeviceTable(ctx, dt, d_mu, (L, 1), E, cand, tuple(gps))
+
+
+def _owner(tb, gps):
+    return tb.owner if len(tb.owner) == len(gps) and all(a is b for a, b in zip(tb.owner, gps)) else None
+
+
+def first_guess_bands(gps, candidates, obs, weights=None, prior=None, n_best=1, is_gpu=True, precision=np.float64,
+                      device=None, table=None):
+    """The starting states of ``retrieve_bands`` by look-up-table search: among the ``candidates`` (L, D) -- None: the
+    emulators' shared training inputs, where the emulator error is smallest -- per row the ``n_best`` (1..8) of lowest
+
+        J[m, l] = a[l] + 1/2 sum_e w[e, m] (mu_e(c_l) - obs[e, m])^2,     a[l] = 1/2 (c_l - x0)^T P (c_l - x0)
+
+    with ``obs`` and ``weights`` as ``misfit_bands`` takes them -- (E,) or (E, M); M is 1 when both are (E,) -- and
+    ``prior=(x0 (D,), P (D, D))`` shared by the rows (a per-row prior is a ``ValueError``: it is not an offset per
+    candidate; ``a`` is formed on the host).  Returns ``(X0, cost0, index)``: ``index (M, n_best)`` int32 and
+    ``cost0 (M, n_best)`` ascending by (cost, index), exact ties to the lower index, and ``X0 = candidates[index]``,
+    (M, D) for ``n_best`` 1, else (M, n_best, D).  A weight of exactly 0 masks its band whatever ``obs`` holds there;
+    a row with a NaN or an infinity in ``obs`` or in a non-zero weight gets index -1, cost NaN and a NaN state.
+
+    On the GPU one ``BatchModel`` without invQ evaluates ``predict_mean_grad_device`` at the candidates, the (E, L)
+    means stay on the device as the table, ``obs`` and ``weights`` go up once, ``gp_lut_search_device`` searches, and
+    only ``index`` and ``cost`` come back; the gather of ``X0`` is numpy.  ``table=`` (a ``candidate_table``) reuses a
+    table made earlier: ``candidates`` may then be None.  ``is_gpu=False`` is the explicit numpy branch, from each
+    emulator's ``cpu_predict(do_unc=False)`` and ``_lib.lut_search_numpy``; never a fallback."""
+    inputs = _check_shared_inputs(gps)
+    E, D = len(gps), inputs.shape[1]
+    if table is not None and candidates is None:
+        cand = table.candidates
+    else:
+        cand = _first_guess.check_candidates(inputs if candidates is None else candidates, D)
+    n_best = _first_guess.check_n_best(n_best, cand.shape[0])
+    obs = np.asarray(obs, dtype=np.float64)
+    if weights is not None:
+        weights = np.asarray(weights, dtype=np.float64)
+    rows = [a.shape[1] for a in (obs, weights) if a is not None and a.ndim == 2]
+    M = rows[0] if rows else 1
+    obs = _em_broadcast(obs, E, M, "obs")
+    if weights is not None:
+        weights = _em_broadcast(weights, E, M, "weights")
+    prior = _first_guess.shared_prior(prior, D)
+    offset = _first_guess.prior_offset(cand, prior)
+    if not is_gpu:
+        S = np.stack([np.asarray(gp.cpu_predict(cand, do_unc=False)[0]) for gp in gps], axis=1)        # (L, E)
+        index, cost = _lib.lut_search_numpy(S, np.broadcast_to(obs, (E, M)).T,
+                                            None if weights is None else np.broadcast_to(weights, (E, M)).T, offset, n_best)
+    else:
+        tb = table if table is not None else candidate_table(gps, cand, precision, device)
+        try:
+            tb.check(_owner(tb, gps), precision, E)
+            if tb.candidates.shape != cand.shape or (tb.candidates is not cand and not np.array_equal(tb.candidates, cand)):
+                raise ValueError("table= was built for other candidates")
+
+            def strides(a):
+                return (1, 0) if a.shape[1] == 1 and M != 1 else (M, 1)
+            index, cost = _first_guess.search_table(tb, obs, strides(obs), weights,
+                                                    strides(weights) if weights is not None else (0, 0), offset, M, n_best)
+        finally:
+            if table is None:
+                tb.close()
+    return _first_guess.gather_starts(cand, index, n_best), cost, index
+
+
+def retrieve_bands_multistart(gps, candidates, obs, weights=None, n_starts=4, table=None, **loop_args):
+    """``retrieve_bands`` from several starts per pixel: ``first_guess_bands`` with ``n_best = n_starts``, ranked with
+    the loop's shared ``prior``; the starts clipped to ``bounds``; ONE ``retrieve_bands`` call on the ``M n_starts``
+    rows (row-shaped ``obs``, ``weights`` and ``next_prior`` repeated, shared ones passed through); per pixel the start
+    of lowest ``F = cost + prior term`` is kept (``_retrieve._prior_term``; ties to the lower start, a non-finite F
+    loses; the selection is numpy on a few (M,) arrays).  ``loop_args`` are ``retrieve_bands``' keywords
+    (``is_gpu``, ``precision`` and ``device`` also choose the first guess's branch); ``emulator_unc``, ``step_fn`` and
+    per-row priors are not offered.  Returns ``(results, start (M,) int32, cost0 (M, n_starts))``: ``results`` is exactly
+    the tuple ``retrieve_bands`` returns for M rows, every array gathered from the chosen start."""
+    D = _check_shared_inputs(gps).shape[1]
+    fg = {k: loop_args[k] for k in ("is_gpu", "precision", "device") if k in loop_args}
+
+    def first_guess(prior, n_best):
+        return first_guess_bands(gps, candidates, obs, weights, prior, n_best, table=table, **fg)
+
+    def retrieve(X0, obs_r, w_r, **kw):
+        return retrieve_bands(gps, X0, obs_r, w_r, **kw)
+    return _first_guess.multistart(first_guess, retrieve, 1, obs, weights, n_starts, D, loop_args)
 
 
 def retrieve_bands_series(gps, X0, obs, weights, prior, noise, smooth=False, **loop_args):

@@ -598,6 +598,39 @@ int gp_rts_smooth_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_
                          const void* d_lo, const void* d_hi, void* d_x_smooth, void* d_cov_smooth,
                          void* d_sigma_smooth, int32_t* d_status, int64_t n_rows, int n_inputs);
 
+/* ---- look-up-table search: the first guess of a retrieval ---------------------------------------------
+ * For rows m < n_rows, candidates l < n_candidates and terms k < n_terms,
+ *   J[m][l] = a[l] + 1/2 sum_k w[m][k] (S[l][k] - o[m][k])^2
+ * and per row the n_best (1..8, <= n_candidates) candidates of lowest J: d_index [n_rows][n_best] int32 and d_cost
+ * [n_rows][n_best], ascending in the total order (J, then index): exact ties go to the lower index.  The (n_rows,
+ * n_candidates) matrix of costs is never formed.
+ *   S, the table (the emulators' means at the candidate states): element (k, l) at d_table[k * table_kstride +
+ *      l * table_lstride] (elements): (n_candidates, 1) is the term-major (n_terms, n_candidates) array that
+ *      gp_predict_mean_grad_device writes for a batch, (1, n_terms) the row-major array of gp_reconstruct_device.
+ *   o, w: element (k, m) at d_obs[k * obs_kstride + m * obs_mstride], the weights likewise; (1, 0) is one vector
+ *      shared by all rows, (0, 0) one value.  d_weights NULL: all 1.
+ *   a: d_offset [n_candidates], the prior term of a shared prior at the candidates, or NULL: 0.
+ * Arithmetic, per (m, l): d = S - o, t = w d, acc = fma(t, d, acc) over k ascending from 0 (t = d without weights),
+ * J = fma(1/2, acc, a), all in `dtype`.  J does not depend on n_rows, n_candidates, the place of the row or the
+ * candidate in the call, the grid or n_slices; no atomics; two calls agree bit for bit.
+ * A weight of exactly 0 masks its term whatever o holds there (selected away, not multiplied).  A J that is NaN or
+ * +infinity is never returned; slots for which no candidate is left hold index -1 and cost NaN -- every slot of a row
+ * with a NaN or an infinity in its observations, or in a non-zero weight -- and every other row is bit for bit what
+ * the call without those rows gives.  A NaN or an infinity in the table takes its candidate out for every row.
+ * n_slices: the candidate range is cut into that many slices of whole 64-candidate tiles so that few rows against
+ * many candidates still fill the chip (work item = 256 rows x one slice; partial lists in the context's scratch,
+ * merged in the same total order); 0: chosen from n_rows, n_candidates and the compute units (gp_launch_plan,
+ * GP_OP_LUT_SEARCH, reports it).  The result does not depend on it.
+ * GP_ERR_INVALID: a NULL context, table, obs, index or cost, a bad dtype, non-positive sizes, n_candidates beyond
+ * int32, n_best outside 1..8 or above n_candidates, a negative n_slices or stride.
+ * Device pointers of `dtype` (d_index int32), asynchronous on the context's stream. */
+int gp_lut_search_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t table_kstride, int64_t table_lstride,
+                         const void* d_offset, const void* d_obs, int64_t obs_kstride, int64_t obs_mstride,
+                         const void* d_weights, int64_t w_kstride, int64_t w_mstride, int32_t* d_index, void* d_cost,
+                         int64_t n_rows, int64_t n_candidates, int n_terms, int n_best, int n_slices);
+/* The kernel's geometry (no GPU needed): rows of a work item, candidates of a register tile, terms of a staged chunk. */
+int gp_lut_search_geometry(int* rows_per_item, int* candidate_tile, int* term_chunk);
+
 /* ---- training objective (next after the predict path: SURVEY.md 8f rank 2) -------------------
  * For each of n_sets hyper-parameter vectors theta [n_sets][n_inputs+2]: what
  * GaussianProcess.loglikelihood + partial_devs compute (gp_emulator/GaussianProcess.py:52-125):
@@ -637,6 +670,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_MISFIT 4             /* n_inputs is n_pcs and aux n_bands, as for GP_OP_RECONSTRUCT */
 #define GP_OP_MV_GRAM 5            /* gp_mv_weight_gram_device: n_inputs is n_pcs and aux n_bands */
 #define GP_OP_VAR_GRAD 6           /* gp_predict_var_grad_device */
+#define GP_OP_LUT_SEARCH 7         /* gp_lut_search_device: n_inputs is n_terms and aux n_candidates; rest_items is n_slices */
 #define GP_PLAN_PREDICT_FEW 1      /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
@@ -649,6 +683,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_MISFIT 10          /* misfit_kernel: an item is 64 rows over all bands */
 #define GP_PLAN_MV_GRAM 11         /* weight_gram_kernel: an item is 64 rows over all bands; workgroups per CU by instance */
 #define GP_PLAN_VAR_GRAD 12        /* var_grad_kernel: predict_kernel's items and grid, whatever the size of the call */
+#define GP_PLAN_LUT_SEARCH 13      /* lut_search_kernel: an item is 256 rows x one slice of the candidates */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
