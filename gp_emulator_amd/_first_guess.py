@@ -44,11 +44,13 @@ def gather_starts(candidates, index, n_best):
 class DeviceTable(object):
     """A table of candidate means resident on the device: what ``candidate_table`` of either emulator type hands to
     ``table=``.  ``d_table`` holds element (term k, candidate l) at ``k * strides[0] + l * strides[1]``; ``close()``
-    (or leaving the ``with`` block) frees it."""
+    (or leaving the ``with`` block) frees it.  ``space`` tags what the terms are: "band" (the terms of the data term
+    itself: bands, or per-band emulators) or "pc" (the per-PC means of a ``MultivariateEmulator``, searched by
+    ``gp_lut_search_pc_device``)."""
 
-    def __init__(self, ctx, dtype, d_table, strides, n_terms, candidates, owner):
+    def __init__(self, ctx, dtype, d_table, strides, n_terms, candidates, owner, space="band"):
         self.ctx, self.dtype, self.d_table, self.strides = ctx, np.dtype(dtype), d_table, strides
-        self.n_terms, self.candidates, self.owner = n_terms, candidates, owner
+        self.n_terms, self.candidates, self.owner, self.space = n_terms, candidates, owner, space
 
     def __enter__(self):
         return self
@@ -61,9 +63,11 @@ class DeviceTable(object):
             self.ctx.free(self.d_table)
             self.d_table = None
 
-    def check(self, owner, dtype, n_terms):
+    def check(self, owner, dtype, n_terms, space="band"):
         if self.d_table is None:
             raise ValueError("the candidate table has been closed")
+        if self.space != space:
+            raise ValueError("table= is a %r-space table, the call searches in %r space" % (self.space, space))
         if self.owner is not owner or self.dtype != np.dtype(dtype) or self.n_terms != n_terms:
             raise ValueError("table= was built for other emulators or another precision")
 
@@ -78,6 +82,71 @@ def search_table(tb, obs, obs_strides, weights, w_strides, offset, M, n_best):
         ctx.lut_search_device(dt, tb.d_table, tb.strides, d_a, d_o, obs_strides, d_w, w_strides, d_i, d_c, M,
                               tb.candidates.shape[0], tb.n_terms, n_best)
         return _lib._download(ctx, d_i, (M, n_best), np.int32), _lib._download(ctx, d_c, (M, n_best), dt)
+
+
+def rows_of(a, rows):
+    """``a[rows]`` of a row-shaped array; a shared vector or None as it is."""
+    return a if a is None or a.ndim == 1 else a[rows]
+
+
+def search_table_rows(tb, obs, weights, offset, M, n_best):
+    """``search_table`` for row-major host arrays: ``obs`` (K,) or (M, K), ``weights`` None, (K,) or (M, K)."""
+    def strides(a):
+        return (1, tb.n_terms) if a.ndim == 2 else (1, 0)
+    return search_table(tb, obs, strides(obs), weights, strides(weights) if weights is not None else (0, 0), offset, M, n_best)
+
+
+def route_rows(index, cost, status, band_search):
+    """The rows the PC form could not centre (``status != 0``) searched in band space: ``band_search(rows)`` returns
+    their ``(index, cost)``, which replace, in place, the empty slots the PC search left.  Returns how many there were."""
+    rows = np.flatnonzero(status != 0)
+    if rows.size:
+        index[rows], cost[rows] = band_search(rows)
+    return int(rows.size)
+
+
+def mask_obs(obs, weights, dtype):
+    """``obs`` with 0 selected in wherever the weight, rounded to the device ``dtype``, is exactly 0 (``obs`` itself
+    without weights): what the PC-space set-up takes, whose misfit kernel multiplies by the weight and does not
+    select."""
+    if weights is None:
+        return obs
+    masked = np.asarray(weights, dtype=dtype) == 0
+    return np.where(masked, 0.0, obs) if masked.any() else obs
+
+
+def search_table_pc(tb, d_basis, obs, weights, offset, M, n_best, n_bands, stages=None):
+    """The PC-space search of ``M`` rows against the device table ``tb`` of per-PC means: ``obs`` (masked terms
+    selected to 0 here) and ``weights`` go up once, ``gp_mv_lut_prepare_device`` and ``gp_lut_search_pc_device`` run on
+    the context's stream, ``index``, ``cost`` and ``status`` come back.  ``stages``: a dict that receives the device
+    times in ms of the set-up and of the search (HIP events), for the timing tool."""
+    ctx, dt = tb.ctx, tb.dtype
+    P, L, isz = tb.n_terms, tb.candidates.shape[0], tb.dtype.itemsize
+    obs = mask_obs(obs, weights, dt)
+    per_row = weights is not None and weights.ndim == 2
+    with _lib.Scratch(ctx, dt) as scratch:
+        d_o, d_w, d_a = scratch.up(obs), scratch.up(weights), scratch.up(offset)
+        d_G = scratch.alloc((M if per_row else 1) * P * P * isz)
+        d_c0, d_j0, d_g0, d_st = scratch.alloc(P * M * isz), scratch.alloc(M * isz), scratch.alloc(P * M * isz), scratch.alloc(M * 4)
+        d_i, d_c = scratch.alloc(M * n_best * 4), scratch.alloc(M * n_best * isz)
+        ev = [ctx.event() for _ in range(3)] if stages is not None else None
+        if ev:
+            ctx.record(ev[0])
+        ctx.mv_lut_prepare_device(dt, d_basis, d_o, n_bands if obs.ndim == 2 else 0, d_w, n_bands if per_row else 0, d_G,
+                                  P * P if per_row else 0, d_c0, d_j0, d_g0, d_st, M, P, n_bands)
+        if ev:
+            ctx.record(ev[1])
+        ctx.lut_search_pc_device(dt, tb.d_table, tb.strides, d_a, d_c0, d_j0, d_g0, d_G, P * P if per_row else 0, d_st, d_i,
+                                 d_c, M, L, P, n_best)
+        if ev:
+            ctx.record(ev[2])
+        out = (_lib._download(ctx, d_i, (M, n_best), np.int32), _lib._download(ctx, d_c, (M, n_best), dt),
+               _lib._download(ctx, d_st, (M,), np.int32))
+        if ev:
+            stages["prepare_ms"], stages["search_ms"] = ctx.elapsed_ms(ev[0], ev[1]), ctx.elapsed_ms(ev[1], ev[2])
+            for e in ev:
+                ctx.event_destroy(e)
+        return out
 
 
 def check_n_best(n_best, L):

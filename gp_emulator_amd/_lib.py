@@ -14,7 +14,8 @@ import numpy as np
 
 from ._dense_numpy import (DAMPINGS, newton_step_numpy, posterior_cov_numpy, prec_rows, prior_propagate_numpy,  # noqa: F401
                            prior_rows, row_strides, rts_smooth_numpy, _cholesky_inverse_numpy, _mirror_lower)
-from ._lut_numpy import lut_search_numpy  # noqa: F401
+from ._lut_numpy import MAX_PCS as lut_pc_max_pcs  # noqa: F401
+from ._lut_numpy import lut_pc_prepare_numpy, lut_search_numpy, lut_search_pc_numpy  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_PREDICT_LIB lets tools/ab_bench.py time differently-built variants of the library on
@@ -89,6 +90,11 @@ SIGNATURES = {
     "gp_lut_search_device": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
                                      c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int]),
     "gp_lut_search_geometry": (c_int, [ctypes.POINTER(c_int)] * 3),
+    "gp_lut_search_pc_device": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_i64] + [c_void_p] * 5 + [c_i64] + [c_void_p] * 3
+                                + [c_i64, c_i64, c_int, c_int, c_int]),
+    "gp_lut_search_pc_geometry": (c_int, [c_int, c_int] + [ctypes.POINTER(c_int)] * 4),
+    "gp_mv_lut_prepare_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
+                                 + [c_void_p] * 4 + [c_i64, c_int, c_int]),
     "gp_hessian_f64": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_hessian_f32": (c_int, [c_void_p] + [c_void_p] * 5 + [c_i64, c_int, c_int, c_int]),
     "gp_reconstruct_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int]),
@@ -702,6 +708,32 @@ class Context:
                                             int(n_candidates), int(n_terms), int(n_best), int(n_slices)),
               "gp_lut_search_device")
 
+    def lut_search_pc_device(self, dtype, d_table, table_strides, d_offset, d_c0, d_j0, d_g0, d_gram, gram_stride, d_status,
+                             d_index, d_cost, n_rows, n_candidates, n_pcs, n_best, n_slices=0):
+        """Asynchronous look-up-table search in PC space (``gp_lut_search_pc_device``): per row the ``n_best`` candidates
+        of lowest ``J[m, l] = a[l] + J0[m] + g0[:, m]^T d + 1/2 d^T G[m] d``, ``d = mu[:, l] - c0[:, m]``, into
+        ``d_index`` (int32) and ``d_cost``, both ``[n_rows][n_best]``, with ``lut_search_device``'s order and empty
+        slots.  ``table_strides`` is the element pair ``(per PC, per candidate)`` of the means: ``(L, 1)`` for the
+        PC-major array ``predict_mean_grad_device`` writes.  ``d_c0`` / ``d_g0`` are ``[n_pcs][n_rows]``, ``d_j0``
+        ``[n_rows]`` (``mv_lut_prepare_device`` writes them), row m's matrix is at ``d_gram + m * gram_stride``
+        elements (0: one for all rows).  ``d_offset`` and ``d_status`` (int32: rows with a non-zero entry are skipped)
+        may be None."""
+        check(self.lib.gp_lut_search_pc_device(self.h, _dtype_code(dtype), d_table, int(table_strides[0]), int(table_strides[1]),
+                                               d_offset, d_c0, d_j0, d_g0, d_gram, int(gram_stride), d_status, d_index, d_cost,
+                                               int(n_rows), int(n_candidates), int(n_pcs), int(n_best), int(n_slices)),
+              "gp_lut_search_pc_device")
+
+    def mv_lut_prepare_device(self, dtype, d_basis, d_obs, obs_stride, d_weights, weights_stride, d_gram, gram_stride,
+                              d_c0, d_j0, d_g0, d_status, n_rows, n_pcs, n_bands):
+        """Asynchronous set-up of the PC-space search (``gp_mv_lut_prepare_device``): ``d_gram`` (per row with per-row
+        weights, ``gram_stride = n_pcs^2``; else one matrix, stride 0), the centre ``d_c0 [n_pcs][n_rows]`` solving
+        ``G c0 = B W o``, the misfit there ``d_j0 [n_rows]`` and its coefficient ``d_g0 [n_pcs][n_rows]``, and
+        ``d_status`` (int32; non-zero: the row cannot be centred).  ``d_obs`` must hold 0 wherever the weight is
+        exactly 0 (the callers select that in before the upload).  ``d_weights`` may be None."""
+        check(self.lib.gp_mv_lut_prepare_device(self.h, _dtype_code(dtype), d_basis, d_obs, int(obs_stride), d_weights,
+                                                int(weights_stride), d_gram, int(gram_stride), d_c0, d_j0, d_g0, d_status,
+                                                int(n_rows), int(n_pcs), int(n_bands)), "gp_mv_lut_prepare_device")
+
     def lut_search(self, table, obs, weights=None, offset=None, n_best=1, precision=None, is_gpu=True, n_slices=0):
         """``(index (M, n_best) int32, cost (M, n_best))`` of the look-up-table search for the host arrays ``table``
         (L, K), ``obs`` (K,) or (M, K), ``weights`` None, (K,) or (M, K) and ``offset`` None or (L,): uploads, launches
@@ -1160,12 +1192,13 @@ class BatchModel(Model):
 
 GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_VAR_GRAD = 0, 1, 2, 3, 4, 5, 6
 GP_OP_LUT_SEARCH = 7
+GP_OP_LUT_SEARCH_PC = 8
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
                 6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
-                10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search"}
+                10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search", 14: "lut_search_pc"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
              "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM, "var_grad": GP_OP_VAR_GRAD,
-             "lut_search": GP_OP_LUT_SEARCH}
+             "lut_search": GP_OP_LUT_SEARCH, "lut_search_pc": GP_OP_LUT_SEARCH_PC}
 
 
 def lut_search_geometry():
@@ -1174,6 +1207,17 @@ def lut_search_geometry():
     r, t, c = c_int(0), c_int(0), c_int(0)
     check(load().gp_lut_search_geometry(ctypes.byref(r), ctypes.byref(t), ctypes.byref(c)), "gp_lut_search_geometry")
     return dict(rows_per_item=r.value, candidate_tile=t.value, term_chunk=c.value)
+
+
+def lut_search_pc_geometry(n_pcs, precision=np.float64):
+    """``dict(rows_per_item, candidate_tile, padded_pcs, workgroups_per_cu)`` of ``lut_search_pc_kernel`` for ``n_pcs``
+    and the device dtype: the rows of a work item, the candidates of a staged tile, the padded ``n_pcs`` the compiled
+    instance holds in registers and the workgroups a compute unit takes of it (``gp_lut_search_pc_geometry``; no GPU
+    needed)."""
+    r, t, pp, w = c_int(0), c_int(0), c_int(0), c_int(0)
+    check(load().gp_lut_search_pc_geometry(_dtype_code(precision), int(n_pcs), ctypes.byref(r), ctypes.byref(t),
+                                           ctypes.byref(pp), ctypes.byref(w)), "gp_lut_search_pc_geometry")
+    return dict(rows_per_item=r.value, candidate_tile=t.value, padded_pcs=pp.value, workgroups_per_cu=w.value)
 
 
 def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_pcs=0, n_bands=0,
@@ -1187,11 +1231,14 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
     output pointers are 16-byte aligned.  reconstruct, misfit and mv_gram take ``n_pcs`` and ``n_bands``.
     "lut_search" takes ``n_terms`` and ``n_candidates``: an item is ``rows_per_item`` rows against one slice of the
     candidates, and the dict also holds ``slices`` (the slices chosen: items = row tiles x slices), ``candidate_tile``
-    and ``term_chunk`` (``lut_search_geometry``)."""
+    and ``term_chunk`` (``lut_search_geometry``).  "lut_search_pc" takes ``n_pcs`` and ``n_candidates``: the same
+    items and slices, with ``candidate_tile``, ``padded_pcs`` and ``workgroups_per_cu`` (``lut_search_pc_geometry``)."""
     code = _PLAN_OPS[op]
-    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_LUT_SEARCH)
+    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_LUT_SEARCH, GP_OP_LUT_SEARCH_PC)
     if code == GP_OP_LUT_SEARCH:
         n_pcs, n_bands = n_terms, n_candidates
+    if code == GP_OP_LUT_SEARCH_PC:
+        n_bands = n_candidates
     k, wg, rwg, rpi = c_int(0), c_int(0), c_int(0), c_int(0)
     items, ritems = c_i64(0), c_i64(0)
     check(load().gp_launch_plan(
@@ -1204,6 +1251,11 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
         return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
                     rest_items=0, rest_workgroups=0, slices=ritems.value, candidate_tile=geo["candidate_tile"],
                     term_chunk=geo["term_chunk"])
+    if code == GP_OP_LUT_SEARCH_PC:
+        geo = lut_search_pc_geometry(n_pcs, precision)
+        return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
+                    rest_items=0, rest_workgroups=0, slices=ritems.value, candidate_tile=geo["candidate_tile"],
+                    padded_pcs=geo["padded_pcs"], workgroups_per_cu=geo["workgroups_per_cu"])
     return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
                 rest_items=ritems.value, rest_workgroups=rwg.value)
 

@@ -327,6 +327,16 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     rpi = gpk::lkRows;
     g = lp.grid;
     rest.items = lp.n_slices;
+  } else if (op == GP_OP_LUT_SEARCH_PC) {
+    // (n_inputs = n_pcs here; aux = n_candidates; rest_items reports the slices)
+    if (n_inputs <= 0 || aux <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    if (n_inputs > gpk::lpMaxPcs) return fail(GP_ERR_UNSUPPORTED, "the PC-space search serves n_pcs <= %d", gpk::lpMaxPcs);
+    const int wgs = gpk::lut_pc_wgs_per_cu(gpk::lut_pc_padded(n_inputs), f64 ? 8 : 4);
+    const gpk::LutPlan lp = gpk::plan_lut_search_pc(n_rows, aux, gpk::lkRows, gpk::lkTile, gpk::lut_cap(compute_units, wgs), 0);
+    k = GP_PLAN_LUT_SEARCH_PC;
+    rpi = gpk::lkRows;
+    g = lp.grid;
+    rest.items = lp.n_slices;
   } else if (op == GP_OP_VAR_GRAD) {
     int kd, knb;
     int rc = pick_kernel(n_train, n_inputs, &kd, &knb);

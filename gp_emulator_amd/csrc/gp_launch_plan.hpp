@@ -138,4 +138,15 @@ inline LutPlan plan_lut_search(long long n_rows, long long n_candidates, int row
 }
 inline long long lut_cap(int compute_units, int wgs_per_cu) { return (long long)compute_units * wgs_per_cu; }
 
+// lut_search_pc_kernel: lut_search_kernel's items, slices and persistent grid.  The instance is the padded n_pcs
+// (8, 12 or 16: what its per-row registers are sized for); a lane holds the row's packed G, so the fp64 instances
+// from 12 PCs on take more than 256 VGPRs and a CU holds one 4-wave workgroup of them, two of every other instance.
+constexpr int lpMaxPcs = 16;         // the largest n_pcs the PC-space search and its set-up serve
+constexpr int lut_pc_padded(int n_pcs) { return n_pcs <= 8 ? 8 : n_pcs <= 12 ? 12 : 16; }
+constexpr int lut_pc_wgs_per_cu(int padded_pcs, int elem_bytes) { return elem_bytes == 8 && padded_pcs > 8 ? 1 : 2; }
+inline LutPlan plan_lut_search_pc(long long n_rows, long long n_candidates, int rows_per_item, int cand_tile, long long cap,
+                                  int forced) {
+  return plan_lut_search(n_rows, n_candidates, rows_per_item, cand_tile, cap, forced);
+}
+
 }  // namespace gpk

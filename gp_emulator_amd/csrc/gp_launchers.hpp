@@ -24,6 +24,8 @@ template <typename T> struct MisfitArgs;
 template <typename T> struct GramArgs;
 template <typename T> struct MvUncArgs;
 template <typename T> struct LutArgs;
+template <typename T> struct LutPcArgs;
+template <typename T> struct LutPcSolveArgs;
 struct TrainArgs;
 
 #pragma GCC visibility push(hidden)      // (the launchers are the library's own)
@@ -56,6 +58,11 @@ template <typename T> hipError_t launch_weight_gram(const GramArgs<T>&, int cus,
 template <typename T> hipError_t launch_mv_unc(const MvUncArgs<T>&, hipStream_t);
 // lut_search_kernel on `grid` workgroups, then lut_merge_kernel when the call is sliced
 template <typename T> hipError_t launch_lut_search(const LutArgs<T>&, int grid, hipStream_t);
+// lut_search_pc_kernel on `grid` workgroups (the instance by n_pcs), then lut_merge_kernel when the call is sliced;
+// lut_pc_solve_kernel, a workgroup per 8 rows; x[0 .. n) = v
+template <typename T> hipError_t launch_lut_search_pc(const LutPcArgs<T>&, int grid, hipStream_t);
+template <typename T> hipError_t launch_lut_pc_solve(const LutPcSolveArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_lut_pc_fill(T* x, T v, long long n, hipStream_t);
 
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);      // fp64 only
 #pragma GCC visibility pop

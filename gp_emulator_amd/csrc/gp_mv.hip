@@ -3,6 +3,8 @@
 
 #include "gp_gram_kernel.hpp"
 #include "gp_launchers.hpp"
+#include "gp_lut_pc_solve_kernel.hpp"
+#include "gp_lut_search_pc_kernel.hpp"
 #include "gp_misfit_kernel.hpp"
 #include "gp_mv_unc_kernel.hpp"
 #include "gp_reconstruct_kernel.hpp"
@@ -360,6 +362,56 @@ int gp_mv_misfit_unc_device(gp_ctx* ctx, int dtype, const void* d_cost0, const v
     const hipError_t e = gpk::launch_mv_unc<T>(a, ctx->stream);
     if (e != hipSuccess) return fail(GP_ERR_HIP, "mv variance term kernel launch: %s", hipGetErrorString(e));
     return GP_OK;
+  });
+}
+
+int gp_mv_lut_prepare_device(gp_ctx* ctx, int dtype, const void* d_basis, const void* d_obs, int64_t obs_stride,
+                             const void* d_weights, int64_t weights_stride, void* d_gram, int64_t gram_stride,
+                             void* d_c0, void* d_j0, void* d_g0, int32_t* d_status, int64_t n_rows, int n_pcs,
+                             int n_bands) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (!d_basis || !d_obs || !d_gram || !d_c0 || !d_j0 || !d_g0 || !d_status) return fail(GP_ERR_INVALID, "null device pointer");
+  if (n_rows <= 0 || n_pcs <= 0 || n_bands <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_pcs > gpk::lpMaxPcs) return fail(GP_ERR_UNSUPPORTED, "the PC-space search serves n_pcs <= %d", gpk::lpMaxPcs);
+  if (obs_stride < 0 || (obs_stride != 0 && obs_stride < n_bands) || weights_stride < 0 ||
+      (d_weights && weights_stride != 0 && weights_stride < n_bands))
+    return fail(GP_ERR_INVALID, "a row stride is 0 (one vector for all rows) or >= n_bands");
+  const bool per_row = d_weights && weights_stride != 0;
+  // (the Gram kernel writes its matrices packed)
+  if (gram_stride != (per_row ? (int64_t)n_pcs * n_pcs : 0))
+    return fail(GP_ERR_INVALID, "gram_stride is n_pcs^2 with per-row weights and 0 otherwise");
+  if (n_rows > (int64_t)0x7fffffff * gpk::kLutPcSolveRowsPerWg) return fail(GP_ERR_INVALID, "n_rows too large for one launch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t isz = dtype == GP_F64 ? 8 : 4;
+  if (!d_weights)
+    if (int rc = ensure_scratch(ctx, (size_t)n_bands * isz)) return rc;
+  // 1. the misfit at mu = 0: coef = -B W o
+  HIP_TRY(hipMemsetAsync(d_c0, 0, (size_t)n_pcs * (size_t)n_rows * isz, st));
+  if (int rc = misfit_on(ctx, dtype, d_basis, d_c0, nullptr, d_obs, obs_stride, d_weights, weights_stride, nullptr, d_g0,
+                         nullptr, n_rows, n_pcs, n_bands, 1, st))
+    return rc;
+  return for_dtype(dtype, [&](auto t) -> int {
+    using T = GP_TAG_TYPE(t);
+    // 2. G: every row's, or the one of the shared weights (of a vector of ones without weights)
+    const T* w = as<T>(d_weights);
+    if (!w) {
+      const hipError_t e = gpk::launch_lut_pc_fill<T>((T*)ctx->scratch, T(1), n_bands, st);
+      if (e != hipSuccess) return fail(GP_ERR_HIP, "fill kernel launch: %s", hipGetErrorString(e));
+      w = (const T*)ctx->scratch;
+    }
+    gpk::GramArgs<T> g{as<T>(d_basis), w, as<T>(d_gram), per_row ? n_rows : 1, per_row ? weights_stride : 0, n_pcs, n_bands};
+    hipError_t e = gpk::launch_weight_gram<T>(g, ctx->compute_units, st);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "weight gram kernel launch: %s", hipGetErrorString(e));
+    // 3. c0 = G^-1 B W o
+    const double eps = dtype == GP_F64 ? 2.220446049250313e-16 : 1.1920928955078125e-07;
+    gpk::LutPcSolveArgs<T> s{as<T>(d_gram), gram_stride, as<T>(d_g0), as<T>(d_c0), d_status, (n_bands + n_pcs) * eps, n_rows, n_pcs};
+    e = gpk::launch_lut_pc_solve<T>(s, st);
+    if (e != hipSuccess) return fail(GP_ERR_HIP, "lut pc solve kernel launch: %s", hipGetErrorString(e));
+    // 4. J0 and g0 at the c0 that was stored
+    return misfit_on(ctx, dtype, d_basis, d_c0, nullptr, d_obs, obs_stride, d_weights, weights_stride, d_j0, d_g0, nullptr,
+                     n_rows, n_pcs, n_bands, 1, st);
   });
 }
 

@@ -6,6 +6,7 @@
 #include "gp_launch_plan.hpp"
 #include "gp_launchers.hpp"
 #include "gp_lut_search_kernel.hpp"
+#include "gp_lut_search_pc_kernel.hpp"
 #include "gp_newton_kernel.hpp"
 #include "gp_posterior_cov_kernel.hpp"
 #include "gp_prior_propagate_kernel.hpp"
@@ -283,6 +284,67 @@ int gp_lut_search_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t ta
     a.tiles_per_slice = plan.tiles_per_slice;
     a.K = n_terms, a.n_best = n_best, a.n_slices = plan.n_slices;
     return launched(gpk::launch_lut_search<T>(a, plan.grid.workgroups, ctx->stream), "lut search");
+  });
+}
+
+int gp_lut_search_pc_geometry(int dtype, int n_pcs, int* rows_per_item, int* candidate_tile, int* padded_pcs,
+                              int* workgroups_per_cu) {
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_pcs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_pcs > gpk::lpMaxPcs) return fail(GP_ERR_UNSUPPORTED, "the PC-space search serves n_pcs <= %d", gpk::lpMaxPcs);
+  const int pp = gpk::lut_pc_padded(n_pcs);
+  if (rows_per_item) *rows_per_item = gpk::lkRows;
+  if (candidate_tile) *candidate_tile = gpk::lkTile;
+  if (padded_pcs) *padded_pcs = pp;
+  if (workgroups_per_cu) *workgroups_per_cu = gpk::lut_pc_wgs_per_cu(pp, dtype == GP_F64 ? 8 : 4);
+  return GP_OK;
+}
+
+int gp_lut_search_pc_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t table_pstride, int64_t table_lstride,
+                            const void* d_offset, const void* d_c0, const void* d_j0, const void* d_g0,
+                            const void* d_gram, int64_t gram_stride, const int32_t* d_status, int32_t* d_index,
+                            void* d_cost, int64_t n_rows, int64_t n_candidates, int n_pcs, int n_best, int n_slices) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (!d_table || !d_c0 || !d_j0 || !d_g0 || !d_gram || !d_index || !d_cost) return fail(GP_ERR_INVALID, "null device pointer");
+  if (n_rows <= 0 || n_candidates <= 0 || n_pcs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_pcs > gpk::lpMaxPcs) return fail(GP_ERR_UNSUPPORTED, "the PC-space search serves n_pcs <= %d", gpk::lpMaxPcs);
+  if (n_candidates > 0x7fffffffLL) return fail(GP_ERR_INVALID, "n_candidates too large for an int32 index");
+  if (n_best < 1) return fail(GP_ERR_INVALID, "n_best %d is not in 1..%d", n_best, gpk::lkMaxBest);
+  if (n_best > gpk::lkMaxBest) return fail(GP_ERR_UNSUPPORTED, "the search keeps n_best <= %d", gpk::lkMaxBest);
+  if (n_best > n_candidates) return fail(GP_ERR_INVALID, "n_best %d exceeds the %lld candidates", n_best, (long long)n_candidates);
+  if (n_slices < 0) return fail(GP_ERR_INVALID, "negative n_slices");
+  if (table_pstride < 0 || table_lstride < 0) return fail(GP_ERR_INVALID, "negative stride");
+  if (gram_stride < 0 || (gram_stride != 0 && gram_stride < (int64_t)n_pcs * n_pcs))
+    return fail(GP_ERR_INVALID, "gram_stride is 0 (one matrix for all rows) or >= n_pcs^2");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int wgs = gpk::lut_pc_wgs_per_cu(gpk::lut_pc_padded(n_pcs), dtype == GP_F64 ? 8 : 4);
+  const gpk::LutPlan plan = gpk::plan_lut_search_pc(n_rows, n_candidates, gpk::lkRows, gpk::lkTile,
+                                                    gpk::lut_cap(ctx->compute_units, wgs), n_slices);
+  const int nb = gpk::lut_list_size(n_best);
+  const size_t isz = dtype == GP_F64 ? 8 : 4;
+  const size_t n_part = plan.n_slices > 1 ? (size_t)plan.n_slices * (size_t)n_rows * nb : 0;
+  if (n_part)
+    if (int rc = ensure_scratch(ctx, n_part * (isz + 4))) return rc;
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::LutPcArgs<T> a;
+    a.table = as<T>(d_table);
+    a.offset = as<T>(d_offset);
+    a.c0 = as<T>(d_c0);
+    a.j0 = as<T>(d_j0);
+    a.g0 = as<T>(d_g0);
+    a.gram = as<T>(d_gram);
+    a.status = d_status;
+    a.index = d_index;
+    a.cost = as<T>(d_cost);
+    a.part_cost = n_part ? (T*)ctx->scratch : nullptr;          // costs first: they carry the alignment
+    a.part_index = n_part ? (int*)((T*)ctx->scratch + n_part) : nullptr;
+    a.t_ps = table_pstride, a.t_ls = table_lstride, a.gram_stride = gram_stride;
+    a.M = n_rows, a.L = n_candidates;
+    a.tiles_per_slice = plan.tiles_per_slice;
+    a.P = n_pcs, a.n_best = n_best, a.n_slices = plan.n_slices;
+    return launched(gpk::launch_lut_search_pc<T>(a, plan.grid.workgroups, ctx->stream), "lut search pc");
   });
 }
 

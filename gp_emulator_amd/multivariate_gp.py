@@ -732,31 +732,40 @@ class MultivariateEmulator(object):
                                        misfit_unc if emulator_unc else misfit, next_prior, return_A)
 
     # ---- the first guess: look-up-table search in band space --------------------------------------
-    def candidate_table(self, candidates, precision=np.float64):
+    def candidate_table(self, candidates, precision=np.float64, space="band"):
         """The device table of ``first_guess_many``: the spectra of the ``candidates`` (L, D), row-major
         ``(L, N_full)``, from ``predict_mean_grad_device`` and ``gp_reconstruct_device`` on the resident emulator; it
         never crosses PCIe.  A context manager (``_first_guess.DeviceTable``): pass it as ``table=`` so that repeated
-        calls (dates, tiles) do not compute the spectra again; leaving the block frees it."""
+        calls (dates, tiles) do not compute the spectra again; leaving the block frees it.  ``space="pc"`` keeps only
+        the ``(n_pcs, L)`` per-PC means, PC-major as ``predict_mean_grad_device`` writes them, for
+        ``first_guess_many(space="pc")``: nothing is reconstructed, and the table is ``N_full / n_pcs`` times smaller."""
         from . import _first_guess
+        if space not in ("band", "pc"):
+            raise ValueError("space must be 'band' or 'pc'")
         dt = _lib.precision_dtype(precision)
         cand = _first_guess.check_candidates(candidates, self.emulators[0].inputs.shape[1])
         st = self._fresh_gpu_state(dt)
         ctx, batch, d_basis = st["ctx"], st["batch"], st["d_basis"]
         P, B, (L, D) = self.n_pcs, self.basis_functions.shape[1], cand.shape
-        d_table = ctx.malloc(L * B * dt.itemsize)
+        if space == "pc" and P > _lib.lut_pc_max_pcs:
+            raise ValueError("the PC-space search serves n_pcs <= %d" % _lib.lut_pc_max_pcs)
+        d_table = ctx.malloc(L * (B if space == "band" else P) * dt.itemsize)
         try:
             with _lib.Scratch(ctx, dt) as scratch:
-                d_mu = scratch.alloc(P * L * dt.itemsize)
+                d_mu = scratch.alloc(P * L * dt.itemsize) if space == "band" else d_table
                 batch.predict_mean_grad_device(scratch.up(cand), d_mu, scratch.alloc(P * L * D * dt.itemsize), L)
-                ctx.reconstruct_device(dt, d_basis, d_mu, d_table, L, P, B)
+                if space == "band":
+                    ctx.reconstruct_device(dt, d_basis, d_mu, d_table, L, P, B)
                 ctx.synchronize()
         except Exception:
             ctx.free(d_table)
             raise
+        if space == "pc":
+            return _first_guess.DeviceTable(ctx, dt, d_table, (L, 1), P, cand, self, space="pc")
         return _first_guess.DeviceTable(ctx, dt, d_table, (1, B), B, cand, self)
 
     def first_guess_many(self, candidates, obs, weights=None, prior=None, n_best=1, is_gpu=True, precision=np.float64,
-                         table=None):
+                         table=None, space="band"):
         """The starting states of ``retrieve_many`` by look-up-table search in band space: among the ``candidates``
         (L, D) per row the ``n_best`` (1..8) of lowest
 
@@ -768,8 +777,26 @@ class MultivariateEmulator(object):
         rules.  On the GPU the table is the candidates' spectra on the device (``candidate_table``; ``table=`` reuses
         one, ``candidates`` may then be None), ``obs`` and ``weights`` go up once and only ``index`` and ``cost`` come
         back.  ``is_gpu=False`` is the explicit numpy branch (``predict_many(is_gpu=False)`` and
-        ``_lib.lut_search_numpy``); never a fallback."""
+        ``_lib.lut_search_numpy``); never a fallback.
+
+        ``space="pc"`` ranks by the same J evaluated in PC space: with the row's weighted least-squares centre ``c0``
+        (``G c0 = B W obs``, ``G = B W B^T``), ``J = a + J0 + g0^T d + 1/2 d^T G d`` for ``d = mu(c_l) - c0``, ``J0`` and
+        ``g0`` the misfit and its coefficient at ``c0`` -- exact for any ``c0``, a sum of non-negative terms and a tiny
+        signed one, ``n_pcs (n_pcs + 1) / 2 + 3 n_pcs + 2`` operations per (row, candidate) instead of ``3 N_full``.
+        The table is the ``(n_pcs, L)`` means (``candidate_table(space="pc")``); ``gp_mv_lut_prepare_device`` and
+        ``gp_lut_search_pc_device`` run on the device; same ``(Y0, cost0, index)``, same tie, zero-weight and NaN rules;
+        a ``table=`` of the other space is a ``ValueError``.  ``is_gpu=False, space="pc"`` is the explicit numpy branch
+        (``_lib.lut_search_pc_numpy``).  Rows the PC form cannot centre -- fewer informative bands than PCs, all masked,
+        non-finite input, or a ``G`` that is ill-conditioned at the search's precision: a Cholesky pivot not above
+        ``(N_full + n_pcs) eps G_kk``, ``eps`` of the device dtype (2.5e-4 of the diagonal in float32 at 2 101 bands,
+        4.7e-13 in float64), below which a pivot of a matrix summed over the bands is not told from zero; the set-up
+        reports them -- are searched in band space, with a band table built only when such rows exist, at the band
+        search's cost per row, and their results are bit for bit ``space="band"`` results: a routing rule by row,
+        stated here, not a fallback of precision.  ``self.last_routed_rows`` holds the number of rows the last
+        ``space="pc"`` call routed."""
         from . import _first_guess
+        if space not in ("band", "pc"):
+            raise ValueError("space must be 'band' or 'pc'")
         D, B = self.emulators[0].inputs.shape[1], self.basis_functions.shape[1]
         cand = table.candidates if table is not None and candidates is None else _first_guess.check_candidates(candidates, D)
         n_best = _first_guess.check_n_best(n_best, cand.shape[0])
@@ -785,36 +812,52 @@ class MultivariateEmulator(object):
         prior = _first_guess.shared_prior(prior, D)
         offset = _first_guess.prior_offset(cand, prior)
         if not is_gpu:
-            index, cost = _lib.lut_search_numpy(self.predict_many(cand, is_gpu=False), obs, weights, offset, n_best)
+            if space == "pc":
+                if self.n_pcs > _lib.lut_pc_max_pcs:
+                    raise ValueError("the PC-space search serves n_pcs <= %d" % _lib.lut_pc_max_pcs)
+                mu = np.stack([gp.predict(cand)[0] for gp in self.emulators])                       # (P, L)
+                index, cost, status = _lib.lut_search_pc_numpy(mu, self.basis_functions, obs, weights, offset, n_best)
+                self.last_routed_rows = _first_guess.route_rows(index, cost, status, lambda rows: _lib.lut_search_numpy(
+                    mu.T @ self.basis_functions, np.broadcast_to(obs, (M, B))[rows], _first_guess.rows_of(weights, rows),
+                    offset, n_best))
+            else:
+                index, cost = _lib.lut_search_numpy(self.predict_many(cand, is_gpu=False), obs, weights, offset, n_best)
         else:
-            tb = table if table is not None else self.candidate_table(cand, precision)
+            tb = table if table is not None else self.candidate_table(cand, precision, space)
             try:
-                tb.check(self, precision, B)
+                tb.check(self, precision, B if space == "band" else self.n_pcs, space)
                 if tb.candidates.shape != cand.shape or (tb.candidates is not cand and not np.array_equal(tb.candidates, cand)):
                     raise ValueError("table= was built for other candidates")
+                if space == "pc":
+                    d_basis = self._fresh_gpu_state(tb.dtype)["d_basis"]
+                    index, cost, status = _first_guess.search_table_pc(tb, d_basis, obs, weights, offset, M, n_best, B)
 
-                def strides(a):
-                    return (1, B) if a.ndim == 2 else (1, 0)
-                index, cost = _first_guess.search_table(tb, obs, strides(obs), weights,
-                                                        strides(weights) if weights is not None else (0, 0), offset, M, n_best)
+                    def band_rows(rows):
+                        with self.candidate_table(cand, precision) as band:
+                            return _first_guess.search_table_rows(band, np.ascontiguousarray(np.broadcast_to(obs, (M, B))[rows]),
+                                                                  _first_guess.rows_of(weights, rows), offset, rows.size, n_best)
+                    self.last_routed_rows = _first_guess.route_rows(index, cost, status, band_rows)
+                else:
+                    index, cost = _first_guess.search_table_rows(tb, obs, weights, offset, M, n_best)
             finally:
                 if table is None:
                     tb.close()
         return _first_guess.gather_starts(cand, index, n_best), cost, index
 
-    def retrieve_many_multistart(self, candidates, obs, weights=None, n_starts=4, table=None, **loop_args):
+    def retrieve_many_multistart(self, candidates, obs, weights=None, n_starts=4, table=None, space="band", **loop_args):
         """``retrieve_many`` from several starts per pixel, as ``perband.retrieve_bands_multistart``: ``first_guess_many``
         with ``n_best = n_starts`` ranked with the loop's shared ``prior``, the starts clipped to ``bounds``, ONE
         ``retrieve_many`` call on the ``M n_starts`` rows (row-shaped ``obs``, ``weights`` and ``next_prior`` repeated),
         per pixel the start of lowest ``F = cost + prior term`` kept (ties to the lower start, a non-finite F loses).
         Returns ``(results, start (M,) int32, cost0 (M, n_starts))``, ``results`` exactly the tuple ``retrieve_many``
-        returns for M rows.  ``emulator_unc`` and per-row priors are not offered."""
+        returns for M rows.  ``emulator_unc`` and per-row priors are not offered.  ``space`` is ``first_guess_many``'s:
+        "pc" ranks the candidates in PC space (``table=`` must then be a ``candidate_table(space="pc")``)."""
         from . import _first_guess
         D = self.emulators[0].inputs.shape[1]
         fg = {k: loop_args[k] for k in ("is_gpu", "precision") if k in loop_args}
 
         def first_guess(prior, n_best):
-            return self.first_guess_many(candidates, obs, weights, prior, n_best, table=table, **fg)
+            return self.first_guess_many(candidates, obs, weights, prior, n_best, table=table, space=space, **fg)
         return _first_guess.multistart(first_guess, self.retrieve_many, 0, obs, weights, n_starts, D, loop_args)
 
     def retrieve_series(self, Y0, obs, weights, prior, noise, smooth=False, **loop_args):

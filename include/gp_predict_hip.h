@@ -631,6 +631,65 @@ int gp_lut_search_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t ta
 /* The kernel's geometry (no GPU needed): rows of a work item, candidates of a register tile, terms of a staged chunk. */
 int gp_lut_search_geometry(int* rows_per_item, int* candidate_tile, int* term_chunk);
 
+/* ---- look-up-table search of a multivariate emulator in PC space -----------------------------------------
+ * The spectra of a multivariate emulator are f = B^T mu (B the [n_pcs][n_bands] basis, mu the n_pcs per-PC means), so
+ * for a row with observation o and weights w (W = diag(w)) and ANY centre c0 [n_pcs]
+ *   r0 = B^T c0 - o,  J0 = 1/2 r0^T W r0,  g0 = B W r0,  G = B W B^T,  d_l = mu_l - c0
+ *   J[m][l] = a[l] + 1/2 (B^T mu_l - o)^T W (B^T mu_l - o) = a[l] + J0 + g0^T d_l + 1/2 d_l^T G d_l      (exact)
+ * With c0 the row's weighted least-squares solution g0 is zero up to rounding and every other term is >= 0: nothing
+ * cancels, and the search costs n_pcs (n_pcs + 1) / 2 + 3 n_pcs + 2 operations per (row, candidate) instead of
+ * 3 n_bands.  The (n_candidates, n_bands) spectra are never formed.
+ *
+ * gp_lut_search_pc_device: model-less; per row the n_best (1..8, <= n_candidates) candidates of lowest J into d_index
+ * [n_rows][n_best] int32 and d_cost [n_rows][n_best], with gp_lut_search_device's order, ties, empty slots (-1 / NaN),
+ * slicing (n_slices) and persistent grid (gp_launch_plan, GP_OP_LUT_SEARCH_PC).
+ *   mu, the table: element (p, l) at d_table[p * table_pstride + l * table_lstride] ((n_candidates, 1): the PC-major
+ *      array gp_predict_mean_grad_device writes for a batch).  d_offset [n_candidates] or NULL: a.
+ *   d_c0 [n_pcs][n_rows], d_j0 [n_rows], d_g0 [n_pcs][n_rows]: what gp_mv_lut_prepare_device writes (J0 and g0 must be
+ *      the misfit AT the stored c0: gp_mv_misfit_device's cost and coef with mu = c0).
+ *   G: row m's [n_pcs][n_pcs] at d_gram + m * gram_stride (elements; 0: one matrix for all rows, else >= n_pcs^2, the
+ *      convention of gp_mv_gauss_newton_rows_device); the lower triangle is read.
+ *   d_status: int32 [n_rows] or NULL; a row with a non-zero entry is skipped (nothing of it is read; empty slots).
+ * Arithmetic per (m, l), all in `dtype`, fmas:  d_p = mu_p - c0_p;  t_p = g0_p, t_p = fma(G_pq, d_q, t_p) for q < p
+ * ascending, t_p = fma(G_pp / 2, d_p, t_p);  acc = fma(t_p, d_p, acc) for p ascending from 0;  J = (a_l + J0) + acc.
+ * J does not depend on n_rows, n_candidates, the place of the row or the candidate in the call, the grid or n_slices;
+ * no atomics; two calls agree bit for bit.  A J that is NaN or +infinity is never returned.  A NaN in a candidate's
+ * means takes it out for every row; a row whose J0, g0, c0 or G holds a NaN or an infinity ends with empty slots
+ * only; every other row is bit for bit what the call without those rows gives.
+ * GP_ERR_UNSUPPORTED: n_pcs > 16 or n_best > 8.  GP_ERR_INVALID: a NULL context, table, c0, j0, g0, gram, index or
+ * cost, a bad dtype, non-positive sizes, n_candidates beyond int32, n_best < 1 or above n_candidates, a negative
+ * n_slices or stride, a gram_stride that is neither 0 nor >= n_pcs^2.
+ * Device pointers of `dtype` (d_index, d_status int32), asynchronous on the context's stream. */
+int gp_lut_search_pc_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t table_pstride, int64_t table_lstride,
+                            const void* d_offset, const void* d_c0, const void* d_j0, const void* d_g0,
+                            const void* d_gram, int64_t gram_stride, const int32_t* d_status, int32_t* d_index,
+                            void* d_cost, int64_t n_rows, int64_t n_candidates, int n_pcs, int n_best, int n_slices);
+/* The kernel's geometry for n_pcs and dtype (no GPU needed): rows of a work item, candidates of a staged tile, the
+ * padded n_pcs of the compiled instance (8, 12 or 16) and the workgroups a compute unit holds of it. */
+int gp_lut_search_pc_geometry(int dtype, int n_pcs, int* rows_per_item, int* candidate_tile, int* padded_pcs,
+                              int* workgroups_per_cu);
+
+/* gp_mv_lut_prepare_device: the set-up of the PC-space search on the context's stream, no host round trip:
+ *   1. gp_mv_misfit_device's kernel at mu = 0: its coef is -B W o, the negated right-hand side;
+ *   2. gp_mv_weight_gram_device's kernel: G per row for per-row weights (weights_stride >= n_bands, gram_stride ==
+ *      n_pcs^2: the kernel writes its matrices packed), ONE G from the one vector of weights (weights_stride 0, gram_stride 0) or from a vector of ones
+ *      (d_weights NULL, gram_stride 0) otherwise; d_gram is written;
+ *   3. lut_pc_solve_kernel: G = L L^T and c0 = G^-1 B W o by two substitutions, in double, rounded to `dtype` once on
+ *      store into d_c0 [n_pcs][n_rows]; d_status[m] = k + 1 for the first pivot k that is not finite or not above
+ *      (n_bands + n_pcs) eps G_kk (eps of `dtype`: below that a pivot of a G summed over n_bands terms in `dtype` is
+ *      not told from zero -- a row with fewer informative bands than PCs, or all masked), n_pcs + 1 for a solution
+ *      that is not finite (a NaN or an infinity in the observations under a non-zero weight), else 0; the c0 of a
+ *      row with non-zero status is NaN throughout, and so are its J0 and g0;
+ *   4. the misfit kernel at mu = c0: d_j0 [n_rows] and d_g0 [n_pcs][n_rows], evaluated at the c0 actually stored.
+ * Masked terms: the misfit kernel multiplies by w and does not select, so a NaN observation under a weight of
+ * exactly 0 would reach J0.  This entry expects d_obs to hold 0 wherever the weight is exactly 0: the Python wrapper
+ * selects that in before the upload (np.where(w == 0, 0, obs)); there is no device pass for it.
+ * obs_stride 0: one observation for all rows.  n_pcs <= 16.  Asynchronous. */
+int gp_mv_lut_prepare_device(gp_ctx* ctx, int dtype, const void* d_basis, const void* d_obs, int64_t obs_stride,
+                             const void* d_weights, int64_t weights_stride, void* d_gram, int64_t gram_stride,
+                             void* d_c0, void* d_j0, void* d_g0, int32_t* d_status, int64_t n_rows, int n_pcs,
+                             int n_bands);
+
 /* ---- training objective (next after the predict path: SURVEY.md 8f rank 2) -------------------
  * For each of n_sets hyper-parameter vectors theta [n_sets][n_inputs+2]: what
  * GaussianProcess.loglikelihood + partial_devs compute (gp_emulator/GaussianProcess.py:52-125):
@@ -671,6 +730,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_MV_GRAM 5            /* gp_mv_weight_gram_device: n_inputs is n_pcs and aux n_bands */
 #define GP_OP_VAR_GRAD 6           /* gp_predict_var_grad_device */
 #define GP_OP_LUT_SEARCH 7         /* gp_lut_search_device: n_inputs is n_terms and aux n_candidates; rest_items is n_slices */
+#define GP_OP_LUT_SEARCH_PC 8      /* gp_lut_search_pc_device: n_inputs is n_pcs and aux n_candidates; rest_items is n_slices */
 #define GP_PLAN_PREDICT_FEW 1      /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
@@ -684,6 +744,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_MV_GRAM 11         /* weight_gram_kernel: an item is 64 rows over all bands; workgroups per CU by instance */
 #define GP_PLAN_VAR_GRAD 12        /* var_grad_kernel: predict_kernel's items and grid, whatever the size of the call */
 #define GP_PLAN_LUT_SEARCH 13      /* lut_search_kernel: an item is 256 rows x one slice of the candidates */
+#define GP_PLAN_LUT_SEARCH_PC 14   /* lut_search_pc_kernel: the same items; workgroups per CU by instance (n_pcs, dtype) */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);

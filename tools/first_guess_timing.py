@@ -24,6 +24,16 @@ counters    one launch of the search per set-A shape at n_best = 8, nothing else
             vector instructions per (row, candidate, term), staging, list upkeep and epilogue included
             (--legs counters_summary --counter-dir DIR prints that per shape; no GPU).
 
+pc          space="pc" (gp_mv_lut_prepare_device + gp_lut_search_pc_device) at P = 12, K = 2101; fp64 and fp32; M in
+            {1e3, 1e5}; L in {4096, 32768}; n_best in {1, 8}; per-row and shared weights.  Every set-up stage and the
+            search by HIP events, and in the same session the band-space search of the same rows, whose kernel the PC
+            form leaves untouched (profiles/r18_pc_first_guess.txt).
+pc_multistart   MultivariateEmulator.retrieve_many_multistart host to host with both spaces (P = 12, N = 250, D = 11,
+            K = 2101, --multistart-rows rows, 4096 candidates, n_starts 4, max_iter 20).
+pc_counters one prepared launch of the PC-space search per pc shape at n_best = 8, for a counter run of its own
+            (rocprofv3 --pmc SQ_INSTS_VALU ... -- python tools/first_guess_timing.py --legs pc_counters;
+            --legs pc_counters_summary --counter-dir DIR prints executed vector instructions per (row, candidate)).
+
 Every leg that touches the GPU runs under the caller's time limit, e.g.
     timeout -k 10 500 python tools/first_guess_timing.py --legs search --out profiles/r17_first_guess.txt
 """
@@ -168,6 +178,138 @@ def leg_multistart(a):
              rows_below_1e_12=int(np.sum(res[1] < 1e-12)), started_from_rank=np.bincount(start, minlength=n).tolist())
 
 
+SET_PC = [(dt, M, L, nb, per_row) for dt in (np.float64, np.float32) for M in (1000, 100_000) for L in (4096, 32768)
+          for nb in (1, 8) for per_row in (True, False)]
+
+
+def timed(ctx, call, reps, warm):
+    """Median and minimum device time in ms of ``call`` by HIP events."""
+    for _ in range(warm):
+        call()
+    ctx.synchronize()
+    e0, e1 = ctx.event(), ctx.event()
+    ts = []
+    for _ in range(reps):
+        ctx.record(e0)
+        call()
+        ctx.record(e1)
+        ctx.synchronize()
+        ts.append(ctx.elapsed_ms(e0, e1))
+    ctx.event_destroy(e0), ctx.event_destroy(e1)
+    return round(float(np.median(ts)), 4), round(min(ts), 4)
+
+
+def leg_pc(a, ctx, counters=False):
+    """space="pc" at P = 12, K = 2101: every stage of the set-up (the misfit kernel at mu = 0, the Gram kernel, the
+    misfit kernel at c0 through their own entries; gp_mv_lut_prepare_device whole, the solve kernel by difference) and
+    the search by HIP events, and in the same session the band-space search of the same rows against the (L, K)
+    spectra, whose kernel is the parent's."""
+    P, K, Mx, Lx = 12, 2101, 100_000, 32768
+    cu = ctx.device_info()["compute_units"]
+    rs = np.random.RandomState(4)
+    basis = rs.standard_normal((P, K)) / np.sqrt(K)
+    for dt in (np.float64, np.float32):
+        isz = np.dtype(dt).itemsize
+        held = []
+
+        def up(x):
+            held.append(ctx.to_device(np.ascontiguousarray(x, dtype=dt)))
+            return held[-1]
+
+        def alloc(n):
+            held.append(ctx.malloc(n))
+            return held[-1]
+        try:
+            mu = rs.uniform(-1.0, 1.0, (P, Lx))
+            d_basis, d_mu = up(basis), up(mu)
+            near = rs.randint(0, Lx, Mx)
+            d_obs = up((mu[:, near].T + 0.05 * rs.standard_normal((Mx, P))) @ basis + 0.01 / np.sqrt(K) * rs.standard_normal((Mx, K)))
+            d_w = up(0.5 + rs.random_sample((Mx, K)))
+            d_spec = alloc(Lx * K * isz)
+            ctx.reconstruct_device(dt, d_basis, d_mu, d_spec, Lx, P, K)           # (L, K) spectra for the band search
+            d_G, d_c0, d_j0, d_g0, d_st = alloc(Mx * P * P * isz), alloc(P * Mx * isz), alloc(Mx * isz), alloc(P * Mx * isz), alloc(Mx * 4)
+            d_i, d_c = alloc(Mx * 8 * 4), alloc(Mx * 8 * isz)
+            for (dt2, M, L, nb, per_row) in SET_PC:
+                if dt2 != dt or (counters and nb != 8):
+                    continue
+                ws, gs = (K, P * P) if per_row else (0, 0)
+
+                def prepare():
+                    ctx.mv_lut_prepare_device(dt, d_basis, d_obs, K, d_w, ws, d_G, gs, d_c0, d_j0, d_g0, d_st, M, P, K)
+
+                def search():                                  # the table is a prefix of every PC's Lx means
+                    ctx.lut_search_pc_device(dt, d_mu, (Lx, 1), None, d_c0, d_j0, d_g0, d_G, gs, d_st, d_i, d_c, M, L, P, nb)
+
+                def band():
+                    ctx.lut_search_device(dt, d_spec, (1, K), None, d_obs, (1, K), d_w, (1, ws), d_i, d_c, M, L, K, nb)
+                prepare()
+                if counters:
+                    search()
+                    ctx.synchronize()
+                    emit(a, leg="pc_counters", dtype=np.dtype(dt).name, P=P, M=M, L=L, n_best=nb, per_row_weights=per_row,
+                         row_candidates=M * L)
+                    continue
+                reps, warm = a.reps, a.warmup
+                t_prep = timed(ctx, prepare, reps, warm)
+                t_m0 = timed(ctx, lambda: ctx.mv_misfit_device(dt, d_basis, d_c0, None, d_obs, K, d_w, ws, None, d_g0, None, M, P, K, 1),
+                             reps, warm)
+                t_gram = timed(ctx, lambda: ctx.mv_weight_gram_device(dt, d_basis, d_w, ws, d_G, M if per_row else 1, P, K), reps, warm)
+                prepare()
+                t_m1 = timed(ctx, lambda: ctx.mv_misfit_device(dt, d_basis, d_c0, None, d_obs, K, d_w, ws, d_j0, d_g0, None, M, P, K, 1),
+                             reps, warm)
+                prepare()
+                t_search = timed(ctx, search, reps, warm)
+                bad = int(np.count_nonzero(np.array(ctx.to_host(d_st, (M,), np.int32))))
+                t_band = timed(ctx, band, 2 if M * L > 1e9 else reps, 1)
+                plan = _lib.launch_plan("lut_search_pc", dt, M, n_pcs=P, n_candidates=L, compute_units=cu)
+                total = t_prep[0] + t_search[0]
+                emit(a, leg="pc", dtype=np.dtype(dt).name, P=P, K=K, M=M, L=L, n_best=nb, per_row_weights=per_row,
+                     prepare_ms=t_prep[0], misfit_at_0_ms=t_m0[0], gram_ms=t_gram[0], misfit_at_c0_ms=t_m1[0],
+                     solve_ms_by_difference=round(t_prep[0] - t_m0[0] - t_gram[0] - t_m1[0], 4), search_ms=t_search[0],
+                     search_min_ms=t_search[1], total_ms=round(total, 4), band_ms=t_band[0], band_min_ms=t_band[1],
+                     band_over_pc=round(t_band[0] / total, 2), rows_not_centred=bad, slices=plan["slices"],
+                     items=plan["items"], workgroups=plan["workgroups"], reps=reps, compute_units=cu)
+        finally:
+            ctx.synchronize()
+            for p in held:
+                ctx.free(p)
+
+
+def leg_pc_multistart(a):
+    """retrieve_many_multistart host to host with both spaces on a synthetic MultivariateEmulator of the shipped shape
+    (P = 12, N = 250, D = 11, K = 2101), 1e5 rows, 4096 candidates, per-row weights, n_starts 4, max_iter 20."""
+    from oracle import gp_oracle
+    from gp_emulator_amd import GaussianProcess
+    from gp_emulator_amd.multivariate_gp import MultivariateEmulator
+    P, N, D, K, M, L = 12, 250, 11, 2101, a.multistart_rows, 4096
+    mv = MultivariateEmulator.__new__(MultivariateEmulator)
+    inputs, x_true, theta, invQ, invQt = gp_oracle.benchmark_inputs(4242, N, D, M)
+    mv.emulators = []
+    for p in range(P):
+        if p:
+            _, _, theta, invQ, invQt = gp_oracle.benchmark_inputs(4242 + p, N, D, 1)
+        gp = GaussianProcess(inputs, [])
+        gp.theta, gp.invQ, gp.invQt = theta, invQ, invQt
+        mv.emulators.append(gp)
+    mv.n_pcs = P
+    rs = np.random.RandomState(5)
+    mv.basis_functions = rs.standard_normal((P, K))
+    cand = rs.random_sample((L, D))
+    obs = mv.predict_many(x_true, is_gpu=True)
+    w = (0.5 + rs.random_sample((M, K))) / K
+    bounds = (np.zeros(D), np.ones(D))
+    for space in ("band", "pc", "band", "pc"):                 # (the first pair warms both paths)
+        t0 = time.perf_counter()
+        fg = mv.first_guess_many(cand, obs, w, n_best=4, space=space)
+        t1 = time.perf_counter()
+        res, start, _ = mv.retrieve_many_multistart(cand, obs, w, n_starts=4, space=space, bounds=bounds, max_iter=20)
+        t2 = time.perf_counter()
+        emit(a, leg="pc_multistart", space=space, P=P, N=N, D=D, K=K, M=M, L=L, n_starts=4, first_guess_s=round(t1 - t0, 4),
+             whole_s=round(t2 - t1, 4), index_checksum=int(np.sum(fg[2].astype(np.int64))),
+             started_from_rank=np.bincount(start, minlength=4).tolist())
+    mv.release_gpu()
+
+
 def leg_counters_summary(a):
     """SQ_INSTS_VALU of every lut_search_kernel dispatch under --counter-dir, in dispatch order, against the shapes the
     counters leg launched in that order."""
@@ -189,8 +331,28 @@ def leg_counters_summary(a):
         emit(a, leg="counters", note="dispatches found %d, shapes %d" % (len(rows), len(shapes)))
 
 
+def leg_pc_counters_summary(a):
+    """SQ_INSTS_VALU of every lut_search_pc_kernel dispatch under --counter-dir, in dispatch order, against the shapes
+    the pc_counters leg launched in that order: executed vector instructions per (row, candidate)."""
+    import csv
+    import glob
+    shapes = [s for dt in (np.float64, np.float32) for s in SET_PC if s[0] == dt and s[3] == 8]
+    rows = []
+    for f in glob.glob(os.path.join(a.counter_dir, "**", "*counter_collection.csv"), recursive=True):
+        for r in csv.DictReader(open(f)):
+            if "lut_search_pc_kernel" in r["Kernel_Name"] and r["Counter_Name"] == "SQ_INSTS_VALU":
+                rows.append((int(r["Dispatch_Id"]), float(r["Counter_Value"])))
+    rows.sort()
+    for (dt, M, L, nb, per_row), (_, valu) in zip(shapes, rows):
+        emit(a, leg="pc_counters", dtype=np.dtype(dt).name, P=12, M=M, L=L, n_best=nb, per_row_weights=per_row,
+             sq_insts_valu=valu, valu_per_row_candidate=round(valu * 64.0 / (float(M) * L), 2))
+    if len(rows) != len(shapes):
+        emit(a, leg="pc_counters", note="dispatches found %d, shapes %d" % (len(rows), len(shapes)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--multistart-rows", type=int, default=100_000, help="pc_multistart: the rows of the retrieval")
     ap.add_argument("--legs", default="search,numpy,multistart")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
@@ -202,6 +364,8 @@ def main():
     legs = a.legs.split(",")
     if "counters_summary" in legs:
         return leg_counters_summary(a)
+    if "pc_counters_summary" in legs:
+        return leg_pc_counters_summary(a)
     if "numpy" in legs:
         leg_numpy(a)
     if "search" in legs or "counters" in legs:
@@ -212,6 +376,14 @@ def main():
             leg_search(a, ctx, counters=True)
     if "multistart" in legs:
         leg_multistart(a)
+    if "pc" in legs or "pc_counters" in legs:
+        ctx = _lib.default_context(0)
+        if "pc" in legs:
+            leg_pc(a, ctx)
+        if "pc_counters" in legs:
+            leg_pc(a, ctx, counters=True)
+    if "pc_multistart" in legs:
+        leg_pc_multistart(a)
 
 
 if __name__ == "__main__":
