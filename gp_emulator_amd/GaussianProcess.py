@@ -394,3 +394,16 @@ class GaussianProcess:
             aa = np.asarray(self.inputs)[:, d][:, None] - testing[:, d][None, :]
             dvar[:, d] = -expX[d] * np.sum(W * aa, axis=0)
         return var, dvar
+
+    # ------------------------------------------------------------------ global sensitivity
+    def sobol_indices(self, bounds, is_gpu=False):
+        """Variance-based (Sobol) sensitivity indices of the posterior mean for independent uniform inputs on the box
+        ``bounds = (lo, hi)``, each (D,) -- or (n_boxes, D) for several boxes, which gives every result a leading
+        ``n_boxes`` axis.  ``SobolIndices(first (D,), total (D,), variance, mean)``: ``first[i] = Var(E[mu | t_i]) / V``,
+        ``total[i] = 1 - Var(E[mu | t_~i]) / V``, ``V = Var(mu)`` and ``E[mu]``, all in closed form (``_sobol_numpy``); NaN
+        indices where ``V <= 0``.  ``is_gpu=True`` runs the HIP kernels (``gp_sobol_batch_f64``, float64 only) and never
+        falls back; ``is_gpu=False`` is the explicit numpy branch.  Not in the reference."""
+        from . import perband
+        r = perband.sobol_bands([self], bounds, is_gpu=is_gpu)
+        boxed = np.ndim(bounds[0]) == 2
+        return r._replace(**{k: (v[:, 0] if boxed else v[0]) for k, v in r._asdict().items()})

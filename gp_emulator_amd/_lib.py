@@ -16,6 +16,7 @@ from ._dense_numpy import (DAMPINGS, newton_step_numpy, posterior_cov_numpy, pre
                            prior_rows, row_strides, rts_smooth_numpy, _cholesky_inverse_numpy, _mirror_lower)
 from ._lut_numpy import MAX_PCS as lut_pc_max_pcs  # noqa: F401
 from ._lut_numpy import lut_pc_prepare_numpy, lut_search_numpy, lut_search_pc_numpy  # noqa: F401
+from ._sobol_numpy import bounds_arrays as _sobol_bounds
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_PREDICT_LIB lets tools/ab_bench.py time differently-built variants of the library on
@@ -117,6 +118,8 @@ SIGNATURES = {
     "gp_frag_index": (c_int, [c_int, c_int, c_int, c_int]),
     "gp_likelihood_batch_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gp_sobol_batch_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_void_p, c_void_p]),
     "gp_pack_sizes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                               ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "gp_launch_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_int),
@@ -788,6 +791,35 @@ class Context:
             _ptr(invQt) if want_inverse else None), "gp_likelihood_batch_f64")
         return (cost, grad, invQ, invQt) if want_inverse else (cost, grad)
 
+    def sobol_batch(self, expX, inputs, invQt, lo, hi, pairs=None):
+        """``(mean, cov)`` of ``gp_sobol_batch_f64``: for E emulators on shared ``inputs`` (N, D) with ``expX`` (E, D + 2)
+        and ``invQt`` (E, N), inputs uniform on the box ``lo``, ``hi`` ((D,), or (n_boxes, D) for several boxes), the
+        means (E,) and for every pair of ``pairs`` (P, 2) -- default: (e, e) of every emulator -- the row
+        ``[V, Vm^1..D, Vt^1..D]`` of cov (P, 1 + 2D); with 2-D bounds both carry a leading ``n_boxes`` axis.  float64
+        only.  ``_sobol_numpy.sobol_pairs_numpy`` is the numpy branch and ``_sobol_numpy.indices`` turns cov into the
+        indices."""
+        expX = np.ascontiguousarray(np.atleast_2d(expX), dtype=np.float64)
+        inputs = np.ascontiguousarray(inputs, dtype=np.float64)
+        invQt = np.ascontiguousarray(np.atleast_2d(invQt), dtype=np.float64)
+        if inputs.ndim != 2:
+            raise ValueError("inputs must be (n_train, n_inputs)")
+        (N, D), E = inputs.shape, expX.shape[0]
+        if expX.shape != (E, D + 2):
+            raise ValueError("expX must be (n_emulators, n_inputs + 2), got %s" % (expX.shape,))
+        if invQt.shape != (E, N):
+            raise ValueError("invQt must be (n_emulators, n_train), got %s" % (invQt.shape,))
+        lo, hi, boxed = _sobol_bounds(lo, hi, D)
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+            if pairs.ndim != 2 or pairs.shape[1] != 2:
+                raise ValueError("pairs must be (n_pairs, 2)")
+        B, P = lo.shape[0], E if pairs is None else pairs.shape[0]
+        mean, cov = np.empty((B, E)), np.empty((B, P, 1 + 2 * D))
+        check(self.lib.gp_sobol_batch_f64(self.h, E, _ptr(expX), _ptr(inputs), _ptr(invQt), N, D, B, _ptr(lo), _ptr(hi), P,
+                                          None if pairs is None else _ptr(pairs), _ptr(mean), _ptr(cov)),
+              "gp_sobol_batch_f64")
+        return (mean, cov) if boxed else (mean[0], cov[0])
+
     # ---- events -----------------------------------------------------------------
     def event(self):
         e = c_void_p()
@@ -1193,12 +1225,13 @@ class BatchModel(Model):
 GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_VAR_GRAD = 0, 1, 2, 3, 4, 5, 6
 GP_OP_LUT_SEARCH = 7
 GP_OP_LUT_SEARCH_PC = 8
+GP_OP_SOBOL = 9
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
                 6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
-                10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search", 14: "lut_search_pc"}
+                10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search", 14: "lut_search_pc", 15: "sobol"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
              "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM, "var_grad": GP_OP_VAR_GRAD,
-             "lut_search": GP_OP_LUT_SEARCH, "lut_search_pc": GP_OP_LUT_SEARCH_PC}
+             "lut_search": GP_OP_LUT_SEARCH, "lut_search_pc": GP_OP_LUT_SEARCH_PC, "sobol": GP_OP_SOBOL}
 
 
 def lut_search_geometry():
@@ -1232,7 +1265,9 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
     "lut_search" takes ``n_terms`` and ``n_candidates``: an item is ``rows_per_item`` rows against one slice of the
     candidates, and the dict also holds ``slices`` (the slices chosen: items = row tiles x slices), ``candidate_tile``
     and ``term_chunk`` (``lut_search_geometry``).  "lut_search_pc" takes ``n_pcs`` and ``n_candidates``: the same
-    items and slices, with ``candidate_tile``, ``padded_pcs`` and ``workgroups_per_cu`` (``lut_search_pc_geometry``)."""
+    items and slices, with ``candidate_tile``, ``padded_pcs`` and ``workgroups_per_cu`` (``lut_search_pc_geometry``).
+    "sobol" takes ``n_rows`` boxes, ``n_emulators`` pairs, ``n_train`` and ``n_inputs``: an item is ``rows_per_item``
+    training rows of one (box, pair)."""
     code = _PLAN_OPS[op]
     recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_LUT_SEARCH, GP_OP_LUT_SEARCH_PC)
     if code == GP_OP_LUT_SEARCH:

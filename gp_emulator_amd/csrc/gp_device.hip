@@ -337,6 +337,14 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     rpi = gpk::lkRows;
     g = lp.grid;
     rest.items = lp.n_slices;
+  } else if (op == GP_OP_SOBOL) {
+    // (n_emulators = n_pairs here; n_rows = n_boxes)
+    if (n_train <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    if (n_inputs > gpk::skMaxD || n_train > gpk::skMaxN)
+      return fail(GP_ERR_UNSUPPORTED, "the Sobol kernels serve n_train <= %d, n_inputs <= %d", gpk::skMaxN, gpk::skMaxD);
+    k = GP_PLAN_SOBOL;
+    rpi = gpk::skRows;
+    g = gpk::plan_sobol(n_rows, n_emulators, n_train, gpk::sobol_cap(compute_units, n_inputs));
   } else if (op == GP_OP_VAR_GRAD) {
     int kd, knb;
     int rc = pick_kernel(n_train, n_inputs, &kd, &knb);

@@ -149,4 +149,18 @@ inline LutPlan plan_lut_search_pc(long long n_rows, long long n_candidates, int 
   return plan_lut_search(n_rows, n_candidates, rows_per_item, cand_tile, cap, forced);
 }
 
+// sobol_pair_kernel: items = (box, pair, block of skRows training rows), j-block fastest; plan_grid with the
+// (box, pair) count as its batch.  The instance is the padded n_inputs (8, 12 or 16: what the per-lane registers are
+// sized for); every instance takes more than 256 VGPRs, so a CU holds one 4-wave workgroup of it.
+constexpr int skRows = 16, skThreads = 256;
+constexpr int skMaxN = 512, skMaxD = 16;      // (a lane owns at most two columns; 16 D <= 256 threads form c^p)
+constexpr int sobol_padded(int n_inputs) { return n_inputs <= 8 ? 8 : n_inputs <= 12 ? 12 : 16; }
+constexpr int sobol_wgs_per_cu(int /*padded_inputs*/) { return 1; }
+inline long long sobol_cap(int compute_units, int n_inputs) {
+  return (long long)compute_units * sobol_wgs_per_cu(sobol_padded(n_inputs));
+}
+inline GridPlan plan_sobol(long long n_boxes, long long n_pairs, int n_train, long long cap) {
+  return plan_grid(n_train, skRows, n_boxes * n_pairs, cap);
+}
+
 }  // namespace gpk

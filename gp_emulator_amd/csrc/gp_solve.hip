@@ -1,6 +1,6 @@
 // The small dense solves on device buffers: damped Newton step, LM update, posterior covariance, prior propagation and
 // the smoother's backward step; and the look-up-table search that starts a retrieval.  Device arrays in, device arrays
-// out, no model.
+// out, no model.  The Sobol indices of a batch of emulators, on host arrays (no model either).
 #include "gp_host.hpp"
 
 #include "gp_launch_plan.hpp"
@@ -11,6 +11,7 @@
 #include "gp_posterior_cov_kernel.hpp"
 #include "gp_prior_propagate_kernel.hpp"
 #include "gp_rts_smooth_kernel.hpp"
+#include "gp_sobol_args.hpp"
 
 // what a launcher returned, as the entry's status
 static int launched(hipError_t e, const char* kernel) {
@@ -346,6 +347,59 @@ int gp_lut_search_pc_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t
     a.P = n_pcs, a.n_best = n_best, a.n_slices = plan.n_slices;
     return launched(gpk::launch_lut_search_pc<T>(a, plan.grid.workgroups, ctx->stream), "lut search pc");
   });
+}
+
+int gp_sobol_batch_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs, const double* invQt,
+                       int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi, int n_pairs,
+                       const int32_t* pairs, double* mean, double* cov) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!expX || !inputs || !invQt || !lo || !hi || !mean || !cov) return fail(GP_ERR_INVALID, "null pointer");
+  if (n_emulators <= 0 || n_train <= 0 || n_inputs <= 0 || n_boxes <= 0 || n_pairs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_inputs > gpk::skMaxD || n_train > gpk::skMaxN)
+    return fail(GP_ERR_UNSUPPORTED, "the Sobol kernels serve n_train <= %d, n_inputs <= %d", gpk::skMaxN, gpk::skMaxD);
+  if (!pairs && n_pairs != n_emulators) return fail(GP_ERR_INVALID, "without a pair list n_pairs is n_emulators");
+  if (pairs)
+    for (size_t k = 0; k < 2 * (size_t)n_pairs; ++k)
+      if (pairs[k] < 0 || pairs[k] >= n_emulators)
+        return fail(GP_ERR_INVALID, "pair %lld names emulator %d of %d", (long long)(k / 2), pairs[k], n_emulators);
+  for (size_t k = 0; k < (size_t)n_boxes * n_inputs; ++k)
+    if (!(hi[k] > lo[k]) || !(hi[k] - lo[k] <= 1.79769313486231570815e308) || !(lo[k] >= -1.79769313486231570815e308))
+      return fail(GP_ERR_INVALID, "box %lld, input %lld: the bounds must be finite with hi > lo", (long long)(k / n_inputs),
+                  (long long)(k % n_inputs));
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t E = (size_t)n_emulators, N = (size_t)n_train, D = (size_t)n_inputs, B = (size_t)n_boxes, P = (size_t)n_pairs;
+  const size_t K = 1 + 2 * D, JB = (N + gpk::skRows - 1) / gpk::skRows;
+  const gpk::GridPlan plan = gpk::plan_sobol(n_boxes, n_pairs, n_train, gpk::sobol_cap(ctx->compute_units, n_inputs));
+  const size_t n_theta = E * (D + 2), n_in = N * D, n_al = E * N, n_box = B * D, n_part = B * P * JB * K, n_mean = B * E,
+               n_cov = B * P * K, n_pair = pairs ? P : 0;      // (the pairs last: two int32 per double)
+  if (int rc = ensure_scratch(ctx, sizeof(double) * (n_theta + n_in + n_al + 2 * n_box + n_part + n_mean + n_cov + n_pair)))
+    return rc;
+  double* d_theta = (double*)ctx->scratch;
+  double* d_in = d_theta + n_theta;
+  double* d_al = d_in + n_in;
+  double* d_lo = d_al + n_al;
+  double* d_hi = d_lo + n_box;
+  double* d_part = d_hi + n_box;
+  double* d_mean = d_part + n_part;
+  double* d_cov = d_mean + n_mean;
+  int* d_pairs = pairs ? (int*)(d_cov + n_cov) : nullptr;
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(d_theta, expX, sizeof(double) * n_theta, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_in, inputs, sizeof(double) * n_in, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_al, invQt, sizeof(double) * n_al, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_lo, lo, sizeof(double) * n_box, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_hi, hi, sizeof(double) * n_box, hipMemcpyHostToDevice, st));
+  if (pairs) HIP_TRY(hipMemcpyAsync(d_pairs, pairs, sizeof(int32_t) * 2 * P, hipMemcpyHostToDevice, st));
+  gpk::SobolArgs a;
+  a.expX = d_theta, a.inputs = d_in, a.alpha = d_al, a.lo = d_lo, a.hi = d_hi, a.pairs = d_pairs;
+  a.part = d_part, a.mean = d_mean, a.cov = d_cov;
+  a.N = n_train, a.D = n_inputs, a.E = n_emulators, a.B = n_boxes, a.P = n_pairs, a.JB = (int)JB;
+  a.items = plan.items;
+  if (int rc = launched(gpk::launch_sobol(a, plan.workgroups, st), "sobol")) return rc;
+  HIP_TRY(hipMemcpyAsync(mean, d_mean, sizeof(double) * n_mean, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(cov, d_cov, sizeof(double) * n_cov, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GP_OK;
 }
 
 }  // extern "C"

@@ -880,6 +880,21 @@ class MultivariateEmulator(object):
         return _retrieve.retrieve_series(self.retrieve_many, Y0, obs, weights, prior, noise, smooth=True, context=context,
                                          **loop_args)
 
+    # ---- global sensitivity ---------------------------------------------------------------------
+    def sobol(self, bounds, is_gpu=True):
+        """Sobol sensitivity indices of every band of the reconstructed output ``f_k = sum_p basis[p, k] mu_p`` for
+        independent uniform inputs on ``bounds = (lo, hi)``, each (D,) or (n_boxes, D): ``SobolIndices(first
+        (D, N_full), total (D, N_full), variance (N_full,), mean (N_full,))``, with a leading ``n_boxes`` axis for 2-D
+        bounds.  The covariances of all ``P (P + 1) / 2`` pairs of PCs come from one ``gp_sobol_batch_f64`` call
+        (``is_gpu=False``: the numpy branch), mirrored into (P, P) matrices; a band's indices are the quadratic forms
+        ``beta_k' Vm^i beta_k / beta_k' V beta_k`` with ``beta_k = basis[:, k]``.  Nothing of size ``N_full`` is
+        emulated.  Not in the reference."""
+        from . import _sobol_numpy, perband
+        P = self.n_pcs
+        mean, cov = perband.sobol_pairs(*perband._sobol_constants(self.emulators), bounds,
+                                        pairs=_sobol_numpy.upper_pairs(P), is_gpu=is_gpu)
+        return _sobol_numpy.spectral(np.asarray(self.basis_functions)[:P], mean, _sobol_numpy.mirror(cov, P))
+
     # ---- second derivatives ---------------------------------------------------------------------
     def hessian(self, y, is_gpu=False, weights=None):
         """Hessian of the reconstructed output at ONE input vector ``y``: ``(N_params, N_params, N_full)`` (axes

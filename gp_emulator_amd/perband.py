@@ -8,7 +8,7 @@ of the fused kernel (BASELINE config 3: 2101 bands x N_train=250 x D=11, shared 
 """
 import numpy as np
 
-from . import _first_guess, _lib, _retrieve, multi_gpu
+from . import _first_guess, _lib, _retrieve, _sobol_numpy, multi_gpu
 from ._retrieve import LAMBDA_MAX, LAMBDA_MIN, _lm_update_numpy, _prior_term     # noqa: F401  (their names here)
 from .perband_train import (learn_bands, _driver_probe, _lockstep_driver, _lockstep_processes,     # noqa: F401  (training
                             _Population, _probe_setulb, _worker_main)                              # many bands at once)
@@ -123,6 +123,32 @@ def variance_gradient_bands(gps, X, precision=np.float64, device=None):
     Arrays of ``precision``; emulator e bit for bit what ``Model.predict_var_grad`` of it gives."""
     with make_batch(gps, precision, device) as batch:
         return batch.predict_var_grad(np.asarray(X))
+
+
+def _sobol_constants(gps):
+    """expX (E, D + 2), the shared inputs and invQt (E, N) of the emulators, float64."""
+    inputs = np.asarray(_check_shared_inputs(gps), dtype=np.float64)
+    return (np.stack([np.exp(np.asarray(gp.theta, dtype=np.float64)) for gp in gps]), inputs,
+            np.stack([np.asarray(gp.invQt, dtype=np.float64).reshape(inputs.shape[0]) for gp in gps]))
+
+
+def sobol_pairs(expX, inputs, invQt, bounds, pairs=None, is_gpu=True, device=None):
+    """``(mean, cov)`` of ``Context.sobol_batch`` on the default context of ``device``, or with ``is_gpu=False`` of its
+    numpy branch ``_sobol_numpy.sobol_pairs_numpy``."""
+    if is_gpu:
+        return _lib.default_context(device).sobol_batch(expX, inputs, invQt, bounds[0], bounds[1], pairs)
+    return _sobol_numpy.sobol_pairs_numpy(expX, inputs, invQt, bounds[0], bounds[1], pairs)
+
+
+def sobol_bands(gps, bounds, is_gpu=True, device=None):
+    """Sobol sensitivity indices of the E emulators in ``gps`` (shared training inputs) for independent uniform inputs
+    on ``bounds = (lo, hi)``, each (D,) or (n_boxes, D): ``SobolIndices(first (E, D), total (E, D), variance (E,),
+    mean (E,))`` -- which inputs drive which band, over which prior range -- with a leading ``n_boxes`` axis for 2-D
+    bounds.  One call of ``gp_sobol_batch_f64`` (float64 only) for all bands and boxes; ``is_gpu=False`` is the numpy
+    branch.  See ``GaussianProcess.sobol_indices``."""
+    mean, cov = sobol_pairs(*_sobol_constants(gps), bounds, is_gpu=is_gpu, device=device)
+    first, total, variance = _sobol_numpy.indices(cov)
+    return _sobol_numpy.SobolIndices(first, total, variance, mean)
 
 
 def hessian_bands(gps, testing, precision=np.float64, weights=None, device=None, devices=None, hessian_fn=None):

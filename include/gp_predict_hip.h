@@ -701,6 +701,25 @@ int gp_likelihood_batch_f64(gp_ctx* ctx, int n_sets, const double* theta, const 
                             const double* targets, int targets_shared, int n_train, int n_inputs,
                             double* cost, double* grad, double* invQ, double* invQt);
 
+/* ---- Sobol sensitivity indices of the posterior mean, closed form ----------------------------------
+ * n_emulators emulators on shared training inputs [n_train][n_inputs], expX [n_emulators][n_inputs+2] (e_1..e_D, b,
+ * nugget) and invQt [n_emulators][n_train]; the inputs t_d independent and uniform on [lo_d, hi_d], n_boxes boxes
+ * lo, hi [n_boxes][n_inputs].  For every box and every pair (p, q) of pairs [n_pairs][2] (NULL: the pairs (e, e) of
+ * every emulator, n_pairs = n_emulators) cov [n_boxes][n_pairs][1 + 2 n_inputs] holds
+ *     V = Cov(mu_p, mu_q),   Vm^i = Cov(E[mu_p | t_i], E[mu_q | t_i]),   Vt^i = V - Cov(E[mu_p | t_~i], E[mu_q | t_~i])
+ * for i = 1..n_inputs (V, Vm^1.., Vt^1..), and mean [n_boxes][n_emulators] the means E[mu_e].  For p = q the
+ * first-order and total indices are Vm^i / V and Vt^i / V.  Every term is a product of one-dimensional Gaussian
+ * integrals (exp, erf, erfc of the device library); the mean is subtracted term by term.  No atomics: a (box, pair)
+ * result is bit for bit the same alone or in any batch, in any pair order, on any grid (gp_launch_plan,
+ * GP_OP_SOBOL).  An emulator with a non-finite expX or invQt entry gives NaN in its mean and in every pair it is part
+ * of and changes no other result.
+ * GP_ERR_INVALID: a NULL argument, non-positive sizes, a pair index outside 0..n_emulators-1, n_pairs != n_emulators
+ * with pairs NULL, a bound that is not finite or hi <= lo.  GP_ERR_UNSUPPORTED: n_inputs > 16 or n_train > 512.
+ * Nothing is written on an error.  Host pointers, fp64 only, synchronous. */
+int gp_sobol_batch_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs, const double* invQt,
+                       int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi, int n_pairs,
+                       const int32_t* pairs, double* mean, double* cov);
+
 /* Host-side packing only (no GPU needed): what gp_model_create_* uploads.  xa and frags
  * are sized by gp_pack_sizes; sd takes 2*kernel_d + 1 reals (sqrt(e_d), the centre c_d, b);
  * used by the CPU tests to check the fragment layout. */
@@ -731,6 +750,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_VAR_GRAD 6           /* gp_predict_var_grad_device */
 #define GP_OP_LUT_SEARCH 7         /* gp_lut_search_device: n_inputs is n_terms and aux n_candidates; rest_items is n_slices */
 #define GP_OP_LUT_SEARCH_PC 8      /* gp_lut_search_pc_device: n_inputs is n_pcs and aux n_candidates; rest_items is n_slices */
+#define GP_OP_SOBOL 9              /* gp_sobol_batch_f64: n_emulators is n_pairs and n_rows n_boxes; an item is 16 training rows */
 #define GP_PLAN_PREDICT_FEW 1      /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
@@ -745,6 +765,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_VAR_GRAD 12        /* var_grad_kernel: predict_kernel's items and grid, whatever the size of the call */
 #define GP_PLAN_LUT_SEARCH 13      /* lut_search_kernel: an item is 256 rows x one slice of the candidates */
 #define GP_PLAN_LUT_SEARCH_PC 14   /* lut_search_pc_kernel: the same items; workgroups per CU by instance (n_pcs, dtype) */
+#define GP_PLAN_SOBOL 15           /* sobol_pair_kernel: items = n_boxes x n_pairs x ceil(n_train / 16); one workgroup per CU */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
