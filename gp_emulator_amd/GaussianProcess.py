@@ -407,3 +407,24 @@ class GaussianProcess:
         r = perband.sobol_bands([self], bounds, is_gpu=is_gpu)
         boxed = np.ndim(bounds[0]) == 2
         return r._replace(**{k: (v[:, 0] if boxed else v[0]) for k, v in r._asdict().items()})
+
+    # ------------------------------------------------------------------ Gaussian input uncertainty
+    def predict_uncertain(self, X, cov, is_gpu=False):
+        """Predict at uncertain inputs ``x_m ~ N(X[m], cov[m])`` -- ``X`` (M, D), ``cov`` (D, D) or (M, D, D), positive
+        semi-definite (an input may be held fixed: a zero row and column; ``cov = 0`` is ``predict``) -- by exact
+        moment matching: ``UncertainPrediction(mean (M,), var_state (M,), var_emulator (M,), expected_grad (M, D),
+        info (M,))`` with ``mean = E[mu(x)]``, ``var_state = Var[mu(x)]``, ``var_emulator = E[v(x)]`` (their sum is
+        the total predictive variance; NaN without ``invQ``) and ``expected_grad = E[d mu / dx]``, so that
+        ``Cov[x, mu] = cov @ expected_grad``.  Closed form for the squared-exponential kernel (``_moments_numpy``), no
+        sampling, and accurate as ``cov -> 0``.  ``info[m]`` is nonzero and the row NaN where ``cov[m]`` is not positive
+        semi-definite (k + 1: pivot k) or the row is not finite (-1).  ``is_gpu=True`` runs the HIP kernels
+        (``gp_moments_batch_f64``, float64 only) and never falls back; ``is_gpu=False`` is the explicit numpy branch::
+
+            x, *_, cov, sigma, status = perband.retrieve_bands(gps, X0, obs, return_cov=True)
+            p = gp.predict_uncertain(x, cov)          # the band this emulator models, given the retrieved states
+
+        Not in the reference."""
+        from . import perband
+        r = perband.predict_uncertain_bands([self], X, cov, is_gpu=is_gpu)
+        return r._replace(mean=r.mean[0], var_state=r.var_state[0], var_emulator=r.var_emulator[0],
+                          expected_grad=r.expected_grad[0])

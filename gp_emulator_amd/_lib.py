@@ -16,6 +16,7 @@ from ._dense_numpy import (DAMPINGS, newton_step_numpy, posterior_cov_numpy, pre
                            prior_rows, row_strides, rts_smooth_numpy, _cholesky_inverse_numpy, _mirror_lower)
 from ._lut_numpy import MAX_PCS as lut_pc_max_pcs  # noqa: F401
 from ._lut_numpy import lut_pc_prepare_numpy, lut_search_numpy, lut_search_pc_numpy  # noqa: F401
+from ._moments_numpy import rows_arrays as _moments_rows
 from ._sobol_numpy import bounds_arrays as _sobol_bounds
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -120,6 +121,8 @@ SIGNATURES = {
                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gp_sobol_batch_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p, c_void_p]),
+    "gp_moments_batch_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_void_p,
+                                     c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gp_pack_sizes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
                               ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "gp_launch_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_int),
@@ -820,6 +823,44 @@ class Context:
               "gp_sobol_batch_f64")
         return (mean, cov) if boxed else (mean[0], cov[0])
 
+    def moments_batch(self, expX, inputs, invQt, invQ, mean_in, cov_in, pairs=None):
+        """``(mean (M, E), egrad (M, E, D), cov (M, P), evar (M, E) or None, info (M,) int32)`` of
+        ``gp_moments_batch_f64``: for E emulators on shared ``inputs`` (N, D) with ``expX`` (E, D + 2), ``invQt`` (E, N)
+        and ``invQ`` (E, N, N) or None, and the Gaussian inputs ``N(mean_in[m], cov_in[m])`` -- ``mean_in`` (M, D),
+        ``cov_in`` (D, D) or (M, D, D), positive semi-definite -- the means ``E[mu_e]``, the expected gradients, the
+        covariances ``Cov[mu_p, mu_q]`` of ``pairs`` (P, 2) -- default: (e, e) of every emulator -- and with ``invQ``
+        the expected emulator variances ``E[v_e]`` (NaN without the pair (e, e)); ``info`` as posterior_cov's (k + 1:
+        pivot k negative; -1: a non-finite row), NaN in such a row.  float64 only.
+        ``_moments_numpy.moments_pairs_numpy`` is the numpy branch."""
+        expX = np.ascontiguousarray(np.atleast_2d(expX), dtype=np.float64)
+        inputs = np.ascontiguousarray(inputs, dtype=np.float64)
+        invQt = np.ascontiguousarray(np.atleast_2d(invQt), dtype=np.float64)
+        if inputs.ndim != 2:
+            raise ValueError("inputs must be (n_train, n_inputs)")
+        (N, D), E = inputs.shape, expX.shape[0]
+        if expX.shape != (E, D + 2):
+            raise ValueError("expX must be (n_emulators, n_inputs + 2), got %s" % (expX.shape,))
+        if invQt.shape != (E, N):
+            raise ValueError("invQt must be (n_emulators, n_train), got %s" % (invQt.shape,))
+        if invQ is not None:
+            invQ = np.ascontiguousarray(invQ, dtype=np.float64)
+            if invQ.size != E * N * N:
+                raise ValueError("invQ must be (n_emulators, n_train, n_train), got %s" % (invQ.shape,))
+        m, S = _moments_rows(mean_in, cov_in, D)
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+            if pairs.ndim != 2 or pairs.shape[1] != 2:
+                raise ValueError("pairs must be (n_pairs, 2)")
+        M, P = m.shape[0], E if pairs is None else pairs.shape[0]
+        mean, egrad, cov = np.empty((M, E)), np.empty((M, E, D)), np.empty((M, P))
+        evar = None if invQ is None else np.empty((M, E))
+        info = np.empty(M, np.int32)
+        check(self.lib.gp_moments_batch_f64(self.h, E, _ptr(expX), _ptr(inputs), _ptr(invQt),
+                                            None if invQ is None else _ptr(invQ), N, D, M, _ptr(m), _ptr(S), P,
+                                            None if pairs is None else _ptr(pairs), _ptr(mean), _ptr(egrad), _ptr(cov),
+                                            None if evar is None else _ptr(evar), _ptr(info)), "gp_moments_batch_f64")
+        return mean, egrad, cov, evar, info
+
     # ---- events -----------------------------------------------------------------
     def event(self):
         e = c_void_p()
@@ -1226,12 +1267,15 @@ GP_OP_PREDICT, GP_OP_MEAN_GRAD, GP_OP_HESSIAN, GP_OP_RECONSTRUCT, GP_OP_MISFIT, 
 GP_OP_LUT_SEARCH = 7
 GP_OP_LUT_SEARCH_PC = 8
 GP_OP_SOBOL = 9
+GP_OP_MOMENTS = 10
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
                 6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
-                10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search", 14: "lut_search_pc", 15: "sobol"}
+                10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search", 14: "lut_search_pc", 15: "sobol",
+                16: "moments"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
              "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM, "var_grad": GP_OP_VAR_GRAD,
-             "lut_search": GP_OP_LUT_SEARCH, "lut_search_pc": GP_OP_LUT_SEARCH_PC, "sobol": GP_OP_SOBOL}
+             "lut_search": GP_OP_LUT_SEARCH, "lut_search_pc": GP_OP_LUT_SEARCH_PC, "sobol": GP_OP_SOBOL,
+             "moments": GP_OP_MOMENTS}
 
 
 def lut_search_geometry():
@@ -1267,7 +1311,8 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
     and ``term_chunk`` (``lut_search_geometry``).  "lut_search_pc" takes ``n_pcs`` and ``n_candidates``: the same
     items and slices, with ``candidate_tile``, ``padded_pcs`` and ``workgroups_per_cu`` (``lut_search_pc_geometry``).
     "sobol" takes ``n_rows`` boxes, ``n_emulators`` pairs, ``n_train`` and ``n_inputs``: an item is ``rows_per_item``
-    training rows of one (box, pair)."""
+    training rows of one (box, pair).  "moments" takes ``n_rows``, ``n_emulators`` pairs, ``n_train`` and ``n_inputs``:
+    an item is one (row, pair)."""
     code = _PLAN_OPS[op]
     recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_LUT_SEARCH, GP_OP_LUT_SEARCH_PC)
     if code == GP_OP_LUT_SEARCH:

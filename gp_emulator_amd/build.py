@@ -127,7 +127,8 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
               ("gp_band_misfit_tu.hip", "band_misfit", []), ("gp_band_unc_tu.hip", "band_unc", []),
               ("gp_mv_unc_tu.hip", "mv_unc", []), ("gp_newton_tu.hip", "newton", []),
               ("gp_lut_search_tu.hip", "lut_search", []), ("gp_lut_search_pc_tu.hip", "lut_search_pc", []),
-              ("gp_train_tu.hip", "train", []), ("gp_sobol_tu.hip", "sobol", [])]
+              ("gp_train_tu.hip", "train", []), ("gp_sobol_tu.hip", "sobol", []),
+              ("gp_moments_tu.hip", "moments", [])]
     # the host units (gp_host.hpp lists them)
     units += [("gp_%s.hip" % u, "gp_" + u, []) for u in ("ctx", "model", "device", "solve", "host_path", "folds", "mv")]
     tasks = [[HIPCC] + FLAGS + defines + extra + ["-c", os.path.join(CSRC, src), "-o", os.path.join(OBJ, name + ".o")]

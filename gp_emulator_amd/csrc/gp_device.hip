@@ -345,6 +345,14 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     k = GP_PLAN_SOBOL;
     rpi = gpk::skRows;
     g = gpk::plan_sobol(n_rows, n_emulators, n_train, gpk::sobol_cap(compute_units, n_inputs));
+  } else if (op == GP_OP_MOMENTS) {
+    // (n_emulators = n_pairs here)
+    if (n_train <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    if (n_inputs > gpk::gmMaxD || n_train > gpk::gmMaxN)
+      return fail(GP_ERR_UNSUPPORTED, "the moments kernels serve n_train <= %d, n_inputs <= %d", gpk::gmMaxN, gpk::gmMaxD);
+    k = GP_PLAN_MOMENTS;
+    rpi = 1;
+    g = gpk::plan_moments(n_rows, n_emulators, gpk::moments_cap(compute_units, n_inputs));
   } else if (op == GP_OP_VAR_GRAD) {
     int kd, knb;
     int rc = pick_kernel(n_train, n_inputs, &kd, &knb);

@@ -163,4 +163,23 @@ inline GridPlan plan_sobol(long long n_boxes, long long n_pairs, int n_train, lo
   return plan_grid(n_train, skRows, n_boxes * n_pairs, cap);
 }
 
+// moments_pair_kernel: an item is one (row, pair) over all n_train x n_train; plan_grid with one row per item.  The
+// instance is the padded n_inputs (8, 12 or 16: the width of the g table in LDS, 512 x padded doubles, which with the
+// other tables is 52, 69 and 85 KB of a CU's 160; two workgroups a CU where the registers allow it without spills).  The rows of a call run in slabs whose
+// scratch -- (n_emulators + n_pairs)(n_inputs^2 + 1) doubles a row -- stays within gmSlabBytes.
+constexpr int gmThreads = 256;
+constexpr int gmMaxN = 512, gmMaxD = 16;      // (a lane owns at most two columns; an F is loaded by n_inputs^2 <= 256 threads)
+constexpr long long gmSlabBytes = 256LL << 20;
+constexpr int moments_padded(int n_inputs) { return n_inputs <= 8 ? 8 : n_inputs <= 12 ? 12 : 16; }
+constexpr int moments_wgs_per_cu(int padded_inputs) { return padded_inputs <= 12 ? 2 : 1; }
+inline long long moments_cap(int compute_units, int n_inputs) {
+  return (long long)compute_units * moments_wgs_per_cu(moments_padded(n_inputs));
+}
+inline GridPlan plan_moments(long long n_rows, long long n_pairs, long long cap) { return plan_grid(n_rows, 1, n_pairs, cap); }
+inline long long moments_slab_rows(long long n_rows, long long n_classes, int n_inputs) {
+  const long long per_row = 8 * n_classes * ((long long)n_inputs * n_inputs + 1);
+  const long long r = gmSlabBytes / per_row;
+  return r < 1 ? 1 : r < n_rows ? r : n_rows;
+}
+
 }  // namespace gpk

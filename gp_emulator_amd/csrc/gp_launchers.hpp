@@ -28,6 +28,7 @@ template <typename T> struct LutPcArgs;
 template <typename T> struct LutPcSolveArgs;
 struct TrainArgs;
 struct SobolArgs;
+struct MomentsArgs;
 
 #pragma GCC visibility push(hidden)      // (the launchers are the library's own)
 // predict_kernel<T, D, NK, var> (var = false: the mean+gradient instance) for the compiled kernel_d
@@ -68,6 +69,10 @@ template <typename T> hipError_t launch_lut_pc_fill(T* x, T v, long long n, hipS
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);      // fp64 only
 // sobol_pair_kernel on `grid` workgroups (the instance by n_inputs), then sobol_fold_kernel; fp64 only
 hipError_t launch_sobol(const SobolArgs&, int grid, hipStream_t);
+// moments_flag_kernel, once per call; then per slab of rows moments_prepare_kernel, moments_mean_kernel and
+// moments_pair_kernel on `grid` workgroups (the instance by n_inputs); fp64 only
+hipError_t launch_moments_flags(const MomentsArgs&, hipStream_t);
+hipError_t launch_moments(const MomentsArgs&, int grid, hipStream_t);
 #pragma GCC visibility pop
 
 }  // namespace gpk

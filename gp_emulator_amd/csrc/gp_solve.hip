@@ -1,6 +1,7 @@
 // The small dense solves on device buffers: damped Newton step, LM update, posterior covariance, prior propagation and
 // the smoother's backward step; and the look-up-table search that starts a retrieval.  Device arrays in, device arrays
-// out, no model.  The Sobol indices of a batch of emulators, on host arrays (no model either).
+// out, no model.  The Sobol indices of a batch of emulators and their moments under a Gaussian input, on host arrays
+// (no model either).
 #include "gp_host.hpp"
 
 #include "gp_launch_plan.hpp"
@@ -11,6 +12,7 @@
 #include "gp_posterior_cov_kernel.hpp"
 #include "gp_prior_propagate_kernel.hpp"
 #include "gp_rts_smooth_kernel.hpp"
+#include "gp_moments_args.hpp"
 #include "gp_sobol_args.hpp"
 
 // what a launcher returned, as the entry's status
@@ -398,6 +400,75 @@ int gp_sobol_batch_f64(gp_ctx* ctx, int n_emulators, const double* expX, const d
   if (int rc = launched(gpk::launch_sobol(a, plan.workgroups, st), "sobol")) return rc;
   HIP_TRY(hipMemcpyAsync(mean, d_mean, sizeof(double) * n_mean, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(cov, d_cov, sizeof(double) * n_cov, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GP_OK;
+}
+
+int gp_moments_batch_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs, const double* invQt,
+                         const double* invQ, int n_train, int n_inputs, int64_t n_rows, const double* mean_in,
+                         const double* cov_in, int n_pairs, const int32_t* pairs, double* mean, double* egrad, double* cov,
+                         double* evar, int32_t* info) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!expX || !inputs || !invQt || !mean_in || !cov_in || !mean || !cov || !info) return fail(GP_ERR_INVALID, "null pointer");
+  if (evar && !invQ) return fail(GP_ERR_INVALID, "the expected variance needs invQ");
+  if (n_emulators <= 0 || n_train <= 0 || n_inputs <= 0 || n_rows <= 0 || n_pairs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_inputs > gpk::gmMaxD || n_train > gpk::gmMaxN)
+    return fail(GP_ERR_UNSUPPORTED, "the moments kernels serve n_train <= %d, n_inputs <= %d", gpk::gmMaxN, gpk::gmMaxD);
+  if (!pairs && n_pairs != n_emulators) return fail(GP_ERR_INVALID, "without a pair list n_pairs is n_emulators");
+  if (pairs)
+    for (size_t k = 0; k < 2 * (size_t)n_pairs; ++k)
+      if (pairs[k] < 0 || pairs[k] >= n_emulators)
+        return fail(GP_ERR_INVALID, "pair %lld names emulator %d of %d", (long long)(k / 2), pairs[k], n_emulators);
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t E = (size_t)n_emulators, N = (size_t)n_train, D = (size_t)n_inputs, P = (size_t)n_pairs, DD = D * D;
+  const size_t R = (size_t)gpk::moments_slab_rows(n_rows, n_emulators + (long long)n_pairs, n_inputs);      // rows of a slab
+  const size_t n_theta = E * (D + 2), n_in = N * D, n_al = E * N, n_q = invQ ? E * N * N : 0, n_m = R * D, n_sig = R * DD,
+               n_F = R * (E + P) * DD, n_ld = R * (E + P), n_mean = R * E, n_grad = egrad ? R * E * D : 0, n_cov = R * P,
+               n_ev = evar ? R * E : 0, n_int = (R + E + (pairs ? 2 * P : 0) + 1) / 2;      // (two int32 per double)
+  if (int rc = ensure_scratch(ctx, sizeof(double) * (n_theta + n_in + n_al + n_q + n_m + n_sig + n_F + n_ld + n_mean + n_grad +
+                                                     n_cov + n_ev + n_int)))
+    return rc;
+  double* d_theta = (double*)ctx->scratch;
+  double* d_in = d_theta + n_theta;
+  double* d_al = d_in + n_in;
+  double* d_q = d_al + n_al;
+  double* d_m = d_q + n_q;
+  double* d_sig = d_m + n_m;
+  double* d_F = d_sig + n_sig;
+  double* d_ld = d_F + n_F;
+  double* d_mean = d_ld + n_ld;
+  double* d_grad = d_mean + n_mean;
+  double* d_cov = d_grad + n_grad;
+  double* d_ev = d_cov + n_cov;
+  int* d_info = (int*)(d_ev + n_ev);
+  int* d_flag = d_info + R;
+  int* d_pairs = pairs ? d_flag + E : nullptr;
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(d_theta, expX, sizeof(double) * n_theta, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_in, inputs, sizeof(double) * n_in, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_al, invQt, sizeof(double) * n_al, hipMemcpyHostToDevice, st));
+  if (invQ) HIP_TRY(hipMemcpyAsync(d_q, invQ, sizeof(double) * n_q, hipMemcpyHostToDevice, st));
+  if (pairs) HIP_TRY(hipMemcpyAsync(d_pairs, pairs, sizeof(int32_t) * 2 * P, hipMemcpyHostToDevice, st));
+  gpk::MomentsArgs a;
+  a.expX = d_theta, a.inputs = d_in, a.alpha = d_al, a.invQ = invQ ? d_q : nullptr, a.pairs = d_pairs, a.flag = d_flag;
+  a.m = d_m, a.sigma = d_sig, a.F = d_F, a.ld = d_ld;
+  a.mean = d_mean, a.egrad = egrad ? d_grad : nullptr, a.cov = d_cov, a.evar = evar ? d_ev : nullptr, a.info = d_info;
+  a.N = n_train, a.D = n_inputs, a.E = n_emulators, a.P = n_pairs, a.R = 0, a.items = 0;
+  if (int rc = launched(gpk::launch_moments_flags(a, st), "moments_flag")) return rc;
+  const long long cap = gpk::moments_cap(ctx->compute_units, n_inputs);
+  for (size_t r0 = 0; r0 < (size_t)n_rows; r0 += R) {
+    const size_t nr = (size_t)n_rows - r0 < R ? (size_t)n_rows - r0 : R;
+    HIP_TRY(hipMemcpyAsync(d_m, mean_in + r0 * D, sizeof(double) * nr * D, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_sig, cov_in + r0 * DD, sizeof(double) * nr * DD, hipMemcpyHostToDevice, st));
+    const gpk::GridPlan plan = gpk::plan_moments((long long)nr, n_pairs, cap);
+    a.R = (long long)nr, a.items = plan.items;
+    if (int rc = launched(gpk::launch_moments(a, plan.workgroups, st), "moments")) return rc;
+    HIP_TRY(hipMemcpyAsync(mean + r0 * E, d_mean, sizeof(double) * nr * E, hipMemcpyDeviceToHost, st));
+    if (egrad) HIP_TRY(hipMemcpyAsync(egrad + r0 * E * D, d_grad, sizeof(double) * nr * E * D, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cov + r0 * P, d_cov, sizeof(double) * nr * P, hipMemcpyDeviceToHost, st));
+    if (evar) HIP_TRY(hipMemcpyAsync(evar + r0 * E, d_ev, sizeof(double) * nr * E, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(info + r0, d_info, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st));
+  }
   HIP_TRY(hipStreamSynchronize(st));
   return GP_OK;
 }

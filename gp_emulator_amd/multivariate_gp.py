@@ -895,6 +895,34 @@ class MultivariateEmulator(object):
                                         pairs=_sobol_numpy.upper_pairs(P), is_gpu=is_gpu)
         return _sobol_numpy.spectral(np.asarray(self.basis_functions)[:P], mean, _sobol_numpy.mirror(cov, P))
 
+    # ---- Gaussian input uncertainty ----------------------------------------------------------------
+    def predict_uncertain(self, Y, cov, is_gpu=True, return_pc=False):
+        """The reconstructed spectrum ``f_k = sum_p basis[p, k] mu_p`` under Gaussian inputs ``y_m ~ N(Y[m], cov[m])``
+        -- ``Y`` (M, D), ``cov`` (D, D) or (M, D, D), positive semi-definite -- by exact moment matching:
+        ``UncertainSpectrum(mean (M, N_full), var_state (M, N_full), var_emulator (M, N_full), info (M,))``.  One
+        ``gp_moments_batch_f64`` call (``is_gpu=False``: the numpy branch) gives the PCs' means ``M_p``, the covariances
+        ``V`` of all ``P (P + 1) / 2`` pairs and the expected emulator variances ``Ev_p``; the mean is reconstructed
+        from ``M_p`` as ``predict_many`` reconstructs a spectrum, ``var_state[m, k] = beta_k' V[m] beta_k`` and
+        ``var_emulator[m, k] = sum_p beta_pk^2 Ev_p[m]`` with ``beta_k = basis[:, k]``, on the host.  Nothing of size
+        ``N_full`` is emulated.  ``return_pc=True`` appends ``pc_mean (M, P)`` and ``pc_cov (M, P, P)``.  ``info`` as
+        ``GaussianProcess.predict_uncertain``::
+
+            y, *_, cov, sigma, status = mv.retrieve_many(Y0, obs, return_cov=True)
+            s = mv.predict_uncertain(y, cov)          # the predicted-observation distribution of the retrieved states
+
+        Not in the reference."""
+        from . import _moments_numpy, perband
+        P = self.n_pcs
+        mean, _, V, evar, info = perband.moments_pairs(*perband._moments_constants(self.emulators[:P]), Y, cov,
+                                                        pairs=_moments_numpy.upper_pairs(P), is_gpu=is_gpu)
+        basis = np.asarray(self.basis_functions, dtype=np.float64)[:P]
+        pc_cov = _moments_numpy.mirror(V[..., None], P)[..., 0]
+        evar = np.full(mean.shape, np.nan) if evar is None else evar
+        var_state, var_emulator = _moments_numpy.spectral_variances(basis, pc_cov, evar)
+        if return_pc:
+            return _moments_numpy.UncertainSpectrumPC(mean @ basis, var_state, var_emulator, info, mean, pc_cov)
+        return _moments_numpy.UncertainSpectrum(mean @ basis, var_state, var_emulator, info)
+
     # ---- second derivatives ---------------------------------------------------------------------
     def hessian(self, y, is_gpu=False, weights=None):
         """Hessian of the reconstructed output at ONE input vector ``y``: ``(N_params, N_params, N_full)`` (axes

@@ -8,7 +8,7 @@ of the fused kernel (BASELINE config 3: 2101 bands x N_train=250 x D=11, shared 
 """
 import numpy as np
 
-from . import _first_guess, _lib, _retrieve, _sobol_numpy, multi_gpu
+from . import _first_guess, _lib, _moments_numpy, _retrieve, _sobol_numpy, multi_gpu
 from ._retrieve import LAMBDA_MAX, LAMBDA_MIN, _lm_update_numpy, _prior_term     # noqa: F401  (their names here)
 from .perband_train import (learn_bands, _driver_probe, _lockstep_driver, _lockstep_processes,     # noqa: F401  (training
                             _Population, _probe_setulb, _worker_main)                              # many bands at once)
@@ -149,6 +149,42 @@ def sobol_bands(gps, bounds, is_gpu=True, device=None):
     mean, cov = sobol_pairs(*_sobol_constants(gps), bounds, is_gpu=is_gpu, device=device)
     first, total, variance = _sobol_numpy.indices(cov)
     return _sobol_numpy.SobolIndices(first, total, variance, mean)
+
+
+def _moments_constants(gps):
+    """``_sobol_constants`` and invQ (E, N, N) -- None when an emulator has none."""
+    expX, inputs, invQt = _sobol_constants(gps)
+    N = inputs.shape[0]
+    if any(getattr(gp, "invQ", None) is None for gp in gps):
+        return expX, inputs, invQt, None
+    return expX, inputs, invQt, np.stack([np.asarray(gp.invQ, dtype=np.float64).reshape(N, N) for gp in gps])
+
+
+def moments_pairs(expX, inputs, invQt, invQ, X, cov, pairs=None, is_gpu=True, device=None):
+    """``(mean, egrad, cov, evar, info)`` of ``Context.moments_batch`` on the default context of ``device``, or with
+    ``is_gpu=False`` of its numpy branch ``_moments_numpy.moments_pairs_numpy``."""
+    if is_gpu:
+        return _lib.default_context(device).moments_batch(expX, inputs, invQt, invQ, X, cov, pairs)
+    return _moments_numpy.moments_pairs_numpy(expX, inputs, invQt, invQ, X, cov, pairs)
+
+
+def predict_uncertain_bands(gps, X, cov, is_gpu=True, device=None):
+    """The E emulators in ``gps`` (shared training inputs) under Gaussian inputs ``x_m ~ N(X[m], cov[m])`` -- ``X``
+    (M, D), ``cov`` (D, D) or (M, D, D), positive semi-definite, only the lower triangles read -- in closed form:
+    ``UncertainPrediction(mean (E, M), var_state (E, M), var_emulator (E, M), expected_grad (E, M, D), info (M,))``.
+    ``mean = E[mu_e(x)]``, ``var_state = Var[mu_e(x)]`` (the state's share of a band's uncertainty), ``var_emulator =
+    E[v_e(x)]`` (the emulator's; NaN when an emulator has no ``invQ``), their sum the total predictive variance, and
+    ``expected_grad = E[d mu_e / dx]``, so that ``Cov[x, mu_e] = cov @ expected_grad``.  ``info`` is nonzero, and the
+    row NaN, where ``cov[m]`` is not positive semi-definite (k + 1: pivot k) or the row is not finite (-1).  One call
+    of ``gp_moments_batch_f64`` (float64 only) for all bands and rows; ``is_gpu=False`` is the numpy branch::
+
+        x, *_, cov, sigma, status = retrieve_bands(gps, X0, obs, return_cov=True)
+        other = predict_uncertain_bands(other_sensor_gps, x, cov)      # what the state implies for another sensor
+
+    See ``GaussianProcess.predict_uncertain``."""
+    mean, egrad, V, evar, info = moments_pairs(*_moments_constants(gps), X, cov, is_gpu=is_gpu, device=device)
+    evar = np.full(mean.shape, np.nan) if evar is None else evar
+    return _moments_numpy.UncertainPrediction(mean.T.copy(), V.T.copy(), evar.T.copy(), egrad.transpose(1, 0, 2).copy(), info)
 
 
 def hessian_bands(gps, testing, precision=np.float64, weights=None, device=None, devices=None, hessian_fn=None):

@@ -720,6 +720,34 @@ int gp_sobol_batch_f64(gp_ctx* ctx, int n_emulators, const double* expX, const d
                        int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi, int n_pairs,
                        const int32_t* pairs, double* mean, double* cov);
 
+/* ---- Moments of the emulators under a Gaussian input, closed form -------------------------------------
+ * The emulators as in gp_sobol_batch_f64, with invQ [n_emulators][n_train][n_train] or NULL; n_rows inputs
+ * x ~ N(mean_in[m], cov_in[m]), mean_in [n_rows][n_inputs], cov_in [n_rows][n_inputs][n_inputs] (only the lower
+ * triangles are read; positive SEMI-definite: a direction whose pivot d_k of the Cholesky factorisation has
+ * |d_k| <= 64 u cov_kk carries no uncertainty, so an input may be held fixed and cov may be 0).  For every row
+ *     mean  [n_rows][n_emulators]            E[mu_e(x)]
+ *     egrad [n_rows][n_emulators][n_inputs]  E[d mu_e / dx]; Cov[x, mu_e] = cov_in egrad          (or NULL)
+ *     cov   [n_rows][n_pairs]                Cov[mu_p(x), mu_q(x)] of the pairs [n_pairs][2] (NULL: (e, e) of every
+ *                                            emulator, n_pairs = n_emulators)
+ *     evar  [n_rows][n_emulators]            E[v_e(x)], the expected emulator variance, from the pair (e, e); NaN for an
+ *                                            emulator without that pair (or NULL; needs invQ)
+ *     info  [n_rows]                         0; k + 1: pivot k of cov_in is negative beyond 64 u cov_kk; -1: a non-finite
+ *                                            entry of the row's mean_in or cov_in.  Every output of such a row is NaN.
+ * The total predictive variance of emulator e is cov (e, e) + evar.  The sums are those of moment matching written so
+ * that what is of order one cancels algebraically (gp_moments_kernel.hpp): cov keeps its digits as cov_in -> 0 and is
+ * exactly 0 at cov_in = 0, where mean, evar and egrad are predict's values at mean_in.  No atomics: a (row, pair) and
+ * a (row, emulator) result is bit for bit the same alone or in any batch, in any pair order, on any grid
+ * (gp_launch_plan, GP_OP_MOMENTS).  An emulator with a non-finite expX, invQt or invQ entry gives NaN in its own
+ * results and in every pair it is part of and changes no other result.
+ * GP_ERR_INVALID: a NULL argument that is not optional, evar without invQ, non-positive sizes, a pair index outside
+ * 0..n_emulators-1, n_pairs != n_emulators with pairs NULL.  GP_ERR_UNSUPPORTED: n_inputs > 16 or n_train > 512.
+ * Nothing is written on an error.  Host pointers, fp64 only, synchronous; the rows run in slabs that bound the
+ * device scratch. */
+int gp_moments_batch_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs, const double* invQt,
+                         const double* invQ, int n_train, int n_inputs, int64_t n_rows, const double* mean_in,
+                         const double* cov_in, int n_pairs, const int32_t* pairs, double* mean, double* egrad,
+                         double* cov, double* evar, int32_t* info);
+
 /* Host-side packing only (no GPU needed): what gp_model_create_* uploads.  xa and frags
  * are sized by gp_pack_sizes; sd takes 2*kernel_d + 1 reals (sqrt(e_d), the centre c_d, b);
  * used by the CPU tests to check the fragment layout. */
@@ -751,7 +779,8 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_LUT_SEARCH 7         /* gp_lut_search_device: n_inputs is n_terms and aux n_candidates; rest_items is n_slices */
 #define GP_OP_LUT_SEARCH_PC 8      /* gp_lut_search_pc_device: n_inputs is n_pcs and aux n_candidates; rest_items is n_slices */
 #define GP_OP_SOBOL 9              /* gp_sobol_batch_f64: n_emulators is n_pairs and n_rows n_boxes; an item is 16 training rows */
-#define GP_PLAN_PREDICT_FEW 1      /* predict_few_kernel: a workgroup per 16-row tile */
+#define GP_OP_MOMENTS 10           /* gp_moments_batch_f64: n_emulators is n_pairs; an item is one (row, pair) */
+#define GP_PLAN_PREDICT_FEW 1     /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
 #define GP_PLAN_HESS_VALU 4        /* hessian_kernel */
@@ -766,6 +795,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_LUT_SEARCH 13      /* lut_search_kernel: an item is 256 rows x one slice of the candidates */
 #define GP_PLAN_LUT_SEARCH_PC 14   /* lut_search_pc_kernel: the same items; workgroups per CU by instance (n_pcs, dtype) */
 #define GP_PLAN_SOBOL 15           /* sobol_pair_kernel: items = n_boxes x n_pairs x ceil(n_train / 16); one workgroup per CU */
+#define GP_PLAN_MOMENTS 16         /* moments_pair_kernel: items = n_rows x n_pairs; 2 workgroups per CU for n_inputs <= 12, 1 beyond */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
