@@ -41,7 +41,8 @@ def _system_matrices(A, prior_prec):
 
 
 def _clip(x, bounds):
-    """``x`` (M, D) clamped to ``bounds = (lo (D,), hi (D,))``: max with lo, then min with hi, as the kernels' clamp."""
+    """``x`` (M, D) clamped to ``bounds = (lo (D,), hi (D,))``: max with lo, then min with hi, as the kernels' clamp; a
+    NaN stays NaN, there as here."""
     return np.minimum(np.maximum(x, np.asarray(bounds[0], dtype=np.float64)), np.asarray(bounds[1], dtype=np.float64))
 
 

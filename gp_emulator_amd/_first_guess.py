@@ -107,8 +107,8 @@ def route_rows(index, cost, status, band_search):
 
 def mask_obs(obs, weights, dtype):
     """``obs`` with 0 selected in wherever the weight, rounded to the device ``dtype``, is exactly 0 (``obs`` itself
-    without weights): what the PC-space set-up takes, whose misfit kernel multiplies by the weight and does not
-    select."""
+    without weights, or when no weight is 0): what the PC-space set-up, the misfits and the retrievals take, whose
+    kernels and numpy forms multiply by the weight and do not select."""
     if weights is None:
         return obs
     masked = np.asarray(weights, dtype=dtype) == 0

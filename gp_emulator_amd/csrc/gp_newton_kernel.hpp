@@ -10,6 +10,7 @@
 //   L L^T = A'                            Cholesky of the LOWER triangle; the upper triangle is never loaded
 //   step[m]  = -L^-T L^-1 g'
 //   trial[m] = clamp(x_m + step[m], lo, hi)         (lo / hi [D] both or neither; without them x + step)
+//                                         a NaN x_m + step[m] stays NaN: the clamp selects it, fmin / fmax would not
 //   status[m] = 0, or k + 1 when pivot k is not > 0 or not finite; then step[m] = 0 and trial[m] = x_m
 //
 // Arithmetic: double in both precisions; step and trial are each rounded to T once, on store (trial from the
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(kNewtonThreads) void newton_step_kernel(NewtonArgs<
       p.trial[m * D + j] = p.x[m * D + j];
     } else {
       double t = xj + st;
-      if (p.lo) t = fmin(fmax(t, (double)p.lo[j]), (double)p.hi[j]);
+      if (p.lo) t = t != t ? t : fmin(fmax(t, (double)p.lo[j]), (double)p.hi[j]);   // (fmin / fmax would drop a NaN)
       p.trial[m * D + j] = (T)t;
     }
   }

@@ -11,6 +11,7 @@
 //   G  = C N                              smoother gain
 //   d  = x_next[m] - x[m]                 d_j one subtraction of the two inputs as doubles
 //   x_smooth[m] = clamp(x[m] + G d, lo, hi)        the step kernel's clamp on the double; without lo / hi x + G d
+//                                         (a NaN stays NaN, as there)
 //   Delta = cov_next[m] - S               Delta_ij one subtraction, (double)cov_next_ij - S_ij, S_ij the fl(C_ij + Q_ij)
 //                                         that is factored; the lower triangle of cov_next is read
 //   F = G Delta,  K = F G^T,  C_s = C + K          K and C_s at i >= j only
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(kRtsThreads) void rts_smooth_kernel(RtsSmoothArgs<T
 
   if (live) {
     double xs = xi + gd;
-    if (p.lo) xs = fmin(fmax(xs, (double)p.lo[i]), (double)p.hi[i]);
+    if (p.lo) xs = xs != xs ? xs : fmin(fmax(xs, (double)p.lo[i]), (double)p.hi[i]);   // (fmin / fmax would drop a NaN)
     p.x_smooth[m * D + i] = (T)(bad ? qnan : xs);
     if (p.sigma_smooth) p.sigma_smooth[m * D + i] = (T)(bad ? qnan : sqrt(L[ti + i]));
     if (i == 0) p.status[m] = bad;

@@ -414,8 +414,11 @@ class MultivariateEmulator(object):
         = Jac diag(w) Jac^T`` (``gauss_newton``; weights shared by all rows) and ``coef (M, n_pcs)``
         (``return_coef``) ``= basis (w * r)``, which ``hessian_many(Y, coef=coef)`` turns into the curvature term:
         ``gn + hessian_many(Y, coef=coef)`` is the full second-order data term.  ``obs`` is ``(N_full,)`` or
-        ``(M, N_full)``; ``weights`` None (all 1), ``(N_full,)`` or ``(M, N_full)``.  Not in the reference, whose
-        caller contracts ``predict``'s Jacobian on the host.
+        ``(M, N_full)``; ``weights`` None (all 1), ``(N_full,)`` or ``(M, N_full)``.  A weight of exactly 0 (as rounded
+        to the call's ``precision`` on the GPU, in float64 on the numpy branch) masks its band whatever ``obs`` holds
+        there: 0 is selected into ``obs`` before the upload and before the numpy data term, which multiply by the
+        weight and do not select; a NaN or an infinity in ``obs`` under a non-zero weight, or in a weight, makes the
+        row's results NaN.  Not in the reference, whose caller contracts ``predict``'s Jacobian on the host.
 
         Nothing of size ``N_params x N_full`` is formed: ``coef[p] = sum_b basis[p, b] w_b r_b`` and ``grad[d] =
         sum_p coef[p] dmu_p/dy_d``.  The numpy branch states exactly that on the per-PC ``gp.predict`` outputs.  On
@@ -446,9 +449,11 @@ class MultivariateEmulator(object):
         weights) or the host's matrix uploaded once, ``mv_misfit_unc_device``, results down.  ``is_gpu=False`` is the
         explicit float64 numpy branch of the same formulas from ``cpu_predict(do_unc=True)`` and
         ``variance_gradient(is_gpu=False)``; never a fallback.  With ``False`` nothing changes."""
+        from . import _first_guess
         if emulator_unc and return_coef:
             raise ValueError("return_coef=True needs the Hessian of the variance: not available with emulator_unc=True")
         Y, obs, weights = self._misfit_args(Y, obs, weights, gauss_newton and not emulator_unc)
+        obs = _first_guess.mask_obs(obs, weights, precision if is_gpu else np.float64)
         M, D = Y.shape
         P, B = self.n_pcs, self.basis_functions.shape[1]
         if emulator_unc:
@@ -621,7 +626,10 @@ class MultivariateEmulator(object):
 
         from ``Y0`` (M, D), inside ``bounds=(lo (D,), hi (D,))`` when given.  ``obs`` is ``(N_full,)`` or
         ``(M, N_full)``; ``weights`` None (all 1), ``(N_full,)`` or ``(M, N_full)`` -- per-row weights are per-pixel
-        uncertainties and masks: weight 0 marks a missing or contaminated band.  The loop, its arguments and what it
+        uncertainties and masks: weight 0 marks a missing or contaminated band, and a weight of exactly 0 masks its band
+        whatever ``obs`` holds there (NaN or a fill value); a row with a NaN or an infinity in ``obs`` under a non-zero
+        weight, in a weight or in ``Y0`` is never accepted and comes back as it went in ("Invalid pixels in
+        the retrievals").  The loop, its arguments and what it
         returns are ``perband.retrieve_bands``': an iteration is the misfit at the trial rows, the accept / reject
         update (a trial that lowers F is taken and lambda multiplied by ``down``, any other is dropped and lambda
         multiplied by ``up``, between ``perband.LAMBDA_MIN`` and ``LAMBDA_MAX``; a row whose accepted step gains no
@@ -669,7 +677,7 @@ class MultivariateEmulator(object):
         ``predict_var_grad_device``, ``mv_misfit_device`` (cost and ``basis (w * r)``, no gradient) and
         ``mv_misfit_unc_device`` with the matrix formed once before the loop, then the same update and step; the numpy
         branch hands the loop the numpy form of that term.  With ``False`` nothing changes."""
-        from . import _retrieve
+        from . import _first_guess, _retrieve
         Y0 = np.asarray(Y0)
         if Y0.ndim != 2:
             raise ValueError("Y0 must be (n_rows, n_inputs)")
@@ -678,6 +686,7 @@ class MultivariateEmulator(object):
         if D != self.emulators[0].inputs.shape[1]:
             raise ValueError("Y0 has %d columns, the emulators have %d inputs" % (D, self.emulators[0].inputs.shape[1]))
         _, obs, weights = self._misfit_args(Y0, obs, weights, False)
+        obs = _first_guess.mask_obs(obs, weights, precision if is_gpu else np.float64)
         prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D, M)
         max_iter = int(max_iter)
         per_row = weights is not None and weights.ndim == 2

@@ -323,7 +323,11 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
 
     Returns ``cost (M,), grad (M, D)``, then ``gn`` (``second_order="gauss_newton"``) or ``hess`` (``"full"``)
     ``(M, D, D)``, then with ``return_residual`` ``wr = w r (E, M)`` -- the ``weights`` of ``hessian_bands``.
-    ``obs`` and ``weights`` are ``(E,)`` (one spectrum for all rows) or ``(E, M)``.  On the GPU
+    ``obs`` and ``weights`` are ``(E,)`` (one spectrum for all rows) or ``(E, M)``.  A weight of exactly 0 (as rounded to
+    the call's ``precision`` on the GPU, in float64 on the numpy branch) masks its band whatever ``obs`` holds there: 0
+    is selected into ``obs`` before the upload and before the numpy data term, whose kernels and formulas multiply by
+    the weight and do not select; a NaN or an infinity in ``obs`` under a non-zero weight, or in a weight, makes the
+    row's results NaN.  On the GPU
     (``BatchModel.misfit``, ``gp_band_misfit_host``) the per-emulator means, gradients and residuals never leave the
     device; no inverse is stacked or uploaded.  ``is_gpu=False`` is the explicit numpy branch, built from each
     emulator's ``cpu_predict(do_unc=False)`` and ``hessian``; never a fallback.
@@ -356,6 +360,7 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
     obs = _em_broadcast(obs, E, M, "obs")
     if weights is not None:
         weights = _em_broadcast(weights, E, M, "weights")
+    obs = _first_guess.mask_obs(obs, weights, precision if is_gpu else np.float64)
 
     def block(a, e0, e1):           # a block of emulators in the shape the caller gave: (e,) or (e, M)
         if a is None:
@@ -404,7 +409,10 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
         F(x) = 1/2 sum_e w (mu_e(x) - obs[e])^2  (+ 1/2 (x - x0)^T P (x - x0) with ``prior=(x0 (D,), P (D, D))``)
 
     from ``X0`` (M, D), inside ``bounds=(lo (D,), hi (D,))`` when given.  ``obs`` and ``weights`` as in
-    ``misfit_bands``; ``second_order`` is "gauss_newton" or "full" (the matrix A of the step).  An iteration is: the
+    ``misfit_bands``: a weight of exactly 0 masks its band whatever ``obs`` holds there (a cloudy or missing band may
+    be NaN or a fill value under it); a row with a NaN or an infinity in ``obs`` under a non-zero weight, in a weight or
+    in ``X0`` is never accepted and comes back as it went in ("Invalid pixels in the retrievals").
+    ``second_order`` is "gauss_newton" or "full" (the matrix A of the step).  An iteration is: the
     misfit at the trial rows, the accept / reject update (a trial that lowers F is taken and lambda multiplied by
     ``down``, any other is dropped and lambda multiplied by ``up``, between ``LAMBDA_MIN`` and ``LAMBDA_MAX``; a row
     whose accepted step gains no more than ``ftol * F`` or moves no more than ``xtol`` is converged and frozen), then
@@ -463,6 +471,7 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     obs = _em_broadcast(obs, E, M, "obs")
     if weights is not None:
         weights = _em_broadcast(weights, E, M, "weights")
+    obs = _first_guess.mask_obs(obs, weights, precision if is_gpu and step_fn is None else np.float64)
     prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D, M)
     max_iter = int(max_iter)
 

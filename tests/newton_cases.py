@@ -48,6 +48,46 @@ def seeded(D, M, full_rank, dtype, seed=1, prior=False, bounds=False):
     return case
 
 
+NAN_GRAD_ROWS, NAN_X_ROWS = (2, 16, 64), (5, 15, 63)      # of 65: both sides of a 16-row edge, the ragged last row
+
+
+def same(a, b):
+    assert a.dtype == b.dtype and a.shape == b.shape
+    assert np.array_equal(a, b, equal_nan=True)
+
+
+def check_nan_into_the_clamp(step_fn, case):
+    """Rows with a sound matrix and a NaN in one component of ``grad`` (NAN_GRAD_ROWS) or of ``x`` (NAN_X_ROWS), on
+    either branch: ``step_fn(case) -> (step, trial, status)``.  The factorisation does not see the NaN, so status is
+    0; the NaN reaches the clamp and comes out of it.  A NaN gradient, or a NaN state under a prior (whose P (x - x0)
+    joins the gradient), makes every component of step and trial NaN -- the back substitution carries z_{D-1} into
+    every other component; a NaN state without a prior leaves the step that of the clean call, bit for bit, and trial
+    NaN in that component only.  Every other row is bit for bit the call without the planted rows."""
+    M, D = case["x"].shape
+    bad = dict(case, grad=case["grad"].copy(), x=case["x"].copy())
+    for m in NAN_GRAD_ROWS:
+        bad["grad"][m, m % D] = np.nan
+    for m in NAN_X_ROWS:
+        bad["x"][m, m % D] = np.nan
+    clean, got = step_fn(case), step_fn(bad)
+    keep = np.ones(M, bool)
+    keep[list(NAN_GRAD_ROWS + NAN_X_ROWS)] = False
+    for a, b in zip(got, clean):
+        same(a[keep], b[keep])
+    step, trial, status = got
+    assert not status.any() and not clean[2].any()
+    for m in NAN_GRAD_ROWS:
+        assert np.all(np.isnan(step[m])) and np.all(np.isnan(trial[m])), m
+    for m in NAN_X_ROWS:
+        c = np.arange(D) == m % D
+        if case["prior"] is not None:
+            assert np.all(np.isnan(step[m])) and np.all(np.isnan(trial[m])), m
+        else:
+            same(step[m], clean[0][m])
+            assert np.all(np.isnan(trial[m][c])), m
+            same(trial[m][~c], clean[1][m][~c])
+
+
 def formed(case, lam, damping):
     """A' (M, D, D) and g' (M, D) in longdouble from the inputs as given."""
     x, g, A = (case[k].astype(LD) for k in ("x", "grad", "A"))

@@ -67,6 +67,30 @@ def successor(case, full_rank, seed=4):
     return ((x.astype(np.float64) + delta).astype(x.dtype), np.ascontiguousarray(cov.astype(x.dtype)))
 
 
+def check_nan_into_the_clamp(smooth_fn, case, x_next):
+    """Rows with sound matrices and a NaN in one component of ``x`` (newton_cases.NAN_X_ROWS) or of ``x_next``
+    (NAN_GRAD_ROWS), on either branch: ``smooth_fn(x, x_next) -> (x_smooth, cov_smooth, sigma_smooth, status)``.  Neither
+    inversion sees the NaN, so status is 0; d = x_next - x carries it into every component of G d (G is dense), and it
+    comes out of the clamp: the row's x_smooth is NaN throughout, its cov_smooth and sigma_smooth, which read neither
+    state, are those of the clean call bit for bit, and so is every output of every other row."""
+    x = case["x"]
+    M, D = x.shape
+    xb, xnb = x.copy(), x_next.copy()
+    for m in nc.NAN_X_ROWS:
+        xb[m, m % D] = np.nan
+    for m in nc.NAN_GRAD_ROWS:
+        xnb[m, m % D] = np.nan
+    clean, got = smooth_fn(x, x_next), smooth_fn(xb, xnb)
+    planted = list(nc.NAN_X_ROWS + nc.NAN_GRAD_ROWS)
+    keep = np.ones(M, bool)
+    keep[planted] = False
+    assert not clean[3].any() and not got[3].any()
+    nc.same(got[0][keep], clean[0][keep])
+    assert np.all(np.isnan(got[0][planted]))
+    for k in (1, 2, 3):
+        nc.same(got[k], clean[k])
+
+
 def truth(case, Q, x_next, cov_next, bounds=None):
     """dict(x, cov, sigma, ok and the intermediates C, S, N, G, d, Delta, F, G1, G2) in longdouble."""
     t = prc.propagate_truth(case, Q)

@@ -82,6 +82,19 @@ def test_numpy_branch_reports_the_failed_pivot():
         _lib.newton_step_numpy(case["x"], case["grad"], A, 1.0, "marquardt")
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("D", nc.DIMS)
+def test_numpy_branch_carries_a_nan_through_the_clamp(D, dtype):
+    """newton_cases.check_nan_into_the_clamp, both damping modes, without and with prior + bounds: a NaN gradient or
+    state under a sound matrix gives status 0 and a NaN trial, as the kernel does."""
+    for extras in (False, True):
+        case = nc.seeded(D, 65, True, dtype, prior=extras, bounds=extras)
+        lam = np.array(nc.LAMBDAS, dtype)[np.arange(65) % 3]
+        for damping in ("diagonal", "identity"):
+            nc.check_nan_into_the_clamp(lambda c: _lib.newton_step_numpy(c["x"], c["grad"], c["A"], lam, damping, c["prior"],
+                                                                          c["bounds"]), case)
+
+
 # ---- the C entries ---------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_exported_and_bound():
     text = open(os.path.join(ROOT, "include", "gp_predict_hip.h")).read()

@@ -15,7 +15,7 @@ import pytest
 import newton_cases as nc
 from oracle import gp_oracle
 
-from gp_emulator_amd import GaussianProcess, _lib, perband
+from gp_emulator_amd import GaussianProcess, _lib, _retrieve, perband
 
 pytestmark = pytest.mark.gpu
 
@@ -194,6 +194,30 @@ def test_step_is_deterministic_and_rows_are_independent(gpu_lib, D, dtype):
         same(a, b)
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("D", nc.DIMS)
+def test_a_nan_goes_through_the_clamp(gpu_lib, D, dtype):
+    """newton_cases.check_nan_into_the_clamp on the device, both damping modes, without and with prior + bounds: a NaN
+    gradient or state under a sound matrix gives status 0 and a NaN trial (fmin / fmax alone would hand back a bound),
+    and the NaN masks and the status are the numpy branch's."""
+    ctx = _lib.default_context(0)
+    M = 65
+    for extras in (False, True):
+        case = nc.seeded(D, M, True, dtype, prior=extras, bounds=extras)
+        lam = np.array(nc.LAMBDAS, dtype)[np.arange(M) % 3]
+        for damping in ("diagonal", "identity"):
+            seen = []
+
+            def step_fn(c):
+                got = device_step(ctx, c, lam, damping)
+                cpu = _lib.newton_step_numpy(c["x"], c["grad"], c["A"], lam, damping, c["prior"], c["bounds"])
+                seen.append((got, cpu))
+                return got
+            nc.check_nan_into_the_clamp(step_fn, case)
+            for got, cpu in seen:
+                same(np.isnan(got[0]), np.isnan(cpu[0])), same(np.isnan(got[1]), np.isnan(cpu[1])), same(got[2], cpu[2])
+
+
 # ---- lm_update ------------------------------------------------------------------------------------------
 def prior_term(X, prior):
     return perband._prior_term(X.astype(np.float64), tuple(a.astype(np.float64) for a in prior)) if prior is not None else 0.0
@@ -301,6 +325,71 @@ def test_lm_update_against_numpy_exactly(gpu_lib, D, M, with_prior, dtype):
         same(ref[k][frozen | failed], c[k][frozen | failed])
     same(ref["lam"][frozen], c["lam"][frozen])
     assert not ref["accepted"][frozen | failed].any()
+
+
+def nonfinite_update_case(D, M, dtype, with_prior):
+    """``update_case`` with three more kinds on the rows m % 13 == 10, 11, 12, all active, with a sound status and a
+    finite trial cost below the current one where that is finite: 8 a NaN current cost, 9 a +inf current cost, 10 (with
+    a prior, which is then per row) a NaN in the row's own prior mean or, every second such row, precision."""
+    c = update_case(D, M, dtype, with_prior)
+    m = np.arange(M)
+    kind = c["kind"].copy()
+    kind[m % 13 == 10], kind[m % 13 == 11] = 8, 9
+    if with_prior:
+        kind[m % 13 == 12] = 10
+        x0 = np.ascontiguousarray(np.broadcast_to(c["prior"][0], (M, D)))
+        P = np.ascontiguousarray(np.broadcast_to(c["prior"][1], (M, D, D)))
+        holes = np.flatnonzero(kind == 10)
+        x0[holes[0::2], D // 2] = np.nan
+        P[holes[1::2], D - 1, 0] = np.nan
+        c["prior"] = (x0, P)
+    new = kind >= 8
+    c["cost"][kind == 8], c["cost"][kind == 9] = np.nan, np.inf
+    c["cost_t"][new] = 0.5 * np.where(np.isfinite(c["cost"][new]), c["cost"][new], 10.0)
+    c["status"][new], c["state"][new] = 0, 0
+    return dict(c, kind=kind)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("D,M,with_prior", [(3, 130, True), (16, 67, False), (11, 65, True), (1, 27, True)])
+def test_lm_update_nonfinite_current_cost_and_a_hole_in_the_row_prior(gpu_lib, D, M, with_prior, dtype):
+    """Everything the kernel writes equals ``_retrieve._lm_update_numpy`` exactly: a NaN F never accepts (a NaN current
+    cost, or a NaN in the row's own prior), a +inf F accepts any finite trial and converges at once (inf <= ftol inf)."""
+    ctx = _lib.default_context(0)
+    c = nonfinite_update_case(D, M, dtype, with_prior)
+    f64 = np.float64
+    ref = {k: c[k].astype(f64) for k in ("x", "cost", "grad", "A", "lam")}
+    ref["state"] = c["state"].copy()
+    prior = tuple(a.astype(f64) for a in c["prior"]) if with_prior else None
+    ref["accepted"] = _retrieve._lm_update_numpy(
+        ref["x"], c["trial"].astype(f64), ref["cost"], c["cost_t"].astype(f64), ref["grad"], c["grad_t"].astype(f64), ref["A"],
+        c["A_t"].astype(f64), ref["lam"], c["status"], ref["state"], prior, UPDATE["down"], UPDATE["up"], UPDATE["lambda_min"],
+        UPDATE["lambda_max"], UPDATE["ftol"], UPDATE["xtol"])
+    kind = c["kind"]
+    for k in (8, 9) + ((10,) if with_prior else ()):
+        assert np.any(kind == k)
+    assert not ref["accepted"][kind == 8].any() and not ref["accepted"][kind == 10].any()
+    assert ref["accepted"][kind == 9].all() and np.all(ref["state"][kind == 9] == 1)
+    for k in ("x", "cost", "grad", "A"):                                   # a never-accepting row keeps its own
+        same(ref[k][np.isin(kind, (8, 10))].astype(dtype), c[k][np.isin(kind, (8, 10))])
+    b = Buffers(ctx)
+    try:
+        d = {k: b.out(c[k]) for k in ("x", "cost", "lam", "state", "grad", "A")}
+        d["accepted"] = b.out(np.full(M, 7, np.int32))
+        ins = {k: b.up(c[k]) for k in ("trial", "cost_t", "status", "grad_t", "A_t")}
+        pr = [b.up(a) for a in (c["prior"] or (None, None))]
+        args = (dtype, d["x"], ins["trial"], d["cost"], ins["cost_t"], d["grad"], ins["grad_t"], d["A"], ins["A_t"], d["lam"],
+                ins["status"], d["state"], d["accepted"], M, D, pr[0], pr[1])
+        if with_prior:
+            ctx.lm_update_rows_device(*args, prior_mean_stride=D, prior_prec_stride=D * D, **UPDATE)
+        else:
+            ctx.lm_update_device(*args, **UPDATE)
+        shapes = dict(x=(M, D), cost=(M,), lam=(M,), state=(M,), accepted=(M,), grad=(M, D), A=(M, D, D))
+        for k, p in d.items():
+            int32 = k in ("state", "accepted")
+            same(b.down(p, shapes[k], np.int32 if int32 else dtype), ref[k] if int32 else ref[k].astype(dtype))
+    finally:
+        b.close()
 
 
 # ---- retrieve_bands -------------------------------------------------------------------------------------

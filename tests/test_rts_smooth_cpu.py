@@ -168,6 +168,18 @@ def test_status_is_the_propagation_s_and_failed_rows_are_nan(D, dtype):
         same(got[~bad], want)
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("D", [1, 3, 16, 17])
+def test_numpy_branch_carries_a_nan_through_the_clamp(D, dtype):
+    """smoother_cases.check_nan_into_the_clamp without and with bounds: a NaN state under sound matrices gives status 0
+    and a NaN smoothed state, as the kernel does."""
+    for bounds in (False, True):
+        case, P, Q = sc.case_for(D, 65, True, True, dtype, True, bounds=bounds)
+        x_next, cov_next = sc.successor(case, True)
+        sc.check_nan_into_the_clamp(lambda x, xn: _lib.rts_smooth_numpy(case["A"], P, Q, x, xn, cov_next, case["bounds"]),
+                                    case, x_next)
+
+
 def test_upper_triangles_are_not_read_and_repeated_arrays_are_the_shared_call():
     D, M = 11, 65
     shared, P1, Q1 = sc.case_for(D, M, False, True, np.float64, False)

@@ -152,6 +152,25 @@ def test_status_is_the_propagation_s_and_failed_rows_are_nan(gpu_lib, D, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("D", [1, 3, 16, 17])
+def test_a_nan_goes_through_the_clamp(gpu_lib, D, dtype):
+    """smoother_cases.check_nan_into_the_clamp on the device without and with bounds: a NaN state under sound matrices
+    gives status 0 and a NaN smoothed state (fmin / fmax alone would hand back a bound); the NaN mask and the status are
+    the numpy branch's."""
+    ctx = _lib.default_context(0)
+    for bounds in (False, True):
+        case, P, Q = sc.case_for(D, 65, True, True, dtype, True, bounds=bounds)
+        x_next, cov_next = sc.successor(case, True)
+
+        def smooth_fn(x, xn):
+            got = device_smooth(ctx, case["A"], P, Q, x, xn, cov_next, bounds=case["bounds"])
+            cpu = _lib.rts_smooth_numpy(case["A"], P, Q, x, xn, cov_next, case["bounds"])
+            same(np.isnan(got[0]), np.isnan(cpu[0])), same(got[3], cpu[3])
+            return got
+        sc.check_nan_into_the_clamp(smooth_fn, case, x_next)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("D", [3, 17])
 def test_bounds_clamp_the_smoothed_state_only(gpu_lib, D, dtype):
     ctx = _lib.default_context(0)
