@@ -1,7 +1,8 @@
 """The small dense solves in float64 numpy: the explicit CPU branches of ``Context.newton_step``, ``posterior_cov``,
-``prior_propagate`` and ``rts_smooth`` and of the retrievals, and the reference the CPU tests compare against.  Pure
-numpy: nothing here touches the library.  Every function is vectorised over the rows and written out as explicit loops
-in the kernels' summation order (csrc/gp_dense_device.hpp and the four kernel headers); never a fallback.
+``prior_propagate``, ``rts_smooth``, ``series_step`` and ``series_cov`` and of the retrievals, and the reference the CPU
+tests compare against.  Pure numpy: nothing here touches the library.  Every function is vectorised over the rows and
+written out as explicit loops in the kernels' summation order (csrc/gp_dense_device.hpp and the five kernel headers); never
+a fallback.
 """
 import numpy as np
 
@@ -117,10 +118,17 @@ def _cholesky_inverse_numpy(L):
     the inverse by the kernels' chains (ascending index in the factorisation and in both substitutions of every unit
     vector), NaN throughout where ``status`` (k + 1 for the first pivot that is not > 0 or not finite) is not 0.  Only
     the lower triangle of ``L`` is read."""
+    with np.errstate(all="ignore"):
+        status = _cholesky_factor_numpy(L)
+    return _factor_inverse_numpy(L, status), status
+
+
+def _factor_inverse_numpy(L, status):
+    """``W`` of ``_cholesky_inverse_numpy`` from the factors ``L`` (M, D, D) that ``_cholesky_factor_numpy`` left and
+    its ``status``."""
     M, D = L.shape[:2]
     W = np.zeros((M, D, D))                                         # W[:, i, j]: y_i, then z_i, of column j
     with np.errstate(all="ignore"):
-        status = _cholesky_factor_numpy(L)
         for i in range(D):                                           # y = L^-1 e_j, the columns j <= i side by side
             s = np.zeros((M, i + 1))
             s[:, i] = 1.0
@@ -133,7 +141,7 @@ def _cholesky_inverse_numpy(L):
                 a -= L[:, k, i][:, None] * W[:, k, :i + 1]
             W[:, i, :i + 1] = a / L[:, i, i][:, None]
         W[status != 0] = np.nan
-    return W, status
+    return W
 
 
 def _mirror_lower(W):
@@ -226,3 +234,210 @@ def rts_smooth_numpy(A, prior_prec, noise, x, x_next, cov_next, bounds=None):
     bad = status != 0
     xs[bad], cov[bad], sigma[bad] = np.nan, np.nan, np.nan
     return xs, cov, sigma, status
+
+
+def _series_factor_numpy(A, W, prior_prec, lam, damping):
+    """The forward sweep of the series kernels: ``(L, B, status)``, ``L[t]`` (M, D, D) the factor of
+    ``S_t = H'_tt - B_t B_t^T`` (lower triangle), ``B[t]`` (M, D, D) with ``B_t L_{t-1}^T = -W`` (``B[0]`` is None),
+    ``status`` (M,) int32: 0, or t D + k + 1 for the first failed pivot.  ``W`` is (M, D, D); ``lam`` None = no damping.
+    The caller holds ``np.errstate(all="ignore")``."""
+    T, M, D = A.shape[:3]
+    idx = np.arange(D)
+    Ls, Bs = [], [None]
+    status = np.zeros(M, np.int32)
+    for t in range(T):
+        H = np.array(A[t], dtype=np.float64)
+        if t == 0 and prior_prec is not None:
+            H = H + prior_prec
+        if t > 0:
+            H = H + W
+        if t < T - 1:
+            H = H + W
+        if lam is not None:
+            diag = H[:, idx, idx]
+            H[:, idx, idx] = diag + lam[:, None] * (diag if damping == "diagonal" else 1.0)
+        if t > 0:
+            B = Bs[t]
+            for k in range(D):
+                H -= B[:, :, k, None] * B[:, None, :, k]
+        st = _cholesky_factor_numpy(H)
+        status = np.where((status == 0) & (st != 0), t * D + st, status).astype(np.int32)
+        Ls.append(H)
+        if t < T - 1:
+            Bn = np.zeros((M, D, D))
+            for k in range(D):                                       # row i of B by substitution, the rows side by side
+                s = -W[:, :, k]
+                for q in range(k):
+                    s = s - Bn[:, :, q] * H[:, k, q][:, None]
+                Bn[:, :, k] = s / H[:, k, k][:, None]
+            Bs.append(Bn)
+    return Ls, Bs, status
+
+
+def _series_arrays(A, W, prior_prec):
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 4 or A.shape[2] != A.shape[3]:
+        raise ValueError("A must be (n_dates, n_rows, n_inputs, n_inputs)")
+    T, M, D = A.shape[:3]
+    Wm = np.broadcast_to(prec_rows(W, M, D), (M, D, D))
+    P = prec_rows(prior_prec, M, D) if prior_prec is not None else None
+    return A, Wm, P, T, M, D
+
+
+def series_step_numpy(x, grad, A, lam, W, damping="diagonal", prior=None, bounds=None):
+    """The block-tridiagonal damped Newton step of ``gp_series_step_device`` in float64 numpy, vectorised over the pixels
+    and written out in the kernel's order (csrc/gp_series_kernel.hpp): ``(step (T, M, D), trial (T, M, D), status (M,)
+    int32)`` for date-major ``x``, ``grad`` (T, M, D) and ``A`` (T, M, D, D).  The explicit CPU branch of
+    ``Context.series_step`` and of the joint retrievals, and the reference of the CPU tests; never a fallback.
+
+        H_tt = A_t (+ P, t = 0) (+ W, t > 0) (+ W, t < T-1),  H_t,t-1 = -W,
+        g'_t = grad_t (+ P (x_0 - x0)) + W (x_t - x_{t-1}) - W (x_{t+1} - x_t),  H'_dd = H_dd + lam * (H_dd | 1),
+        S_0 = H'_00, S_t = H'_tt - B_t B_t^T, L_t L_t^T = S_t, B_{t+1} L_t^T = -W, forward and backward substitutions,
+        trial = clip(x + step, lo, hi);  status = t D + k + 1 for the first failed pivot, then step = 0 and trial = x.
+
+    ``W`` is the precision of the process noise, (D, D) or (M, D, D); ``prior=(x0, P)`` is date 0's, shared or per
+    pixel; ``lam`` (M,) or a scalar.  With T = 1 this is ``newton_step_numpy`` bit for bit."""
+    if damping not in DAMPINGS:
+        raise ValueError("damping must be 'diagonal' or 'identity'")
+    x = np.array(x, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError("x must be (n_dates, n_rows, n_inputs)")
+    A, Wm, _, T, M, D = _series_arrays(A, W, None)
+    g = np.array(grad, dtype=np.float64).reshape(T, M, D)
+    lam = np.broadcast_to(np.asarray(lam, dtype=np.float64), (M,))
+    P = None
+    with np.errstate(all="ignore"):
+        if prior is not None:
+            x0, P = prior_rows(prior, M, D)
+            for c in range(D):
+                g[0] += P[..., :, c] * (x[0][:, c] - x0[..., c])[:, None]
+        for t in range(T):
+            if t > 0:
+                d = x[t] - x[t - 1]
+                for c in range(D):
+                    g[t] += Wm[:, :, c] * d[:, c, None]
+            if t < T - 1:
+                d = x[t + 1] - x[t]
+                for c in range(D):
+                    g[t] -= Wm[:, :, c] * d[:, c, None]
+        Ls, Bs, status = _series_factor_numpy(A, Wm, P, lam, damping)
+        ys = []
+        for t in range(T):                                           # y_t = L_t^-1 (g'_t - B_t y_{t-1})
+            L, y = Ls[t], g[t]
+            if t > 0:
+                for k in range(D):
+                    y -= Bs[t][:, :, k] * ys[t - 1][:, k, None]
+            for k in range(D):
+                y[:, k] = y[:, k] / L[:, k, k]
+                y[:, k + 1:] -= L[:, k + 1:, k] * y[:, k][:, None]
+            ys.append(y)
+        zs = [None] * T
+        for t in range(T - 1, -1, -1):                               # z_t = L_t^-T (y_t - B_{t+1}^T z_{t+1})
+            L, a_t = Ls[t], ys[t].copy()
+            if t < T - 1:
+                for k in range(D):
+                    a_t -= Bs[t + 1][:, k, :] * zs[t + 1][:, k, None]
+            z = np.zeros((M, D))
+            for i in range(D - 1, -1, -1):
+                a = a_t[:, i].copy()
+                for k in range(i + 1, D):
+                    a -= L[:, k, i] * z[:, k]
+                z[:, i] = a / L[:, i, i]
+            zs[t] = z
+        ok = (status == 0)[None, :, None]
+        step = np.where(ok, -np.stack(zs), 0.0)
+        trial = x + step
+        if bounds is not None:
+            trial = _clip(trial, bounds)
+        trial = np.where(ok, trial, x)
+    return step, trial, status
+
+
+def series_cov_numpy(A, W, prior_prec=None):
+    """The marginal posterior covariances of ``gp_series_cov_device`` in float64 numpy, in the kernel's order:
+    ``(cov (T, M, D, D), sigma (T, M, D), status (M,) int32)``.  The explicit CPU branch of ``Context.series_cov`` and
+    of the joint retrievals, and the reference of the CPU tests; never a fallback.
+
+        the forward factorisation of ``series_step_numpy`` without damping,  Sigma_{T-1} = (L L^T)^-1 as
+        ``posterior_cov_numpy``,  K_t = -L_t^-T B_{t+1}^T,  Sigma_t = (L_t L_t^T)^-1 + (K_t Sigma_{t+1}) K_t^T (lower
+        triangle computed, upper mirrored), every product a sum from 0 in ascending index;  sigma = sqrt(diag);  on a
+        failed pivot the pixel's outputs are NaN.
+
+    With T = 1 this is ``posterior_cov_numpy`` bit for bit."""
+    A, Wm, P, T, M, D = _series_arrays(A, W, prior_prec)
+    idx = np.arange(D)
+    with np.errstate(all="ignore"):
+        Ls, Bs, status = _series_factor_numpy(A, Wm, P, None, None)
+        covs = [None] * T
+        N = _mirror_lower(_factor_inverse_numpy(Ls[T - 1], status))
+        covs[T - 1] = N
+        for t in range(T - 2, -1, -1):
+            L, B = Ls[t], Bs[t + 1]
+            K = np.zeros((M, D, D))
+            for k in range(D - 1, -1, -1):                           # column r of K by back substitution, side by side
+                s = -B[:, :, k]
+                for q in range(k + 1, D):
+                    s = s - L[:, q, k][:, None] * K[:, q, :]
+                K[:, k, :] = s / L[:, k, k][:, None]
+            C = _mirror_lower(_factor_inverse_numpy(L, np.zeros(M, np.int32)))
+            F, Kx = np.zeros((M, D, D)), np.zeros((M, D, D))
+            for l in range(D):
+                F += K[:, :, l, None] * N[:, None, l, :]
+            for k in range(D):
+                Kx += F[:, :, k, None] * K[:, None, :, k]
+            N = _mirror_lower(C + Kx)
+            N[status != 0] = np.nan
+            covs[t] = N
+        cov = np.stack(covs)
+        sigma = np.sqrt(cov[:, :, idx, idx])
+    return cov, sigma, status
+
+
+def _quadratic_numpy(d, P):
+    """1/2-less ``d^T P d`` per row, outer and inner index ascending as the update kernels sum it."""
+    D = d.shape[1]
+    q = np.zeros(d.shape[0])
+    for i in range(D):
+        ri = np.zeros(d.shape[0])
+        for c in range(D):
+            ri += P[..., i, c] * d[:, c]
+        q += d[:, i] * ri
+    return q
+
+
+def series_objective_numpy(X, cost, prior, W):
+    """``F`` (M,) of the trajectories ``X`` (T, M, D) with the data terms ``cost`` (T, M): the sum of the costs over t
+    ascending, the prior term on date 0, then 1/2 d_t^T W d_t for t ascending -- ``gp_series_update_device``'s order."""
+    T, M, D = X.shape
+    F = np.zeros(M)
+    for t in range(T):
+        F = F + cost[t]
+    if prior is not None:
+        F = F + 0.5 * _quadratic_numpy(X[0] - prior[0], prior[1])
+    for t in range(1, T):
+        F = F + 0.5 * _quadratic_numpy(X[t] - X[t - 1], W)
+    return F
+
+
+def series_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, status, state, prior, W, down, up, lam_min,
+                        lam_max, ftol, xtol, F_out=None):
+    """``gp_series_update_device`` in float64 numpy, in place on ``X`` (T, M, D), ``cost`` (T, M), ``grad``, ``A``,
+    ``lam``, ``state`` (and ``F_out`` (M,), the objective of the state each active pixel is left with); returns
+    ``accepted`` (M,) int32.  ``prior = (x0, P)`` as ``prior_rows`` returns it, or None; ``W`` (D, D) or (M, D, D)."""
+    active = state == 0
+    with np.errstate(all="ignore"):
+        F, Ft = series_objective_numpy(X, cost, prior, W), series_objective_numpy(trial, cost_t, prior, W)
+        accept = active & (np.asarray(status) == 0) & np.isfinite(Ft) & (Ft < F)
+        conv = ((F - Ft) <= ftol * F) | (np.max(np.abs(trial - X), axis=(0, 2)) <= xtol)
+    reject = active & ~accept
+    X[:, accept], cost[:, accept] = trial[:, accept], cost_t[:, accept]
+    if grad is not None:
+        grad[:, accept] = grad_t[:, accept]
+    if A is not None:
+        A[:, accept] = A_t[:, accept]
+    lam[accept] = np.maximum(lam[accept] * down, lam_min)
+    lam[reject] = np.minimum(lam[reject] * up, lam_max)
+    state[accept & conv] = 1
+    if F_out is not None:
+        F_out[accept], F_out[reject] = Ft[accept], F[reject]
+    return accept.astype(np.int32)

@@ -13,7 +13,8 @@ import threading
 import numpy as np
 
 from ._dense_numpy import (DAMPINGS, newton_step_numpy, posterior_cov_numpy, prec_rows, prior_propagate_numpy,  # noqa: F401
-                           prior_rows, row_strides, rts_smooth_numpy, _cholesky_inverse_numpy, _mirror_lower)
+                           prior_rows, row_strides, rts_smooth_numpy, series_cov_numpy, series_objective_numpy,
+                           series_step_numpy, series_update_numpy, _cholesky_inverse_numpy, _mirror_lower)
 from ._lut_numpy import MAX_PCS as lut_pc_max_pcs  # noqa: F401
 from ._lut_numpy import lut_pc_prepare_numpy, lut_search_numpy, lut_search_pc_numpy  # noqa: F401
 from ._moments_numpy import rows_arrays as _moments_rows
@@ -89,6 +90,13 @@ SIGNATURES = {
     "gp_posterior_cov_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_i64, c_int, c_i64]),
     "gp_prior_propagate_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int]),
     "gp_rts_smooth_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 9 + [c_i64, c_int]),
+    "gp_series_work_bytes": (c_i64, [c_i64, c_int, c_int]),
+    "gp_series_step_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
+                              + [c_void_p] * 6 + [c_i64, c_i64, c_int, c_int]),
+    "gp_series_update_device": (c_int, [c_void_p, c_int] + [c_void_p] * 13 + [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64]
+                                + [ctypes.c_double] * 6 + [c_i64, c_int, c_int]),
+    "gp_series_cov_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64] + [c_void_p] * 4
+                             + [c_i64, c_i64, c_int, c_int]),
     "gp_lut_search_device": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
                                      c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int]),
     "gp_lut_search_geometry": (c_int, [ctypes.POINTER(c_int)] * 3),
@@ -281,6 +289,26 @@ def _matrix_rows(A, precision):
     if A.ndim != 3 or A.shape[1] != A.shape[2]:
         raise ValueError("A must be (n_rows, n_inputs, n_inputs)")
     return A, _device_dtype(precision, A), A.shape[0], A.shape[1]
+
+
+SERIES_WORK_BUDGET = 1 << 30      # bytes of work memory one joint-series call may take: the pixels are sliced under it
+
+
+def series_work_bytes(n_rows, n_dates, n_inputs):
+    """The work memory ``gp_series_step_device`` / ``gp_series_cov_device`` need for these sizes, in bytes."""
+    n = load().gp_series_work_bytes(int(n_rows), int(n_dates), int(n_inputs))
+    if n < 0:
+        raise ValueError("series sizes out of range: %d rows, %d dates, %d inputs" % (n_rows, n_dates, n_inputs))
+    return n
+
+
+def series_slices(n_rows, n_dates, n_inputs, budget=SERIES_WORK_BUDGET):
+    """``[(m0, m1), ...]``: the pixels cut into runs whose work memory stays under ``budget`` bytes (at least one
+    wave's pixels per run).  Pixels are independent, so the cut changes no bit of any result."""
+    per_wave = series_work_bytes(1, n_dates, n_inputs)          # (a wave's 4 or 2 pixels)
+    group = 4 if n_inputs <= 16 else 2
+    n = max(1, int(budget) // per_wave) * group
+    return [(m0, min(m0 + n, n_rows)) for m0 in range(0, n_rows, n)]
 
 
 def device_numa_cpus(device=0):
@@ -645,6 +673,122 @@ class Context:
                                    d_lo, d_hi, d_xs, d_cov, d_sigma, d_status, M, D)
             return (_download(self, d_xs, (M, D), dt), _download(self, d_cov, (M, D, D), dt),
                     _download(self, d_sigma, (M, D), dt), _download(self, d_status, (M,), np.int32))
+
+    def series_step_device(self, dtype, d_x, d_grad, d_A, d_lambda, d_W, w_stride, d_step, d_trial, d_status, d_work,
+                           work_bytes, n_rows, n_dates, n_inputs, damping="diagonal", d_prior_mean=None, d_prior_prec=None,
+                           d_lo=None, d_hi=None, prior_mean_stride=0, prior_prec_stride=0):
+        """Asynchronous block-tridiagonal damped Newton step of ``n_rows`` trajectories of ``n_dates`` dates on the
+        device (``gp_series_step_device``): date-major ``d_x``, ``d_grad`` [T][M][D] and ``d_A`` [T][M][D][D], the
+        prior on date 0 (shared, stride 0, or per pixel), ``d_W`` the precision of the process noise ([D][D], stride 0,
+        or [M][D][D]); ``status`` int32 (0, or t * D + k + 1 for the first failed pivot: then step = 0, trial = x).
+        ``d_work`` holds at least ``series_work_bytes(n_rows, n_dates, n_inputs)`` bytes.  The prior pair, the bounds
+        pair and one of ``d_step`` / ``d_trial`` may be None."""
+        check(self.lib.gp_series_step_device(self.h, _dtype_code(dtype), d_x, d_grad, d_A, d_lambda, _DAMPING[damping],
+                                             d_prior_mean, int(prior_mean_stride), d_prior_prec, int(prior_prec_stride), d_W,
+                                             int(w_stride), d_lo, d_hi, d_step, d_trial, d_status, d_work, int(work_bytes),
+                                             int(n_rows), int(n_dates), int(n_inputs)), "gp_series_step_device")
+
+    def series_update_device(self, dtype, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A, d_A_trial, d_lambda,
+                             d_status, d_state, d_accepted, d_F, d_W, w_stride, n_rows, n_dates, n_inputs, d_prior_mean=None,
+                             d_prior_prec=None, down=1.0 / 3.0, up=4.0, lambda_min=1e-12, lambda_max=1e12, ftol=1e-10,
+                             xtol=0.0, prior_mean_stride=0, prior_prec_stride=0):
+        """Asynchronous Levenberg-Marquardt accept / reject of whole trial trajectories on the device
+        (``gp_series_update_device``): a pixel with ``state == 0`` whose trial lowers the joint objective takes the
+        trial's x, cost, grad and A on all dates and ``lambda * down``, the others ``lambda * up``.  The grad pair, the
+        A pair, ``d_accepted``, ``d_F`` (the objective the pixel is left with) and the prior pair may be None."""
+        check(self.lib.gp_series_update_device(self.h, _dtype_code(dtype), d_x, d_trial, d_cost, d_cost_trial, d_grad,
+                                               d_grad_trial, d_A, d_A_trial, d_lambda, d_status, d_state, d_accepted, d_F,
+                                               d_prior_mean, int(prior_mean_stride), d_prior_prec, int(prior_prec_stride),
+                                               d_W, int(w_stride), float(down), float(up), float(lambda_min),
+                                               float(lambda_max), float(ftol), float(xtol), int(n_rows), int(n_dates),
+                                               int(n_inputs)), "gp_series_update_device")
+
+    def series_cov_device(self, dtype, d_A, d_prior_prec, prior_prec_stride, d_W, w_stride, d_cov, d_sigma, d_status, d_work,
+                          work_bytes, n_rows, n_dates, n_inputs):
+        """Asynchronous marginal posterior covariances of ``n_rows`` trajectories on the device
+        (``gp_series_cov_device``): ``cov`` [T][M][D][D] symmetric bit for bit, ``sigma`` [T][M][D], ``status`` as the
+        step's (then the pixel's outputs are NaN).  ``d_prior_prec`` and one of ``d_cov`` / ``d_sigma`` may be None."""
+        check(self.lib.gp_series_cov_device(self.h, _dtype_code(dtype), d_A, d_prior_prec, int(prior_prec_stride), d_W,
+                                            int(w_stride), d_cov, d_sigma, d_status, d_work, int(work_bytes), int(n_rows),
+                                            int(n_dates), int(n_inputs)), "gp_series_cov_device")
+
+    def series_step(self, x, grad, A, lam, W, damping="diagonal", prior=None, bounds=None, precision=None, is_gpu=True,
+                    work_budget=SERIES_WORK_BUDGET):
+        """``(step (T, M, D), trial (T, M, D), status (M,))`` of the block-tridiagonal damped Newton step for the
+        date-major host arrays ``x``, ``grad`` (T, M, D), ``A`` (T, M, D, D), ``lam`` (M,) or a scalar and ``W`` the
+        precision of the process noise, (D, D) or (M, D, D): uploads, launches ``gp_series_step_device`` on slices of
+        pixels whose work memory stays under ``work_budget`` bytes (the slicing changes no bit), downloads.
+        ``prior=(x0, P)`` is date 0's, each shared or per pixel; ``bounds=(lo, hi)``.  ``precision`` is the device
+        dtype (default: float32 when ``x`` is float32, else float64).  ``is_gpu=False`` is the explicit numpy branch
+        (``series_step_numpy``: the same algorithm in float64); never a fallback."""
+        if not is_gpu:
+            return series_step_numpy(x, grad, A, lam, W, damping, prior, bounds)
+        if damping not in _DAMPING:
+            raise ValueError("damping must be 'diagonal' or 'identity'")
+        x = np.asarray(x)
+        if x.ndim != 3:
+            raise ValueError("x must be (n_dates, n_rows, n_inputs)")
+        dt = _device_dtype(precision, x)
+        T, M, D = x.shape
+        x, grad, A = (np.ascontiguousarray(a, dtype=dt) for a in (x, np.reshape(grad, (T, M, D)), np.reshape(A, (T, M, D, D))))
+        lam = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=dt), (M,)))
+        x0, P = prior_rows(prior, M, D, dt) if prior is not None else (None, None)
+        Wm = prec_rows(W, M, D, dt)
+        lo, hi = [np.reshape(b, D) for b in bounds] if bounds is not None else (None, None)
+        step, trial, status = np.empty((T, M, D), dt), np.empty((T, M, D), dt), np.empty(M, np.int32)
+        isz = dt.itemsize
+        for m0, m1 in series_slices(M, T, D, work_budget):
+            n = m1 - m0
+            with Scratch(self, dt) as scratch:
+                up_ = scratch.up
+                d_x, d_g, d_A, d_lam = up_(x[:, m0:m1]), up_(grad[:, m0:m1]), up_(A[:, m0:m1]), up_(lam[m0:m1])
+                d_x0 = up_(x0[m0:m1] if x0 is not None and x0.ndim == 2 else x0)
+                d_P = up_(P[m0:m1] if P is not None and P.ndim == 3 else P)
+                d_W, d_lo, d_hi = up_(Wm[m0:m1] if Wm.ndim == 3 else Wm), up_(lo), up_(hi)
+                nbytes = series_work_bytes(n, T, D)
+                d_step, d_trial, d_status, d_work = (scratch.alloc(T * n * D * isz), scratch.alloc(T * n * D * isz),
+                                                     scratch.alloc(n * 4), scratch.alloc(nbytes))
+                strides = row_strides(x0, P)
+                self.series_step_device(dt, d_x, d_g, d_A, d_lam, d_W, row_strides(None, Wm)[1], d_step, d_trial, d_status,
+                                        d_work, nbytes, n, T, D, damping, d_x0, d_P, d_lo, d_hi, *strides)
+                step[:, m0:m1] = _download(self, d_step, (T, n, D), dt)
+                trial[:, m0:m1] = _download(self, d_trial, (T, n, D), dt)
+                status[m0:m1] = _download(self, d_status, (n,), np.int32)
+        return step, trial, status
+
+    def series_cov(self, A, W, prior_prec=None, precision=None, is_gpu=True, work_budget=SERIES_WORK_BUDGET):
+        """``(cov (T, M, D, D), sigma (T, M, D), status (M,))`` of the marginal posterior covariances of the joint
+        problem for the date-major host array ``A`` (T, M, D, D), ``W`` (D, D) or (M, D, D) and date 0's
+        ``prior_prec`` None, (D, D) or (M, D, D): uploads, launches ``gp_series_cov_device`` on slices of pixels under
+        ``work_budget`` bytes of work memory, downloads.  ``is_gpu=False`` is the explicit numpy branch
+        (``series_cov_numpy``); never a fallback."""
+        if not is_gpu:
+            return series_cov_numpy(A, W, prior_prec)
+        A = np.asarray(A)
+        if A.ndim != 4 or A.shape[2] != A.shape[3]:
+            raise ValueError("A must be (n_dates, n_rows, n_inputs, n_inputs)")
+        dt = _device_dtype(precision, A)
+        T, M, D = A.shape[:3]
+        A = np.ascontiguousarray(A, dtype=dt)
+        P = prec_rows(prior_prec, M, D, dt) if prior_prec is not None else None
+        Wm = prec_rows(W, M, D, dt)
+        cov, sigma, status = np.empty((T, M, D, D), dt), np.empty((T, M, D), dt), np.empty(M, np.int32)
+        isz = dt.itemsize
+        for m0, m1 in series_slices(M, T, D, work_budget):
+            n = m1 - m0
+            with Scratch(self, dt) as scratch:
+                up_ = scratch.up
+                d_A, d_P = up_(A[:, m0:m1]), up_(P[m0:m1] if P is not None and P.ndim == 3 else P)
+                d_W = up_(Wm[m0:m1] if Wm.ndim == 3 else Wm)
+                nbytes = series_work_bytes(n, T, D)
+                d_cov, d_sigma, d_status, d_work = (scratch.alloc(T * n * D * D * isz), scratch.alloc(T * n * D * isz),
+                                                    scratch.alloc(n * 4), scratch.alloc(nbytes))
+                self.series_cov_device(dt, d_A, d_P, row_strides(None, P)[1], d_W, row_strides(None, Wm)[1], d_cov, d_sigma,
+                                       d_status, d_work, nbytes, n, T, D)
+                cov[:, m0:m1] = _download(self, d_cov, (T, n, D, D), dt)
+                sigma[:, m0:m1] = _download(self, d_sigma, (T, n, D), dt)
+                status[m0:m1] = _download(self, d_status, (n,), np.int32)
+        return cov, sigma, status
 
     def posterior_cov(self, A, prior_prec=None, precision=None, is_gpu=True):
         """``(cov (M, D, D), sigma (M, D), status (M,) int32)`` of the posterior covariance ``(A + P)^-1`` for the host

@@ -158,6 +158,141 @@ def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, 
     return out
 
 
+def lm_series_numpy(data_term, X0, W, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov):
+    """The loop over whole trajectories on the host in float64: the joint objective of DESIGN.md §4.23 from ``X0``
+    (T, M, D).  ``data_term(rows (T M, D)) -> (cost, grad, A)`` is one call on all dates' rows, date-major; the step is
+    ``_lib.series_step_numpy`` (diagonal damping), the decision ``_lib.series_update_numpy``, on ``lm_numpy``'s
+    schedule and constants.  ``W`` is the precision of the process noise, ``prior`` date 0's (as ``prior_and_bounds``
+    returns it).  Returns ``(X (T, M, D), sigma (T, M, D), cost (T, M), F (M,), state, n_accepted, lam, cov_status)``,
+    with ``return_cov`` ``cov (T, M, D, D)`` behind them: ``_lib.series_cov_numpy`` of the loop's ``A``.  ``F`` is the
+    joint objective the last decision left a pixel with (NaN for a pixel no decision was made for)."""
+    T, M, D = X0.shape
+
+    def term(X):
+        cost, grad, A = data_term(X.reshape(T * M, D))
+        return np.array(cost).reshape(T, M), np.array(grad).reshape(T, M, D), np.array(A).reshape(T, M, D, D)
+    X = np.array(X0, dtype=np.float64)
+    lam, F = np.full(M, float(lam0)), np.full(M, np.nan)
+    state, n_acc = np.zeros(M, np.int32), np.zeros(M, np.int32)
+    cost, grad, A = term(X)
+    for it in range(max_iter):
+        _, trial, status = _lib.series_step_numpy(X, grad, A, lam, W, "diagonal", prior, bounds)
+        cost_t, grad_t, A_t = term(trial)
+        n_acc += _lib.series_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, status, state, prior, W, down, up,
+                                          LAMBDA_MIN, LAMBDA_MAX, ftol, xtol, F_out=F)
+        if it % 4 == 3 and np.all(state == 1):
+            break
+    cov, sigma, cstat = _lib.series_cov_numpy(A, W, prior[1] if prior is not None else None)
+    return (X, sigma, cost, F, state, n_acc, lam, cstat) + ((cov,) if return_cov else ())
+
+
+def lm_series_device(scratch, X0, W, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov, misfit):
+    """``lm_series_numpy`` on the device, in the precision and on the context of ``scratch``: ``misfit(d_rows, d_cost,
+    d_grad, d_A)`` enqueues the data term of the T M date-major rows at ``d_rows``.  Every iteration is that,
+    ``series_update_device`` and ``series_step_device`` on the one stream; nothing comes back inside the loop but
+    ``state``, every fourth iteration.  After the loop one ``series_cov_device`` call on the loop's own arrays.  The
+    work memory of the two kernels is allocated once, in the scratch: the caller slices the pixels under its budget."""
+    ctx, dt = scratch.ctx, scratch.dt
+    up_, alloc, isz = scratch.up, scratch.alloc, dt.itemsize
+    T, M, D = X0.shape
+    R = T * M
+    d_x, d_lam, d_F = up_(X0), up_(np.full(M, float(lam0))), up_(np.full(M, np.nan))
+    d_x0, d_P = (up_(prior[0]), up_(prior[1])) if prior is not None else (None, None)
+    d_lo, d_hi = (up_(bounds[0]), up_(bounds[1])) if bounds is not None else (None, None)
+    d_W, ws = up_(W), _lib.row_strides(None, W)[1]
+    d_cost, d_grad, d_A = alloc(R * isz), alloc(R * D * isz), alloc(R * D * D * isz)
+    d_cost_t, d_grad_t, d_A_t = alloc(R * isz), alloc(R * D * isz), alloc(R * D * D * isz)
+    d_trial, d_status, d_state = alloc(R * D * isz), alloc(M * 4), alloc(M * 4)
+    d_acc = alloc(max(1, max_iter) * M * 4)    # one (M,) slice per iteration, summed after the loop
+    nbytes = _lib.series_work_bytes(M, T, D)
+    d_work = alloc(nbytes)
+    _lib.check(ctx.lib.gp_memset(ctx.h, d_state, 0, M * 4), "gp_memset")
+    ms, ps = _lib.row_strides(*prior) if prior is not None else (0, 0)
+
+    def step():
+        ctx.series_step_device(dt, d_x, d_grad, d_A, d_lam, d_W, ws, None, d_trial, d_status, d_work, nbytes, M, T, D,
+                               "diagonal", d_x0, d_P, d_lo, d_hi, ms, ps)
+    misfit(d_x, d_cost, d_grad, d_A)
+    step()
+    done = 0
+    for it in range(max_iter):
+        misfit(d_trial, d_cost_t, d_grad_t, d_A_t)
+        ctx.series_update_device(dt, d_x, d_trial, d_cost, d_cost_t, d_grad, d_grad_t, d_A, d_A_t, d_lam, d_status, d_state,
+                                 _lib.c_void_p(d_acc.value + it * M * 4), d_F, d_W, ws, M, T, D, d_x0, d_P, down, up,
+                                 LAMBDA_MIN, LAMBDA_MAX, ftol, xtol, ms, ps)
+        step()
+        done = it + 1
+        if it % 4 == 3:                       # (the copy synchronises the stream first)
+            ctx.synchronize()
+            if np.all(np.asarray(ctx.to_host(d_state, (M,), np.int32)) == 1):
+                break
+    d_cov = alloc(R * D * D * isz) if return_cov else None
+    d_sigma, d_cstat = alloc(R * D * isz), alloc(M * 4)
+    ctx.series_cov_device(dt, d_A, d_P, ps, d_W, ws, d_cov, d_sigma, d_cstat, d_work, nbytes, M, T, D)
+    ctx.synchronize()
+    down_ = lambda p, shape, t=dt: np.array(ctx.to_host(p, shape, t))
+    n_acc = down_(d_acc, (done, M), np.int32).sum(axis=0, dtype=np.int32) if done else np.zeros(M, np.int32)
+    out = (down_(d_x, (T, M, D)), down_(d_sigma, (T, M, D)), down_(d_cost, (T, M)), down_(d_F, (M,)),
+           down_(d_state, (M,), np.int32), n_acc, down_(d_lam, (M,)), down_(d_cstat, (M,), np.int32))
+    return out + ((down_(d_cov, (T, M, D, D)),) if return_cov else ())
+
+
+def series_precision(noise, M, D, context=None, dt=np.float64):
+    """``W = Q^-1`` for the process noise ``noise`` (D, D) or (M, D, D), inverted once: on the device ``context`` with
+    ``gp_posterior_cov_device(A = Q)`` in the precision ``dt``, without one by ``_lib.posterior_cov_numpy``.  A shared
+    ``Q`` that does not factor raises ``ValueError``; a pixel's own that does not leaves that pixel a NaN ``W``."""
+    Q = _lib.prec_rows(noise, M, D)
+    rows = Q if Q.ndim == 3 else Q[None]
+    if context is None:
+        W, _, status = _lib.posterior_cov_numpy(rows)
+    else:
+        W, _, status = context.posterior_cov(np.ascontiguousarray(rows, dtype=dt), None, precision=dt)
+    if Q.ndim == 2:
+        if status[0] != 0:
+            raise ValueError("noise is not positive definite (pivot %d fails): the joint form needs its inverse" % (status[0] - 1))
+        return W[0]
+    return W
+
+
+JOINT_AXES = (1, 1, 1, 0, 0, 0, 0, 0, 1)     # the pixel axis of what the joint loops return
+
+
+def retrieve_joint(X0, prior, noise, bounds, lam0, max_iter, down, up, ftol, xtol, return_cov, numpy_term=None,
+                   device_term=None, context=None, precision=np.float64, work_budget=None):
+    """The joint retrieval of both emulator types behind their argument checks: ``X0`` (T, M, D).  On the host
+    (``numpy_term(m0, m1)`` gives the data term of those pixels' T (m1 - m0) date-major rows) one ``lm_series_numpy``.
+    On the device ``context`` the pixels are cut into runs whose work memory stays under ``work_budget`` bytes
+    (``_lib.series_slices``) and every run is one ``lm_series_device`` in a scratch of its own, its data term from
+    ``device_term(scratch, m0, m1)``; pixels are independent, so the cut changes no bit."""
+    T, M, D = X0.shape
+    prior, bounds = prior_and_bounds(prior, bounds, D, M)
+    max_iter = int(max_iter)
+    if numpy_term is not None:
+        W = series_precision(noise, M, D)
+        return lm_series_numpy(numpy_term(0, M), X0, W, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov)
+    dt = np.dtype(precision)
+    W = series_precision(noise, M, D, context, dt)
+    budget = _lib.SERIES_WORK_BUDGET if work_budget is None else work_budget
+    parts = []
+    for m0, m1 in _lib.series_slices(M, T, D, budget):
+        cut = lambda a, nd: np.ascontiguousarray(a[m0:m1]) if a.ndim == nd else a
+        with Scratch(context, dt) as scratch:
+            parts.append(lm_series_device(scratch, np.ascontiguousarray(X0[:, m0:m1]), cut(W, 3), lam0,
+                                          (cut(prior[0], 2), cut(prior[1], 3)), bounds, max_iter, down, up, ftol, xtol,
+                                          return_cov, device_term(scratch, m0, m1)))
+    return tuple(np.concatenate([p[k] for p in parts], axis=ax) for k, ax in zip(range(len(parts[0])), JOINT_AXES))
+
+
+def joint_start(X0, T, name="X0"):
+    """``X0`` (T, M, D), or (M, D) taken for every date, as a float64 (T, M, D) array."""
+    X0 = np.asarray(X0, dtype=np.float64)
+    if X0.ndim == 2:
+        X0 = np.broadcast_to(X0, (T,) + X0.shape)
+    if X0.ndim != 3 or X0.shape[0] != T:
+        raise ValueError("%s must be (n_rows, n_inputs) or (%d, n_rows, n_inputs), got %s" % (name, T, X0.shape))
+    return np.ascontiguousarray(X0)
+
+
 def smooth_numpy(A, P, noise, X, cov_last, sigma_last, bounds):
     """The backward pass of a series on the host: ``_lib.rts_smooth_numpy`` for t = T-2 .. 0 on the dates' ``A[t]``,
     ``P[t]`` and filtered states ``X[t]``, started from the last date's state and covariance.  Returns ``(X_s (T, M, D),

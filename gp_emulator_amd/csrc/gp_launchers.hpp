@@ -19,6 +19,9 @@ template <typename T> struct LmUpdateArgs;
 template <typename T> struct PosteriorCovArgs;
 template <typename T> struct PriorPropagateArgs;
 template <typename T> struct RtsSmoothArgs;
+template <typename T> struct SeriesStepArgs;
+template <typename T> struct SeriesCovArgs;
+template <typename T> struct SeriesUpdateArgs;
 template <typename T> struct ReconArgs;
 template <typename T> struct MisfitArgs;
 template <typename T> struct GramArgs;
@@ -52,6 +55,9 @@ template <typename T> hipError_t launch_lm_update(const LmUpdateArgs<T>&, hipStr
 template <typename T> hipError_t launch_posterior_cov(const PosteriorCovArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_prior_propagate(const PriorPropagateArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_rts_smooth(const RtsSmoothArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_series_step(const SeriesStepArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_series_cov(const SeriesCovArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_series_update(const SeriesUpdateArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_reconstruct(const ReconArgs<T>&, int wide, int cus, hipStream_t);
 template <typename T> hipError_t launch_misfit(const MisfitArgs<T>&, int cus, hipStream_t);
 template <typename T> hipError_t launch_gauss_newton(const T* deriv, const T* A, T* gn, long long M, int P, int D, int cus, hipStream_t);

@@ -1,5 +1,5 @@
 // The small dense solves on device buffers: damped Newton step, LM update, posterior covariance, prior propagation and
-// the smoother's backward step; and the look-up-table search that starts a retrieval.  Device arrays in, device arrays
+// the smoother's backward step, the joint step, update and covariance of a whole series; and the look-up-table search that starts a retrieval.  Device arrays in, device arrays
 // out, no model.  The Sobol indices of a batch of emulators and their moments under a Gaussian input, on host arrays
 // (no model either).
 #include "gp_host.hpp"
@@ -12,6 +12,7 @@
 #include "gp_posterior_cov_kernel.hpp"
 #include "gp_prior_propagate_kernel.hpp"
 #include "gp_rts_smooth_kernel.hpp"
+#include "gp_series_kernel.hpp"
 #include "gp_moments_args.hpp"
 #include "gp_sobol_args.hpp"
 
@@ -237,6 +238,156 @@ int gp_rts_smooth_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_
     a.rows = n_rows;
     a.d = n_inputs;
     return launched(gpk::launch_rts_smooth<T>(a, ctx->stream), "smoother");
+  });
+}
+
+int64_t gp_series_work_bytes(int64_t n_rows, int n_dates, int n_inputs) {
+  if (n_rows <= 0 || n_dates <= 0 || n_inputs <= 0 || n_inputs > gpk::kNewtonMaxD) return -1;
+  return (int64_t)gpk::series_work_bytes(n_rows, n_dates, n_inputs);
+}
+
+// what the three series entries check alike: sizes, the prior pair's and W's strides, the work memory
+static int series_sizes(int dtype, int64_t n_rows, int n_dates, int n_inputs, const void* d_prior_mean, bool with_mean,
+                        int64_t prior_mean_stride, const void* d_prior_prec, int64_t prior_prec_stride, const void* d_W,
+                        int64_t w_stride) {
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (n_dates <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (!d_W) return fail(GP_ERR_INVALID, "null device pointer");
+  if (with_mean && (d_prior_mean != nullptr) != (d_prior_prec != nullptr))
+    return fail(GP_ERR_INVALID, "prior mean and prior precision go together");
+  if (with_mean)
+    if (int rc = row_stride("prior mean", d_prior_mean, prior_mean_stride, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  if (int rc = row_stride("noise precision", d_W, w_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  return GP_OK;
+}
+
+static int series_work(const void* d_work, int64_t work_bytes, int64_t n_rows, int n_dates, int n_inputs) {
+  if (!d_work) return fail(GP_ERR_INVALID, "null device pointer");
+  const int64_t need = (int64_t)gpk::series_work_bytes(n_rows, n_dates, n_inputs);
+  if (work_bytes < need)
+    return fail(GP_ERR_INVALID, "work memory of %lld bytes, %lld needed", (long long)work_bytes, (long long)need);
+  return GP_OK;
+}
+
+int gp_series_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A, const void* d_lambda,
+                          int damping, const void* d_prior_mean, int64_t prior_mean_stride, const void* d_prior_prec,
+                          int64_t prior_prec_stride, const void* d_W, int64_t w_stride, const void* d_lo, const void* d_hi,
+                          void* d_step, void* d_trial, int32_t* d_status, void* d_work, int64_t work_bytes, int64_t n_rows,
+                          int n_dates, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_x || !d_grad || !d_A || !d_lambda || !d_status || (!d_step && !d_trial))
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = series_sizes(dtype, n_rows, n_dates, n_inputs, d_prior_mean, true, prior_mean_stride, d_prior_prec,
+                            prior_prec_stride, d_W, w_stride))
+    return rc;
+  if (damping != GP_DAMP_DIAGONAL && damping != GP_DAMP_IDENTITY) return fail(GP_ERR_INVALID, "bad damping %d", damping);
+  if ((d_lo != nullptr) != (d_hi != nullptr)) return fail(GP_ERR_INVALID, "lower and upper bounds go together");
+  if (int rc = series_work(d_work, work_bytes, n_rows, n_dates, n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::SeriesStepArgs<T> a;
+    a.x = as<T>(d_x);
+    a.grad = as<T>(d_grad);
+    a.A = as<T>(d_A);
+    a.lambda = as<T>(d_lambda);
+    a.prior_mean = as<T>(d_prior_mean);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_mean_stride = prior_mean_stride;
+    a.prior_prec_stride = prior_prec_stride;
+    a.W = as<T>(d_W);
+    a.w_stride = w_stride;
+    a.lo = as<T>(d_lo);
+    a.hi = as<T>(d_hi);
+    a.step = as<T>(d_step);
+    a.trial = as<T>(d_trial);
+    a.status = d_status;
+    a.work = (double*)d_work;
+    a.rows = n_rows;
+    a.dates = n_dates;
+    a.d = n_inputs;
+    a.diagonal = damping == GP_DAMP_DIAGONAL ? 1 : 0;
+    return launched(gpk::launch_series_step<T>(a, ctx->stream), "series step");
+  });
+}
+
+int gp_series_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost, const void* d_cost_trial,
+                            void* d_grad, const void* d_grad_trial, void* d_A, const void* d_A_trial, void* d_lambda,
+                            const int32_t* d_status, int32_t* d_state, int32_t* d_accepted, void* d_F,
+                            const void* d_prior_mean, int64_t prior_mean_stride, const void* d_prior_prec,
+                            int64_t prior_prec_stride, const void* d_W, int64_t w_stride, double down, double up,
+                            double lambda_min, double lambda_max, double ftol, double xtol, int64_t n_rows, int n_dates,
+                            int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_x || !d_trial || !d_cost || !d_cost_trial || !d_lambda || !d_status || !d_state)
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = series_sizes(dtype, n_rows, n_dates, n_inputs, d_prior_mean, true, prior_mean_stride, d_prior_prec,
+                            prior_prec_stride, d_W, w_stride))
+    return rc;
+  if ((d_grad != nullptr) != (d_grad_trial != nullptr) || (d_A != nullptr) != (d_A_trial != nullptr))
+    return fail(GP_ERR_INVALID, "grad / grad_trial and A / A_trial are given or left out as pairs");
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::SeriesUpdateArgs<T> a;
+    a.x = as<T>(d_x);
+    a.trial = as<T>(d_trial);
+    a.cost = as<T>(d_cost);
+    a.cost_trial = as<T>(d_cost_trial);
+    a.grad = as<T>(d_grad);
+    a.grad_trial = as<T>(d_grad_trial);
+    a.A = as<T>(d_A);
+    a.A_trial = as<T>(d_A_trial);
+    a.lambda = as<T>(d_lambda);
+    a.status = d_status;
+    a.state = d_state;
+    a.accepted = d_accepted;
+    a.F_out = as<T>(d_F);
+    a.prior_mean = as<T>(d_prior_mean);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_mean_stride = prior_mean_stride;
+    a.prior_prec_stride = prior_prec_stride;
+    a.W = as<T>(d_W);
+    a.w_stride = w_stride;
+    a.down = down;
+    a.up = up;
+    a.lambda_min = lambda_min;
+    a.lambda_max = lambda_max;
+    a.ftol = ftol;
+    a.xtol = xtol;
+    a.rows = n_rows;
+    a.dates = n_dates;
+    a.d = n_inputs;
+    return launched(gpk::launch_series_update<T>(a, ctx->stream), "series update");
+  });
+}
+
+int gp_series_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, int64_t prior_prec_stride,
+                         const void* d_W, int64_t w_stride, void* d_cov, void* d_sigma, int32_t* d_status, void* d_work,
+                         int64_t work_bytes, int64_t n_rows, int n_dates, int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_A || !d_status || (!d_cov && !d_sigma)) return fail(GP_ERR_INVALID, "null device pointer");
+  if (int rc = series_sizes(dtype, n_rows, n_dates, n_inputs, nullptr, false, 0, d_prior_prec, prior_prec_stride, d_W, w_stride))
+    return rc;
+  if (int rc = series_work(d_work, work_bytes, n_rows, n_dates, n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::SeriesCovArgs<T> a;
+    a.A = as<T>(d_A);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_prec_stride = prior_prec_stride;
+    a.W = as<T>(d_W);
+    a.w_stride = w_stride;
+    a.cov = as<T>(d_cov);
+    a.sigma = as<T>(d_sigma);
+    a.status = d_status;
+    a.work = (double*)d_work;
+    a.rows = n_rows;
+    a.dates = n_dates;
+    a.d = n_inputs;
+    return launched(gpk::launch_series_cov<T>(a, ctx->stream), "series covariance");
   });
 }
 

@@ -689,56 +689,128 @@ class MultivariateEmulator(object):
         obs = _first_guess.mask_obs(obs, weights, precision if is_gpu else np.float64)
         prior, bounds = _retrieve.prior_and_bounds(prior, bounds, D, M)
         max_iter = int(max_iter)
-        per_row = weights is not None and weights.ndim == 2
 
         if not is_gpu:
-            obs64 = np.asarray(obs, dtype=np.float64)
-            w64 = None if weights is None else np.asarray(weights, dtype=np.float64)
-            G = self.weight_gram(w64, is_gpu=False) if per_row else self._gauss_newton_matrix(w64)
-
-            def data_term(X):
-                if emulator_unc:
-                    return self._data_term_unc_numpy(X, obs64, w64, G)
-                cost, _, _, grad, gn = self._data_term_numpy(X, obs64, w64, True, G)
-                return cost, grad, gn
-
             def step(x, g, A, lam):
                 return _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds)
-            return _retrieve.lm_numpy(data_term, step, Y0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov,
-                                      next_prior, return_A)
+            return _retrieve.lm_numpy(self._retrieval_term_numpy(obs, weights, emulator_unc), step, Y0, lam0, max_iter, down,
+                                      up, ftol, xtol, prior, return_cov, next_prior, return_A)
 
         dt = np.dtype(precision)
-        isz = dt.itemsize
         st = self._fresh_gpu_state(dt)
-        ctx, batch, d_basis = st["ctx"], st["batch"], st["d_basis"]
-        with _retrieve.Scratch(ctx, dt) as scratch:
-            d_obs = scratch.up(obs)
-            d_w = scratch.up(weights) if weights is not None else None
-            d_mu, d_der = scratch.alloc(P * M * isz), scratch.alloc(P * M * D * isz)
-            os_, ws = B if obs.ndim == 2 else 0, B if per_row else 0
-            if per_row:                                # every row's matrix, once: it does not depend on the state
-                d_G = scratch.alloc(M * P * P * isz)
-                ctx.mv_weight_gram_device(dt, d_basis, d_w, B, d_G, M, P, B)
-            else:
-                d_G = scratch.up(self._gauss_newton_matrix(weights))
-            if emulator_unc:
-                d_var, d_dvar, d_coef = scratch.alloc(P * M * isz), scratch.alloc(P * M * D * isz), scratch.alloc(P * M * isz)
-
-            def misfit_unc(d_rows, c, g, a):
-                batch.predict_mean_grad_device(d_rows, d_mu, d_der, M)
-                batch.predict_var_grad_device(d_rows, d_var, d_dvar, M)
-                ctx.mv_misfit_device(dt, d_basis, d_mu, d_der, d_obs, os_, d_w, ws, c, d_coef, None, M, P, B, D)
-                ctx.mv_misfit_unc_device(dt, c, d_coef, d_G, P * P if per_row else 0, d_var, d_der, d_dvar, c, g, a, M, P, D)
-
-            def misfit(d_rows, c, g, a):
-                batch.predict_mean_grad_device(d_rows, d_mu, d_der, M)
-                ctx.mv_misfit_device(dt, d_basis, d_mu, d_der, d_obs, os_, d_w, ws, c, None, g, M, P, B, D)
-                if per_row:
-                    ctx.mv_gauss_newton_rows_device(dt, d_der, d_G, P * P, a, M, P, D)
-                else:
-                    ctx.mv_gauss_newton_device(dt, d_der, d_G, a, M, P, D)
+        with _retrieve.Scratch(st["ctx"], dt) as scratch:
+            misfit = self._retrieval_term_device(scratch, st, obs, weights, M, D, emulator_unc)
             return _retrieve.lm_device(scratch, M, D, Y0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                       misfit_unc if emulator_unc else misfit, next_prior, return_A)
+                                       misfit, next_prior, return_A)
+
+    def _retrieval_term_numpy(self, obs, weights, emulator_unc):
+        """The data term of the retrievals on the host: ``X (R, D) -> (cost, grad, A)`` for ``obs`` and ``weights`` as
+        ``_misfit_args`` returns them for those R rows; the weights' matrix is formed once."""
+        per_row = weights is not None and weights.ndim == 2
+        obs64 = np.asarray(obs, dtype=np.float64)
+        w64 = None if weights is None else np.asarray(weights, dtype=np.float64)
+        G = self.weight_gram(w64, is_gpu=False) if per_row else self._gauss_newton_matrix(w64)
+
+        def data_term(X):
+            if emulator_unc:
+                return self._data_term_unc_numpy(X, obs64, w64, G)
+            cost, _, _, grad, gn = self._data_term_numpy(X, obs64, w64, True, G)
+            return cost, grad, gn
+        return data_term
+
+    def _retrieval_term_device(self, scratch, st, obs, weights, M, D, emulator_unc):
+        """The data term of the retrievals on the device, for the ``M`` rows ``obs`` and ``weights`` are given for: they
+        go up once into ``scratch`` (on the resident emulator ``st``), with per-row weights one launch of the Gram kernel
+        forms every row's matrix; ``misfit(d_rows, d_cost, d_grad, d_A)`` enqueues the term on those rows."""
+        ctx, batch, d_basis = st["ctx"], st["batch"], st["d_basis"]
+        dt = scratch.dt
+        isz = dt.itemsize
+        P, B = self.n_pcs, self.basis_functions.shape[1]
+        per_row = weights is not None and weights.ndim == 2
+        d_obs = scratch.up(obs)
+        d_w = scratch.up(weights) if weights is not None else None
+        d_mu, d_der = scratch.alloc(P * M * isz), scratch.alloc(P * M * D * isz)
+        os_, ws = B if obs.ndim == 2 else 0, B if per_row else 0
+        if per_row:                                # every row's matrix, once: it does not depend on the state
+            d_G = scratch.alloc(M * P * P * isz)
+            ctx.mv_weight_gram_device(dt, d_basis, d_w, B, d_G, M, P, B)
+        else:
+            d_G = scratch.up(self._gauss_newton_matrix(weights))
+        if emulator_unc:
+            d_var, d_dvar, d_coef = scratch.alloc(P * M * isz), scratch.alloc(P * M * D * isz), scratch.alloc(P * M * isz)
+
+        def misfit_unc(d_rows, c, g, a):
+            batch.predict_mean_grad_device(d_rows, d_mu, d_der, M)
+            batch.predict_var_grad_device(d_rows, d_var, d_dvar, M)
+            ctx.mv_misfit_device(dt, d_basis, d_mu, d_der, d_obs, os_, d_w, ws, c, d_coef, None, M, P, B, D)
+            ctx.mv_misfit_unc_device(dt, c, d_coef, d_G, P * P if per_row else 0, d_var, d_der, d_dvar, c, g, a, M, P, D)
+
+        def misfit(d_rows, c, g, a):
+            batch.predict_mean_grad_device(d_rows, d_mu, d_der, M)
+            ctx.mv_misfit_device(dt, d_basis, d_mu, d_der, d_obs, os_, d_w, ws, c, None, g, M, P, B, D)
+            if per_row:
+                ctx.mv_gauss_newton_rows_device(dt, d_der, d_G, P * P, a, M, P, D)
+            else:
+                ctx.mv_gauss_newton_device(dt, d_der, d_G, a, M, P, D)
+        return misfit_unc if emulator_unc else misfit
+
+    def retrieve_joint(self, Y0, obs, weights, prior, noise, bounds=None, lam0=1e-2, max_iter=20, down=1.0 / 3.0, up=4.0,
+                       ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False, emulator_unc=False,
+                       second_order="gauss_newton", work_budget=None):
+        """Joint maximum a posteriori retrieval of M trajectories of T dates on this emulator: what
+        ``perband.retrieve_bands_joint`` is to ``retrieve_bands`` (the objective, the loop, the keywords, the returned
+        ``(Y (T, M, D), sigma (T, M, D), cost (T, M), F (M,), state, n_accepted, lam, cov_status)`` and ``cov (T, M, D,
+        D)`` with ``return_cov=True``, the positive definite ``noise`` it needs, the invalid pixels), with the data term
+        of ``retrieve_many`` on every date.  ``obs`` is (T, N_full) or (T, M, N_full), ``weights`` None, (N_full,) for
+        every date and pixel, (T, N_full) or (T, M, N_full); ``Y0`` (T, M, D), or (M, D) taken for every date; ``prior`` is
+        date 0's, required.  One data-term call runs on the T M rows of all dates; with anything but one weight vector
+        for all of them the per-row Gram matrices are formed for those rows, once.  ``second_order`` is "gauss_newton"
+        only.  ``is_gpu=False`` is the explicit numpy branch; never a fallback."""
+        from . import _first_guess, _retrieve
+        if second_order != "gauss_newton":
+            raise ValueError("the joint retrieval needs second_order='gauss_newton': the Hessian of F must stay positive definite")
+        if prior is None:
+            raise ValueError("a joint retrieval needs a prior")
+        obs = np.asarray(obs)
+        T = len(obs)
+        if T == 0:
+            raise ValueError("obs has no dates")
+        Y0 = _retrieve.joint_start(Y0, T, "Y0")
+        M, D = Y0.shape[1:]
+        B = self.basis_functions.shape[1]
+        if D != self.emulators[0].inputs.shape[1]:
+            raise ValueError("Y0 has %d columns, the emulators have %d inputs" % (D, self.emulators[0].inputs.shape[1]))
+
+        def rows(a, name):             # per date (N_full,) or (M, N_full): (T, M, N_full)
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape not in ((T, B), (T, M, B)):
+                raise ValueError("%s must be (%d, %d) or (%d, %d, %d), got %s" % (name, T, B, T, M, B, a.shape))
+            return np.broadcast_to(a[:, None, :] if a.ndim == 2 else a, (T, M, B))
+        obs = rows(obs, "obs")
+        if weights is not None and np.ndim(weights) != 1:
+            weights = rows(weights, "weights")
+        flat = Y0.reshape(T * M, D)
+        _, obs_f, w_f = self._misfit_args(flat, np.ascontiguousarray(obs.reshape(T * M, B)),
+                                          weights if weights is None or np.ndim(weights) == 1 else
+                                          np.ascontiguousarray(weights.reshape(T * M, B)), False)
+        obs_f = _first_guess.mask_obs(obs_f, w_f, precision if is_gpu else np.float64)
+        loop = (bounds, lam0, max_iter, down, up, ftol, xtol, return_cov)
+
+        def cut(a, m0, m1):            # the pixels m0 .. m1 of every date of a (T M, N_full) array
+            if a is None or a.ndim == 1:
+                return a
+            return np.ascontiguousarray(a.reshape(T, M, B)[:, m0:m1].reshape(T * (m1 - m0), B))
+        if not is_gpu:
+            def numpy_term(m0, m1):
+                return self._retrieval_term_numpy(cut(obs_f, m0, m1), cut(w_f, m0, m1), emulator_unc)
+            return _retrieve.retrieve_joint(Y0, prior, noise, *loop, numpy_term=numpy_term)
+        dt = np.dtype(precision)
+        st = self._fresh_gpu_state(dt)
+
+        def device_term(scratch, m0, m1):
+            return self._retrieval_term_device(scratch, st, cut(obs_f, m0, m1), cut(w_f, m0, m1), T * (m1 - m0), D, emulator_unc)
+        return _retrieve.retrieve_joint(Y0, prior, noise, *loop, device_term=device_term, context=st["ctx"], precision=precision,
+                                        work_budget=work_budget)
 
     # ---- the first guess: look-up-table search in band space --------------------------------------
     def candidate_table(self, candidates, precision=np.float64, space="band"):
@@ -869,7 +941,7 @@ class MultivariateEmulator(object):
             return self.first_guess_many(candidates, obs, weights, prior, n_best, table=table, space=space, **fg)
         return _first_guess.multistart(first_guess, self.retrieve_many, 0, obs, weights, n_starts, D, loop_args)
 
-    def retrieve_series(self, Y0, obs, weights, prior, noise, smooth=False, **loop_args):
+    def retrieve_series(self, Y0, obs, weights, prior, noise, smooth=False, joint=False, **loop_args):
         """A time series of ``retrieve_many`` on this emulator: ``obs`` (T, N_full) or (T, M, N_full) and ``weights``
         the same or None, one retrieval per date, the posterior of a date propagated by the process noise ``noise``
         (D, D) or (M, D, D) into the prior of the next (``_retrieve.retrieve_series``: what it returns, and why
@@ -878,8 +950,15 @@ class MultivariateEmulator(object):
 
         ``smooth=True`` appends the Rauch-Tung-Striebel smoothed trajectory ``X_s (T, M, D)``, ``sigma_s (T, M, D)``
         and ``smooth_status (T, M)``, as ``perband.retrieve_bands_series`` does: on the GPU one ``rts_smooth_device``
-        call per date on this emulator's context, with ``is_gpu=False`` ``_lib.rts_smooth_numpy``; never a fallback."""
+        call per date on this emulator's context, with ``is_gpu=False`` ``_lib.rts_smooth_numpy``; never a fallback.
+
+        ``joint=True`` runs the filter and the smoother as ``smooth=True`` does, starts ``retrieve_joint`` from the
+        smoothed trajectory ``X_s`` and appends its eight values to the ten, as ``perband.retrieve_bands_series`` does.
+        With ``False`` nothing changes."""
         from . import _retrieve
+        if joint:
+            out = self.retrieve_series(Y0, obs, weights, prior, noise, smooth=True, **loop_args)
+            return out + self.retrieve_joint(out[7], obs, weights, prior, noise, **loop_args)
         if not smooth:
             return _retrieve.retrieve_series(self.retrieve_many, Y0, obs, weights, prior, noise, **loop_args)
         context = None

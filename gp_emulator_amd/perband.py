@@ -478,27 +478,114 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     if step_fn is not None or not is_gpu:
         step = step_fn if step_fn is not None else (
             lambda x, g, A, lam: _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds))
-        numpy_form = _misfit_unc_numpy if emulator_unc else _misfit_numpy
-        return _retrieve.lm_numpy(lambda X: numpy_form(gps, X, obs, weights, second_order, False), step, X0, lam0,
+        return _retrieve.lm_numpy(_data_term_numpy(gps, obs, weights, second_order, emulator_unc), step, X0, lam0,
                                   max_iter, down, up, ftol, xtol, prior, return_cov, next_prior, return_A)
 
     ctx = _lib.default_context(device)
+    with _batch_model(ctx, gps, inputs, precision, bool(emulator_unc)) as batch, \
+            _retrieve.Scratch(ctx, np.dtype(precision)) as scratch:
+        misfit = _data_term_device(batch, scratch, obs, weights, M, second_order, emulator_unc)
+        return _retrieve.lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
+                                   misfit, next_prior, return_A)
+
+
+def _data_term_numpy(gps, obs, weights, second_order, emulator_unc):
+    """The data term of the retrievals on the host: ``X (R, D) -> (cost, grad, A)`` for ``obs`` and ``weights`` as
+    ``_em_broadcast`` returns them for those R rows."""
+    numpy_form = _misfit_unc_numpy if emulator_unc else _misfit_numpy
+    return lambda X: numpy_form(gps, X, obs, weights, second_order, False)
+
+
+def _data_term_device(batch, scratch, obs, weights, n_rows, second_order, emulator_unc):
+    """The data term of the retrievals on the device: ``obs`` and ``weights`` (as ``_em_broadcast`` returns them for
+    the ``n_rows`` rows) go up once, into ``scratch``; ``misfit(d_rows, d_cost, d_grad, d_A)`` enqueues
+    ``misfit_device`` (``misfit_unc_device`` with ``emulator_unc``) on those rows."""
+    M = n_rows
 
     def strides(a):
         return (1, 0) if a.shape[1] == 1 and M != 1 else (M, 1)
-    with _batch_model(ctx, gps, inputs, precision, bool(emulator_unc)) as batch, \
-            _retrieve.Scratch(ctx, np.dtype(precision)) as scratch:
-        d_obs = scratch.up(obs)
-        d_w = scratch.up(weights) if weights is not None else None
-        os_, ws = strides(obs), strides(weights) if weights is not None else (0, 0)
+    d_obs = scratch.up(obs)
+    d_w = scratch.up(weights) if weights is not None else None
+    os_, ws = strides(obs), strides(weights) if weights is not None else (0, 0)
 
-        def misfit(d_rows, c, g, a):
-            if emulator_unc:
-                return batch.misfit_unc_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a)
-            batch.misfit_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a if second_order == "gauss_newton" else None,
-                                d_hess=a if second_order == "full" else None)
-        return _retrieve.lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                   misfit, next_prior, return_A)
+    def misfit(d_rows, c, g, a):
+        if emulator_unc:
+            return batch.misfit_unc_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a)
+        batch.misfit_device(d_rows, d_obs, os_, d_w, ws, c, g, M, d_gn=a if second_order == "gauss_newton" else None,
+                            d_hess=a if second_order == "full" else None)
+    return misfit
+
+
+def _joint_em_rows(a, T, E, M, name):
+    """``a`` (T, E, M) -- or per date anything ``_em_broadcast`` takes -- as one float64 (E, T M) array, date-major
+    along the rows: what a data-term call on the T M rows of a series reads."""
+    if len(a) != T:
+        raise ValueError("%s has %d dates, obs %d" % (name, len(a), T))
+    return np.ascontiguousarray(np.concatenate([np.broadcast_to(_em_broadcast(a[t], E, M, name), (E, M)) for t in range(T)], axis=1))
+
+
+def retrieve_bands_joint(gps, X0, obs, weights, prior, noise, second_order="gauss_newton", bounds=None, lam0=1e-2,
+                         max_iter=20, down=1.0 / 3.0, up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64,
+                         device=None, return_cov=False, emulator_unc=False, work_budget=None):
+    """Joint maximum a posteriori retrieval of M trajectories of T dates on E per-band emulators: minimises, pixel by
+    pixel and over all dates at once, the objective the series is built around,
+
+        F(x_0 .. x_{T-1}) = sum_t J_t(x_t) + 1/2 (x_0 - xp)^T P (x_0 - xp) + 1/2 sum_{t>=1} (x_t - x_{t-1})^T W (x_t - x_{t-1})
+
+    with ``J_t`` the data term of ``retrieve_bands`` on date t's ``obs[t]`` (E, M) and ``weights[t]``, ``prior = (xp,
+    P)`` on date 0 (shared or per pixel; required) and ``W = Q^-1`` the inverse of the process noise ``noise`` (D, D) or
+    (M, D, D).  The joint form needs a POSITIVE DEFINITE ``Q``: it is inverted once, before the loop; a shared ``Q``
+    that does not factor raises ``ValueError``, a pixel's own that does not gives that pixel a NaN ``W``, a non-zero
+    ``cov_status`` and no accepted step.  ``X0`` is (T, M, D); an (M, D) array is taken for every date.
+
+    The loop is ``retrieve_bands``' (its schedule, constants and keywords) on whole trajectories: one data-term call on
+    the T M rows of the trial trajectories, the accept / reject of every pixel's trajectory as a whole, then the
+    block-tridiagonal damped Newton step (``gp_series_step_device``: block Cholesky over the dates).  Where the
+    emulators are linear the minimiser is the smoothed trajectory of ``retrieve_bands_series(smooth=True)``; where they
+    are not, it is the minimiser and the smoother is not.  ``second_order`` must be "gauss_newton" (the Hessian of F
+    must stay positive definite: "full" raises ``ValueError``).  A weight of exactly 0 masks its band; a date with all
+    weights 0 is an ordinary date; a pixel with a NaN or an infinity on any date -- in ``obs`` under a non-zero weight,
+    in a weight, in ``X0`` or in its own prior -- is never accepted and comes back as it went in, and every other pixel
+    is bit for bit the call without it.
+
+    Returns ``(X (T, M, D), sigma (T, M, D), cost (T, M), F (M,), state (M,) int32, n_accepted (M,) int32, lam (M,),
+    cov_status (M,) int32)``: ``sigma`` the square roots of the diagonals of the marginal posterior covariances (the
+    diagonal blocks of the inverse of the undamped Hessian, ``gp_series_cov_device``), ``cost`` the data terms, ``F`` the
+    joint objective at ``X`` (NaN for a pixel no decision was made for), ``cov_status`` 0 or t D + k + 1 for the first
+    failed pivot (then the pixel's ``sigma`` is NaN).  ``return_cov=True`` appends ``cov (T, M, D, D)``.
+
+    On the GPU the pixels are cut into runs whose work memory (the factors between the two sweeps, 8 (D (D + 1) / 2 +
+    D (D | 1) + D) bytes per pixel and date) stays under ``work_budget`` bytes (default 1 GiB); the cut changes no
+    bit.  ``is_gpu=False`` is the explicit numpy branch (``_retrieve.lm_series_numpy``); never a fallback."""
+    if second_order != "gauss_newton":
+        raise ValueError("the joint retrieval needs second_order='gauss_newton': the Hessian of F must stay positive definite")
+    if prior is None:
+        raise ValueError("a joint retrieval needs a prior")
+    T, E = len(obs), len(gps)
+    if T == 0:
+        raise ValueError("obs has no dates")
+    X0 = _retrieve.joint_start(X0, T)
+    M, D = X0.shape[1:]
+    _, inputs = _rows_and_inputs(gps, X0.reshape(T * M, D), "X0")
+    obs = _joint_em_rows(obs, T, E, M, "obs")
+    if weights is not None:
+        weights = _joint_em_rows(weights, T, E, M, "weights")
+    obs = _first_guess.mask_obs(obs, weights, precision if is_gpu else np.float64)
+    loop = (bounds, lam0, max_iter, down, up, ftol, xtol, return_cov)
+
+    def rows_of(a, m0, m1):           # the pixels m0 .. m1 of every date of an (E, T M) array
+        return None if a is None else np.ascontiguousarray(a.reshape(E, T, M)[:, :, m0:m1].reshape(E, T * (m1 - m0)))
+    if not is_gpu:
+        def numpy_term(m0, m1):
+            return _data_term_numpy(gps, rows_of(obs, m0, m1), rows_of(weights, m0, m1), second_order, emulator_unc)
+        return _retrieve.retrieve_joint(X0, prior, noise, *loop, numpy_term=numpy_term)
+    ctx = _lib.default_context(device)
+    with _batch_model(ctx, gps, inputs, precision, bool(emulator_unc)) as batch:
+        def device_term(scratch, m0, m1):
+            return _data_term_device(batch, scratch, rows_of(obs, m0, m1), rows_of(weights, m0, m1), T * (m1 - m0),
+                                     second_order, emulator_unc)
+        return _retrieve.retrieve_joint(X0, prior, noise, *loop, device_term=device_term, context=ctx, precision=precision,
+                                        work_budget=work_budget)
 
 
 def candidate_table(gps, candidates=None, precision=np.float64, device=None):
@@ -603,7 +690,7 @@ def retrieve_bands_multistart(gps, candidates, obs, weights=None, n_starts=4, ta
     return _first_guess.multistart(first_guess, retrieve, 1, obs, weights, n_starts, D, loop_args)
 
 
-def retrieve_bands_series(gps, X0, obs, weights, prior, noise, smooth=False, **loop_args):
+def retrieve_bands_series(gps, X0, obs, weights, prior, noise, smooth=False, joint=False, **loop_args):
     """A time series of ``retrieve_bands`` on the emulators ``gps``: ``obs`` (T, E, M) -- or anything ``retrieve_bands``
     takes, per date -- and ``weights`` the same or None, one retrieval per date, the posterior of a date propagated by
     the process noise ``noise`` (D, D) or (M, D, D) into the prior of the next (``_retrieve.retrieve_series``: what it
@@ -613,9 +700,20 @@ def retrieve_bands_series(gps, X0, obs, weights, prior, noise, smooth=False, **l
     ``smooth_status (T, M)``: every date then also carries the observations after it (a gap is filled from both
     sides).  On the GPU the backward pass is one ``rts_smooth_device`` call per date with the smoothed state and
     covariance of the later date resident on the device; with ``is_gpu=False`` (or a ``step_fn``) it is
-    ``_lib.rts_smooth_numpy``; never a fallback."""
+    ``_lib.rts_smooth_numpy``; never a fallback.
+
+    ``joint=True`` runs the filter and the smoother as ``smooth=True`` does, starts ``retrieve_bands_joint`` from the
+    smoothed trajectory ``X_s`` and appends its eight values to the ten: the minimiser of the series' objective, which
+    the smoother is on linear emulators only.  The loop's keywords go to both; ``step_fn`` has no joint form
+    (``ValueError``).  With ``False`` nothing changes."""
     def retrieve(X, obs_t, weights_t, **kw):
         return retrieve_bands(gps, X, obs_t, weights_t, **kw)
+    if joint:
+        if loop_args.get("step_fn") is not None:
+            raise ValueError("joint=True has no step_fn form")
+        out = retrieve_bands_series(gps, X0, obs, weights, prior, noise, smooth=True, **loop_args)
+        return out + retrieve_bands_joint(gps, out[7], obs, weights, prior, noise,
+                                          **{k: v for k, v in loop_args.items() if k != "step_fn"})
     if not smooth:
         return _retrieve.retrieve_series(retrieve, X0, obs, weights, prior, noise, **loop_args)
     on_device = loop_args.get("is_gpu", True) and loop_args.get("step_fn") is None

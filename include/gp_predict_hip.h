@@ -598,6 +598,63 @@ int gp_rts_smooth_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_
                          const void* d_lo, const void* d_hi, void* d_x_smooth, void* d_cov_smooth,
                          void* d_sigma_smooth, int32_t* d_status, int64_t n_rows, int n_inputs);
 
+/* ---- joint MAP over a series: block-tridiagonal Levenberg-Marquardt -----------------------------------
+ * The minimiser over whole trajectories of
+ *   F = sum_t J_t(x_t) + 1/2 (x_0 - xp)^T P (x_0 - xp) + 1/2 sum_{t>=1} (x_t - x_{t-1})^T W (x_t - x_{t-1})
+ * for n_rows pixels of n_dates dates each, D = n_inputs.  Arrays are DATE-MAJOR: d_x, d_grad, d_step, d_trial
+ * [n_dates][n_rows][D], d_A and d_cov [n_dates][n_rows][D][D], d_cost [n_dates][n_rows], so that a data-term call on
+ * n_dates * n_rows rows fills them.  The prior (d_prior_mean xp, d_prior_prec P; both or neither) is on date 0 only,
+ * one for all pixels (stride 0) or pixel m's at m * stride elements.  d_W is the PRECISION of the process noise,
+ * W = Q^-1, [D][D] (stride 0) or pixel m's at m * w_stride elements; required.
+ * gp_series_step_device, per pixel m:
+ *   H_tt = A_t (+ P if t = 0) (+ W if t > 0) (+ W if t < T-1),  H_t,t-1 = -W      lower triangles of A, P, W read
+ *   g'_t = grad_t (+ P (x_0 - xp) if t = 0) + W (x_t - x_{t-1}) [t > 0] - W (x_{t+1} - x_t) [t < T-1]
+ *                                        fma chains over the column index, ascending, continued from grad_t in that order
+ *   H'_tt,dd = H_tt,dd + lambda[m] s_d   damping = GP_DAMP_DIAGONAL: s_d = H_tt,dd (before damping); GP_DAMP_IDENTITY: 1
+ *   H' delta = -g'                       block Cholesky: S_0 = H'_00, S_t = H'_tt - B_t B_t^T, L_t L_t^T = S_t,
+ *                                        B_{t+1} L_t^T = -W by row substitutions, forward and backward block
+ *                                        substitutions; every sum one fma chain in ascending index
+ *   step = delta, trial = clamp(x + step, lo, hi)  as gp_newton_step_device's (a NaN stays NaN); either may be NULL
+ *   status[m] = 0, or t * D + k + 1 for the first pivot (date t, index k, both 0-based) that is not > 0 or not finite;
+ *               then step = 0 and trial = x on every date
+ * gp_series_update_device decides per pixel with state[m] == 0 over whole trajectories:
+ *   F = sum_t cost[t][m] (t ascending) + gp_lm_update_device's prior term on date 0 + for t = 1 .. T-1 the same form
+ *   with W and x_t - x_{t-1}; F_t the same of the trial;  accept = status[m] == 0 && isfinite(F_t) && F_t < F
+ *   accept: x, cost, grad, A of all dates <- the trial's (copies, bit for bit), lambda <- max(lambda * down, lambda_min),
+ *           state <- 1 if (F - F_t) <= ftol * F or max_{t,d} |trial - x| <= xtol, else 0
+ *   reject: lambda <- min(lambda * up, lambda_max)
+ *   d_accepted[m] (nullable) is 1 or 0; d_F[m] (nullable) is the objective of the state the pixel is left with.
+ *   Pixels with state[m] != 0 are left untouched (d_accepted[m] = 0).
+ * gp_series_cov_device gives the marginal posterior covariances from the undamped H: the same forward factorisation,
+ *   Sigma_{T-1} = (L L^T)^-1, then K_t = -L_t^-T B_{t+1}^T and Sigma_t = (L_t L_t^T)^-1 + K_t Sigma_{t+1} K_t^T;
+ *   cov symmetric bit for bit, sigma = sqrt of its unrounded diagonal (either may be NULL, not both), status as the
+ *   step's; on a failed pivot every output of the pixel is a quiet NaN.
+ * With n_dates = 1 the step's outputs are bit for bit gp_newton_step_rows_device's and the covariance's
+ * gp_posterior_cov_rows_device's.  Everything runs in double in both precisions, every output rounded to `dtype` once
+ * on store.  No atomics: a pixel's result does not depend on the other pixels, on its place in the call or on how the
+ * pixels are cut into calls; two calls agree bit for bit, and so do stride 0 and repeated arrays.
+ * d_work is device memory of at least gp_series_work_bytes(n_rows, n_dates, n_inputs) bytes (the factors between the
+ * sweeps, kept in double; -1 for sizes out of range): cut the pixels into several calls to bound it.
+ * Strides are 0 or >= one pixel's elements (GP_ERR_INVALID otherwise, and for a non-zero stride with a NULL pointer).
+ * Device pointers of `dtype` (d_status, d_state, d_accepted int32), asynchronous on the context's stream;
+ * n_rows > 0, n_dates > 0, 1 <= n_inputs <= 32 (GP_ERR_UNSUPPORTED beyond). */
+int64_t gp_series_work_bytes(int64_t n_rows, int n_dates, int n_inputs);
+int gp_series_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A,
+                          const void* d_lambda, int damping, const void* d_prior_mean, int64_t prior_mean_stride,
+                          const void* d_prior_prec, int64_t prior_prec_stride, const void* d_W, int64_t w_stride,
+                          const void* d_lo, const void* d_hi, void* d_step, void* d_trial, int32_t* d_status,
+                          void* d_work, int64_t work_bytes, int64_t n_rows, int n_dates, int n_inputs);
+int gp_series_update_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost,
+                            const void* d_cost_trial, void* d_grad, const void* d_grad_trial, void* d_A,
+                            const void* d_A_trial, void* d_lambda, const int32_t* d_status, int32_t* d_state,
+                            int32_t* d_accepted, void* d_F, const void* d_prior_mean, int64_t prior_mean_stride,
+                            const void* d_prior_prec, int64_t prior_prec_stride, const void* d_W, int64_t w_stride,
+                            double down, double up, double lambda_min, double lambda_max, double ftol, double xtol,
+                            int64_t n_rows, int n_dates, int n_inputs);
+int gp_series_cov_device(gp_ctx* ctx, int dtype, const void* d_A, const void* d_prior_prec, int64_t prior_prec_stride,
+                         const void* d_W, int64_t w_stride, void* d_cov, void* d_sigma, int32_t* d_status, void* d_work,
+                         int64_t work_bytes, int64_t n_rows, int n_dates, int n_inputs);
+
 /* ---- look-up-table search: the first guess of a retrieval ---------------------------------------------
  * For rows m < n_rows, candidates l < n_candidates and terms k < n_terms,
  *   J[m][l] = a[l] + 1/2 sum_k w[m][k] (S[l][k] - o[m][k])^2
