@@ -84,6 +84,30 @@ def search_table(tb, obs, obs_strides, weights, w_strides, offset, M, n_best):
         return _lib._download(ctx, d_i, (M, n_best), np.int32), _lib._download(ctx, d_c, (M, n_best), dt)
 
 
+def posterior_table(tb, obs, obs_strides, weights, w_strides, offset, M):
+    """The look-up-table posterior of ``M`` rows against the device table ``tb`` (``gp_lut_posterior_device``): ``obs``,
+    ``weights``, the offset and the candidate states (as the table's dtype) go up once per call; ``index``, ``cost`` and
+    the float64 ``mean``, ``cov``, ``lse`` and ``ess`` come back."""
+    ctx, dt = tb.ctx, tb.dtype
+    L, D = tb.candidates.shape
+    with _lib.Scratch(ctx, dt) as scratch:
+        d_o, d_w, d_a, d_x = scratch.up(obs), scratch.up(weights), scratch.up(offset), scratch.up(tb.candidates)
+        d_i, d_c = scratch.alloc(M * 4), scratch.alloc(M * dt.itemsize)
+        d_m, d_v, d_l, d_e = scratch.alloc(M * D * 8), scratch.alloc(M * D * D * 8), scratch.alloc(M * 8), scratch.alloc(M * 8)
+        ctx.lut_posterior_device(dt, tb.d_table, tb.strides, d_a, d_o, obs_strides, d_w, w_strides, d_x, (D, 1), D, d_i, d_c,
+                                 d_m, d_v, d_l, d_e, M, L, tb.n_terms)
+        return (_lib._download(ctx, d_i, (M,), np.int32), _lib._download(ctx, d_c, (M,), dt),
+                _lib._download(ctx, d_m, (M, D), np.float64), _lib._download(ctx, d_v, (M, D, D), np.float64),
+                _lib._download(ctx, d_l, (M,), np.float64), _lib._download(ctx, d_e, (M,), np.float64))
+
+
+def posterior_result(out, L):
+    """``(mean, cov, info)`` from ``(index, cost, mean, cov, lse, ess)``: ``log_evidence = lse - log L``, the Monte-Carlo
+    estimate of the evidence for ``L`` candidates drawn from the prior."""
+    index, cost, mean, cov, lse, ess = out
+    return mean, cov, dict(index=index, cost=cost, log_evidence=lse - np.log(L), ess=ess)
+
+
 def rows_of(a, rows):
     """``a[rows]`` of a row-shaped array; a shared vector or None as it is."""
     return a if a is None or a.ndim == 1 else a[rows]

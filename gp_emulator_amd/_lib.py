@@ -16,7 +16,7 @@ from ._dense_numpy import (DAMPINGS, newton_step_numpy, posterior_cov_numpy, pre
                            prior_rows, row_strides, rts_smooth_numpy, series_cov_numpy, series_objective_numpy,
                            series_step_numpy, series_update_numpy, _cholesky_inverse_numpy, _mirror_lower)
 from ._lut_numpy import MAX_PCS as lut_pc_max_pcs  # noqa: F401
-from ._lut_numpy import lut_pc_prepare_numpy, lut_search_numpy, lut_search_pc_numpy  # noqa: F401
+from ._lut_numpy import lut_pc_prepare_numpy, lut_posterior_numpy, lut_search_numpy, lut_search_pc_numpy  # noqa: F401
 from ._moments_numpy import rows_arrays as _moments_rows
 from ._sobol_numpy import bounds_arrays as _sobol_bounds
 
@@ -100,6 +100,9 @@ SIGNATURES = {
     "gp_lut_search_device": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
                                      c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_int]),
     "gp_lut_search_geometry": (c_int, [ctypes.POINTER(c_int)] * 3),
+    "gp_lut_posterior_device": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_void_p,
+                                        c_i64, c_i64, c_void_p, c_i64, c_i64, c_int] + [c_void_p] * 6 + [c_i64, c_i64, c_int, c_int]),
+    "gp_lut_posterior_geometry": (c_int, [c_int, c_int] + [ctypes.POINTER(c_int)] * 5),
     "gp_lut_search_pc_device": (c_int, [c_void_p, c_int, c_void_p, c_i64, c_i64] + [c_void_p] * 5 + [c_i64] + [c_void_p] * 3
                                 + [c_i64, c_i64, c_int, c_int, c_int]),
     "gp_lut_search_pc_geometry": (c_int, [c_int, c_int] + [ctypes.POINTER(c_int)] * 4),
@@ -858,6 +861,23 @@ class Context:
                                             int(n_candidates), int(n_terms), int(n_best), int(n_slices)),
               "gp_lut_search_device")
 
+    def lut_posterior_device(self, dtype, d_table, table_strides, d_offset, d_obs, obs_strides, d_weights, w_strides, d_states,
+                             state_strides, n_dims, d_index, d_cost, d_mean, d_cov, d_lse, d_ess, n_rows, n_candidates,
+                             n_terms, n_slices=0):
+        """Asynchronous look-up-table posterior on the device (``gp_lut_posterior_device``): every candidate weighted by
+        ``exp(-(J - Jmin))`` with ``lut_search_device``'s J, operands and strides; ``d_states`` holds the candidate
+        states, element (l, d) at ``l * state_strides[0] + d * state_strides[1]``.  Writes the search's result at
+        ``n_best = 1`` into ``d_index`` (int32 ``[n_rows]``) and ``d_cost`` (``dtype``), and in float64 whatever
+        ``dtype`` is ``d_mean [n_rows][n_dims]``, ``d_cov [n_rows][n_dims][n_dims]``, ``d_lse`` and ``d_ess``
+        ``[n_rows]``.  ``n_slices`` 0 leaves the slicing to the launch plan; unlike the search, the result depends on
+        the number of slices through the order of the additions (within rounding)."""
+        check(self.lib.gp_lut_posterior_device(self.h, _dtype_code(dtype), d_table, int(table_strides[0]), int(table_strides[1]),
+                                               d_offset, d_obs, int(obs_strides[0]), int(obs_strides[1]), d_weights,
+                                               int(w_strides[0]), int(w_strides[1]), d_states, int(state_strides[0]),
+                                               int(state_strides[1]), int(n_dims), d_index, d_cost, d_mean, d_cov, d_lse,
+                                               d_ess, int(n_rows), int(n_candidates), int(n_terms), int(n_slices)),
+              "gp_lut_posterior_device")
+
     def lut_search_pc_device(self, dtype, d_table, table_strides, d_offset, d_c0, d_j0, d_g0, d_gram, gram_stride, d_status,
                              d_index, d_cost, n_rows, n_candidates, n_pcs, n_best, n_slices=0):
         """Asynchronous look-up-table search in PC space (``gp_lut_search_pc_device``): per row the ``n_best`` candidates
@@ -915,6 +935,47 @@ class Context:
             self.lut_search_device(dt, d_t, (1, K), d_a, d_o, strides(obs), d_w, strides(weights) if weights is not None else (0, 0),
                                    d_i, d_c, M, L, K, n_best, n_slices)
             return _download(self, d_i, (M, n_best), np.int32), _download(self, d_c, (M, n_best), dt)
+
+    def lut_posterior(self, table, states, obs, weights=None, offset=None, precision=None, is_gpu=True, n_slices=0):
+        """``(index (M,) int32, cost (M,), mean (M, D), cov (M, D, D), lse (M,), ess (M,))`` of the look-up-table
+        posterior for the host arrays ``table`` (L, K), ``states`` (L, D), ``obs`` (K,) or (M, K), ``weights`` None,
+        (K,) or (M, K) and ``offset`` None or (L,): uploads, launches ``gp_lut_posterior_device``, downloads.
+        ``precision`` is the device dtype of J (default: float32 when ``table`` is float32, else float64); mean, cov,
+        lse and ess are float64.  ``is_gpu=False`` is the explicit numpy branch (``lut_posterior_numpy``, float64);
+        never a fallback."""
+        if not is_gpu:
+            return lut_posterior_numpy(table, states, obs, weights, offset)
+        table, states = np.asarray(table), np.asarray(states)
+        if table.ndim != 2:
+            raise ValueError("table must be (n_candidates, n_terms)")
+        dt = _device_dtype(precision, table)
+        L, K = table.shape
+        if states.ndim != 2 or states.shape[0] != L:
+            raise ValueError("states must be (%d, n_dims), got %s" % (L, states.shape))
+        D = states.shape[1]
+        obs = np.asarray(obs)
+        weights = None if weights is None else np.asarray(weights)
+        for name, a in (("obs", obs), ("weights", weights)):
+            if a is not None and (a.ndim not in (1, 2) or a.shape[-1] != K):
+                raise ValueError("%s must be (%d,) or (n_rows, %d), got %s" % (name, K, K, a.shape))
+        rows = [a.shape[0] for a in (obs, weights) if a is not None and a.ndim == 2]
+        M = rows[0] if rows else 1
+        if any(r != M for r in rows):
+            raise ValueError("obs and weights disagree on the number of rows")
+
+        def strides(a):
+            return (1, K) if a.ndim == 2 else (1, 0)
+        with Scratch(self, dt) as scratch:
+            d_t, d_o, d_w, d_a = scratch.up(table), scratch.up(obs), scratch.up(weights), scratch.up(offset)
+            d_x = scratch.up(states)
+            d_i, d_c = scratch.alloc(M * 4), scratch.alloc(M * dt.itemsize)
+            d_m, d_v, d_l, d_e = scratch.alloc(M * D * 8), scratch.alloc(M * D * D * 8), scratch.alloc(M * 8), scratch.alloc(M * 8)
+            self.lut_posterior_device(dt, d_t, (1, K), d_a, d_o, strides(obs), d_w,
+                                      strides(weights) if weights is not None else (0, 0), d_x, (D, 1), D, d_i, d_c, d_m, d_v,
+                                      d_l, d_e, M, L, K, n_slices)
+            return (_download(self, d_i, (M,), np.int32), _download(self, d_c, (M,), dt),
+                    _download(self, d_m, (M, D), np.float64), _download(self, d_v, (M, D, D), np.float64),
+                    _download(self, d_l, (M,), np.float64), _download(self, d_e, (M,), np.float64))
 
     def likelihood_batch(self, thetas, inputs, targets, want_inverse=False):
         """cost (E,), grad (E, D+2) [and invQ (E, N, N), invQt (E, N)] of the training
@@ -1412,14 +1473,15 @@ GP_OP_LUT_SEARCH = 7
 GP_OP_LUT_SEARCH_PC = 8
 GP_OP_SOBOL = 9
 GP_OP_MOMENTS = 10
+GP_OP_LUT_POSTERIOR = 11
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
                 6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
                 10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search", 14: "lut_search_pc", 15: "sobol",
-                16: "moments"}
+                16: "moments", 17: "lut_posterior"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
              "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM, "var_grad": GP_OP_VAR_GRAD,
              "lut_search": GP_OP_LUT_SEARCH, "lut_search_pc": GP_OP_LUT_SEARCH_PC, "sobol": GP_OP_SOBOL,
-             "moments": GP_OP_MOMENTS}
+             "moments": GP_OP_MOMENTS, "lut_posterior": GP_OP_LUT_POSTERIOR}
 
 
 def lut_search_geometry():
@@ -1441,6 +1503,18 @@ def lut_search_pc_geometry(n_pcs, precision=np.float64):
     return dict(rows_per_item=r.value, candidate_tile=t.value, padded_pcs=pp.value, workgroups_per_cu=w.value)
 
 
+def lut_posterior_geometry(n_dims, precision=np.float64):
+    """``dict(rows_per_item, candidate_tile, term_chunk, padded_dims, workgroups_per_cu)`` of ``lut_posterior_kernel``
+    for ``n_dims`` and the device dtype: the rows of a work item, the candidates of the instance's register tile, the
+    terms of a staged chunk, the padded ``n_dims`` the instance's accumulators are sized for and the workgroups a
+    compute unit takes of it (``gp_lut_posterior_geometry``; no GPU needed)."""
+    r, t, c, pd, w = c_int(0), c_int(0), c_int(0), c_int(0), c_int(0)
+    check(load().gp_lut_posterior_geometry(_dtype_code(precision), int(n_dims), ctypes.byref(r), ctypes.byref(t),
+                                           ctypes.byref(c), ctypes.byref(pd), ctypes.byref(w)), "gp_lut_posterior_geometry")
+    return dict(rows_per_item=r.value, candidate_tile=t.value, term_chunk=c.value, padded_dims=pd.value,
+                workgroups_per_cu=w.value)
+
+
 def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_pcs=0, n_bands=0,
                 compute_units=256, aligned16=True, n_terms=0, n_candidates=0):
     """How the device call ``op`` ("predict", "mean_grad", "var_grad", "hessian", "reconstruct", "misfit", "mv_gram") on ``n_rows`` rows would be
@@ -1456,9 +1530,13 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
     items and slices, with ``candidate_tile``, ``padded_pcs`` and ``workgroups_per_cu`` (``lut_search_pc_geometry``).
     "sobol" takes ``n_rows`` boxes, ``n_emulators`` pairs, ``n_train`` and ``n_inputs``: an item is ``rows_per_item``
     training rows of one (box, pair).  "moments" takes ``n_rows``, ``n_emulators`` pairs, ``n_train`` and ``n_inputs``:
-    an item is one (row, pair)."""
+    an item is one (row, pair).  "lut_posterior" takes ``n_inputs`` (the states' n_dims) and ``n_candidates``: the
+    search's items, with ``slices`` (capped by the scratch budget of the partial sums), ``candidate_tile``,
+    ``term_chunk``, ``padded_dims`` and ``workgroups_per_cu`` (``lut_posterior_geometry``)."""
     code = _PLAN_OPS[op]
-    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_LUT_SEARCH, GP_OP_LUT_SEARCH_PC)
+    recon = code in (GP_OP_RECONSTRUCT, GP_OP_MISFIT, GP_OP_MV_GRAM, GP_OP_LUT_SEARCH, GP_OP_LUT_SEARCH_PC, GP_OP_LUT_POSTERIOR)
+    if code == GP_OP_LUT_POSTERIOR:
+        n_pcs, n_bands = n_inputs, n_candidates
     if code == GP_OP_LUT_SEARCH:
         n_pcs, n_bands = n_terms, n_candidates
     if code == GP_OP_LUT_SEARCH_PC:
@@ -1480,6 +1558,11 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
         return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
                     rest_items=0, rest_workgroups=0, slices=ritems.value, candidate_tile=geo["candidate_tile"],
                     padded_pcs=geo["padded_pcs"], workgroups_per_cu=geo["workgroups_per_cu"])
+    if code == GP_OP_LUT_POSTERIOR:
+        geo = lut_posterior_geometry(n_inputs, precision)
+        return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
+                    rest_items=0, rest_workgroups=0, slices=ritems.value, candidate_tile=geo["candidate_tile"],
+                    term_chunk=geo["term_chunk"], padded_dims=geo["padded_dims"], workgroups_per_cu=geo["workgroups_per_cu"])
     return dict(kernel=PLAN_KERNELS[k.value], rows_per_item=rpi.value, items=items.value, workgroups=wg.value,
                 rest_items=ritems.value, rest_workgroups=rwg.value)
 

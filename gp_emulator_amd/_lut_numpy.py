@@ -55,6 +55,79 @@ def lut_search_numpy(table, obs, weights=None, offset=None, n_best=1, max_elemen
     return index, cost
 
 
+MAX_DIMS = 16
+
+
+def lut_posterior_numpy(table, states, obs, weights=None, offset=None, max_elements=1 << 22):
+    """The float64 numpy branch of the look-up-table posterior (``gp_lut_posterior_device``):
+    ``(index (M,) int32, cost (M,), mean (M, D), cov (M, D, D), lse (M,), ess (M,))`` for ``table`` (L, K), the
+    candidate ``states`` (L, D), ``obs`` (K,) or (M, K), ``weights`` None, (K,) or (M, K) and ``offset`` None or (L,).
+    With ``lut_search_numpy``'s J, ``Jmin`` its minimum in a row, ``l*`` the lower index there and ``c = x[l*]``,
+
+        w_l = exp(-(J[m, l] - Jmin))                      (0 for a J that is NaN or +inf)
+        S0 = sum w    Sq = sum w^2    S1 = sum w (x_l - c)    S2 = sum w (x_l - c)(x_l - c)^T
+        mean = c + S1 / S0    cov = S2 / S0 - (S1 / S0)(S1 / S0)^T    lse = -Jmin + log S0    ess = S0^2 / Sq
+
+    centred on the row's own best candidate, so that nothing of order one cancels; ``cov`` is the upper triangle
+    mirrored.  A row without any finite J has index -1 and NaN everywhere else.  The rows go by in chunks of at most
+    ``max_elements / (L max(K, D))``."""
+    S = np.asarray(table, dtype=np.float64)
+    X = np.asarray(states, dtype=np.float64)
+    if S.ndim != 2:
+        raise ValueError("table must be (n_candidates, n_terms)")
+    L, K = S.shape
+    if X.ndim != 2 or X.shape[0] != L:
+        raise ValueError("states must be (%d, n_dims), got %s" % (L, X.shape))
+    D = X.shape[1]
+    if not 1 <= D <= MAX_DIMS:
+        raise ValueError("the look-up-table posterior serves n_dims in 1..%d" % MAX_DIMS)
+    o = np.asarray(obs, dtype=np.float64)
+    w = None if weights is None else np.asarray(weights, dtype=np.float64)
+    for name, a in (("obs", o), ("weights", w)):
+        if a is not None and (a.ndim not in (1, 2) or a.shape[-1] != K):
+            raise ValueError("%s must be (%d,) or (n_rows, %d), got %s" % (name, K, K, a.shape))
+    rows = [a.shape[0] for a in (o, w) if a is not None and a.ndim == 2]
+    M = rows[0] if rows else 1
+    if any(r != M for r in rows):
+        raise ValueError("obs and weights disagree on the number of rows")
+    o = np.broadcast_to(o, (M, K))
+    if w is not None:
+        w = np.broadcast_to(w, (M, K))
+        o = np.where(w == 0, 0.0, o)             # the masked terms: selected away
+    a = np.zeros(L) if offset is None else np.asarray(offset, dtype=np.float64).reshape(L)
+    index = np.full(M, -1, np.int32)
+    cost, lse, ess = np.full(M, np.nan), np.full(M, np.nan), np.full(M, np.nan)
+    mean, cov = np.full((M, D), np.nan), np.full((M, D, D), np.nan)
+    step = max(1, int(max_elements) // max(1, L * max(K, D)))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for r0 in range(0, M, step):
+            r1 = min(M, r0 + step)
+            d = S[None, :, :] - o[r0:r1, None, :]
+            sq = d * d if w is None else (w[r0:r1, None, :] * d) * d
+            J = a[None, :] + 0.5 * np.sum(sq, axis=2)
+            ok = J < np.inf                      # (False for NaN)
+            best = np.argmin(np.where(ok, J, np.inf), axis=1)      # (the first minimum: the lower index)
+            rr = np.arange(r1 - r0)
+            found = ok[rr, best]
+            Jmin = J[rr, best]
+            om = np.where(ok, np.exp(-(J - Jmin[:, None])), 0.0)
+            c = X[best]
+            dx = X[None, :, :] - c[:, None, :]
+            t = om[:, :, None] * dx
+            S0, Sq, S1 = om.sum(axis=1), (om * om).sum(axis=1), t.sum(axis=1)
+            S2 = np.matmul(t.transpose(0, 2, 1), dx)
+            mu = S1 / S0[:, None]
+            cv = np.triu(S2 / S0[:, None, None] - mu[:, :, None] * mu[:, None, :])
+            cv = cv + np.triu(cv, 1).transpose(0, 2, 1)
+            index[r0:r1] = np.where(found, best, -1)
+            cost[r0:r1] = np.where(found, Jmin, np.nan)
+            mean[r0:r1] = np.where(found[:, None], c + mu, np.nan)
+            cov[r0:r1] = np.where(found[:, None, None], cv, np.nan)
+            lse[r0:r1] = np.where(found, -Jmin + np.log(S0), np.nan)
+            ess[r0:r1] = np.where(found, S0 * S0 / Sq, np.nan)
+    return index, cost, mean, cov, lse, ess
+
+
 MAX_PCS = 16
 
 

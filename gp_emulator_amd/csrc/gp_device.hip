@@ -337,6 +337,17 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     rpi = gpk::lkRows;
     g = lp.grid;
     rest.items = lp.n_slices;
+  } else if (op == GP_OP_LUT_POSTERIOR) {
+    // (n_inputs = n_dims here; aux = n_candidates; rest_items reports the slices)
+    if (n_inputs <= 0 || aux <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    if (n_inputs > gpk::lqMaxDims) return fail(GP_ERR_UNSUPPORTED, "the look-up-table posterior serves n_dims <= %d", gpk::lqMaxDims);
+    const int dm = gpk::lut_post_padded(n_inputs), eb = f64 ? 8 : 4;
+    const gpk::LutPlan lp = gpk::plan_lut_posterior(n_rows, aux, n_inputs, gpk::lkRows, gpk::lut_post_tile(dm, eb),
+                                                    gpk::lut_cap(compute_units, gpk::lut_post_wgs_per_cu(dm, eb)), 0);
+    k = GP_PLAN_LUT_POSTERIOR;
+    rpi = gpk::lkRows;
+    g = lp.grid;
+    rest.items = lp.n_slices;
   } else if (op == GP_OP_SOBOL) {
     // (n_emulators = n_pairs here; n_rows = n_boxes)
     if (n_train <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");

@@ -4,7 +4,7 @@
 //   gp_model.hip      kernel choice, packing, models, the operands built on first use, the context's model cache
 //   gp_device.hip     launch sizing; predict, the variance's gradient and the Hessian on device buffers
 //   gp_solve.hip      the small dense solves on device buffers: Newton step, LM update, posterior covariance, prior
-//                     propagation, smoother; the look-up-table search; the Sobol indices and the moments under a
+//                     propagation, smoother; the look-up-table search and posterior; the Sobol indices and the moments under a
 //                     Gaussian input (no model)
 //   gp_host_path.hip  predict and Hessian on host arrays: the slab pipeline, the pinned-array path
 //   gp_folds.hip      folds over the emulators of a batch: the weighted Hessian, the per-band misfit

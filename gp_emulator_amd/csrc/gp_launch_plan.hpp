@@ -149,6 +149,26 @@ inline LutPlan plan_lut_search_pc(long long n_rows, long long n_candidates, int 
   return plan_lut_search(n_rows, n_candidates, rows_per_item, cand_tile, cap, forced);
 }
 
+// lut_posterior_kernel: lut_search_kernel's items and persistent grid, with the instance's own candidate tile.  The
+// instance is the padded n_dims (8, 12 or 16: what the lane's 2 + DM + DM (DM + 1) / 2 double accumulators are sized
+// for); every instance is built for one 4-wave workgroup per CU (the unified register file), and
+// the instances of 16 dimensions take a 32-candidate tile.  The slices' partial sums -- n_rows x terms doubles per slice, far more
+// than the search's lists -- stay within lqPartBytes of the context's scratch: the slices are capped by it, a forced
+// count too, down to one slice, which needs no scratch at all.
+constexpr int lqMaxDims = 16;
+constexpr long long lqPartBytes = 256LL << 20;
+constexpr int lut_post_padded(int n_dims) { return n_dims <= 8 ? 8 : n_dims <= 12 ? 12 : 16; }
+constexpr int lut_post_tile(int padded_dims, int elem_bytes) { return elem_bytes == 8 || padded_dims > 8 ? 32 : 64; }
+constexpr int lut_post_wgs_per_cu(int /*padded_dims*/, int /*elem_bytes*/) { return 1; }
+__host__ __device__ constexpr long long lut_post_terms(int n_dims) { return 2 + n_dims + (long long)n_dims * (n_dims + 1) / 2; }
+inline LutPlan plan_lut_posterior(long long n_rows, long long n_candidates, int n_dims, int rows_per_item, int cand_tile,
+                                  long long cap, int forced) {
+  LutPlan p = plan_lut_search(n_rows, n_candidates, rows_per_item, cand_tile, cap, forced);
+  const long long room = lqPartBytes / (8 * lut_post_terms(n_dims) * n_rows);
+  if (p.n_slices > 1 && p.n_slices > room) p = plan_lut_search(n_rows, n_candidates, rows_per_item, cand_tile, cap, room < 2 ? 1 : (int)room);
+  return p;
+}
+
 // sobol_pair_kernel: items = (box, pair, block of skRows training rows), j-block fastest; plan_grid with the
 // (box, pair) count as its batch.  The instance is the padded n_inputs (8, 12 or 16: what the per-lane registers are
 // sized for); every instance takes more than 256 VGPRs, so a CU holds one 4-wave workgroup of it.

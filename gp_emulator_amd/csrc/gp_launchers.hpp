@@ -28,6 +28,7 @@ template <typename T> struct GramArgs;
 template <typename T> struct MvUncArgs;
 template <typename T> struct LutArgs;
 template <typename T> struct LutPcArgs;
+template <typename T> struct LutPostArgs;
 template <typename T> struct LutPcSolveArgs;
 struct TrainArgs;
 struct SobolArgs;
@@ -71,6 +72,8 @@ template <typename T> hipError_t launch_lut_search(const LutArgs<T>&, int grid, 
 template <typename T> hipError_t launch_lut_search_pc(const LutPcArgs<T>&, int grid, hipStream_t);
 template <typename T> hipError_t launch_lut_pc_solve(const LutPcSolveArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_lut_pc_fill(T* x, T v, long long n, hipStream_t);
+// lut_posterior_kernel on `grid` workgroups (the instance by n_dims), then lut_posterior_finish_kernel when the call is sliced
+template <typename T> hipError_t launch_lut_posterior(const LutPostArgs<T>&, int grid, hipStream_t);
 
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);      // fp64 only
 // sobol_pair_kernel on `grid` workgroups (the instance by n_inputs), then sobol_fold_kernel; fp64 only

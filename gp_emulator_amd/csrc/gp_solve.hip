@@ -1,11 +1,12 @@
 // The small dense solves on device buffers: damped Newton step, LM update, posterior covariance, prior propagation and
-// the smoother's backward step, the joint step, update and covariance of a whole series; and the look-up-table search that starts a retrieval.  Device arrays in, device arrays
+// the smoother's backward step, the joint step, update and covariance of a whole series; the look-up-table search that starts a retrieval and the look-up-table posterior.  Device arrays in, device arrays
 // out, no model.  The Sobol indices of a batch of emulators and their moments under a Gaussian input, on host arrays
 // (no model either).
 #include "gp_host.hpp"
 
 #include "gp_launch_plan.hpp"
 #include "gp_launchers.hpp"
+#include "gp_lut_posterior_kernel.hpp"
 #include "gp_lut_search_kernel.hpp"
 #include "gp_lut_search_pc_kernel.hpp"
 #include "gp_newton_kernel.hpp"
@@ -499,6 +500,73 @@ int gp_lut_search_pc_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t
     a.tiles_per_slice = plan.tiles_per_slice;
     a.P = n_pcs, a.n_best = n_best, a.n_slices = plan.n_slices;
     return launched(gpk::launch_lut_search_pc<T>(a, plan.grid.workgroups, ctx->stream), "lut search pc");
+  });
+}
+
+int gp_lut_posterior_geometry(int dtype, int n_dims, int* rows_per_item, int* candidate_tile, int* term_chunk,
+                              int* padded_dims, int* workgroups_per_cu) {
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (n_dims <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_dims > gpk::lqMaxDims) return fail(GP_ERR_UNSUPPORTED, "the look-up-table posterior serves n_dims <= %d", gpk::lqMaxDims);
+  const int dm = gpk::lut_post_padded(n_dims), eb = dtype == GP_F64 ? 8 : 4;
+  if (rows_per_item) *rows_per_item = gpk::lkRows;
+  if (candidate_tile) *candidate_tile = gpk::lut_post_tile(dm, eb);
+  if (term_chunk) *term_chunk = gpk::lkChunk;
+  if (padded_dims) *padded_dims = dm;
+  if (workgroups_per_cu) *workgroups_per_cu = gpk::lut_post_wgs_per_cu(dm, eb);
+  return GP_OK;
+}
+
+int gp_lut_posterior_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t table_kstride, int64_t table_lstride,
+                            const void* d_offset, const void* d_obs, int64_t obs_kstride, int64_t obs_mstride,
+                            const void* d_weights, int64_t w_kstride, int64_t w_mstride, const void* d_states,
+                            int64_t states_lstride, int64_t states_dstride, int n_dims, int32_t* d_index, void* d_cost,
+                            double* d_mean, double* d_cov, double* d_lse, double* d_ess, int64_t n_rows,
+                            int64_t n_candidates, int n_terms, int n_slices) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (dtype != GP_F32 && dtype != GP_F64) return fail(GP_ERR_INVALID, "bad dtype %d", dtype);
+  if (!d_table || !d_obs || !d_states || !d_index || !d_cost || !d_mean || !d_cov || !d_lse || !d_ess)
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if (n_rows <= 0 || n_candidates <= 0 || n_terms <= 0 || n_dims <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_dims > gpk::lqMaxDims) return fail(GP_ERR_UNSUPPORTED, "the look-up-table posterior serves n_dims <= %d", gpk::lqMaxDims);
+  if (n_candidates > 0x7fffffffLL) return fail(GP_ERR_INVALID, "n_candidates too large for an int32 index");
+  if (n_slices < 0) return fail(GP_ERR_INVALID, "negative n_slices");
+  if (table_kstride < 0 || table_lstride < 0 || obs_kstride < 0 || obs_mstride < 0 || w_kstride < 0 || w_mstride < 0 ||
+      states_lstride < 0 || states_dstride < 0)
+    return fail(GP_ERR_INVALID, "negative stride");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int dm = gpk::lut_post_padded(n_dims), eb = dtype == GP_F64 ? 8 : 4;
+  const gpk::LutPlan plan = gpk::plan_lut_posterior(n_rows, n_candidates, n_dims, gpk::lkRows, gpk::lut_post_tile(dm, eb),
+                                                    gpk::lut_cap(ctx->compute_units, gpk::lut_post_wgs_per_cu(dm, eb)), n_slices);
+  // the partial sums first: the scratch only grows, so the search's own lists (used up by its merge, in stream order,
+  // before the sums are written) do not move it afterwards
+  const size_t n_part = plan.n_slices > 1 ? (size_t)plan.n_slices * (size_t)gpk::lut_post_terms(n_dims) * (size_t)n_rows : 0;
+  if (n_part)
+    if (int rc = ensure_scratch(ctx, n_part * sizeof(double))) return rc;
+  // step 1: the search, untouched, with its own slicing
+  if (int rc = gp_lut_search_device(ctx, dtype, d_table, table_kstride, table_lstride, d_offset, d_obs, obs_kstride, obs_mstride,
+                                    d_weights, w_kstride, w_mstride, d_index, d_cost, n_rows, n_candidates, n_terms, 1, 0))
+    return rc;
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::LutPostArgs<T> a;
+    a.table = as<T>(d_table);
+    a.offset = as<T>(d_offset);
+    a.obs = as<T>(d_obs);
+    a.weights = as<T>(d_weights);
+    a.states = as<T>(d_states);
+    a.index = d_index;
+    a.cost = as<T>((const void*)d_cost);
+    a.mean = d_mean, a.cov = d_cov, a.lse = d_lse, a.ess = d_ess;
+    a.part = n_part ? (double*)ctx->scratch : nullptr;
+    a.t_ks = table_kstride, a.t_ls = table_lstride;
+    a.o_ks = obs_kstride, a.o_ms = obs_mstride;
+    a.w_ks = w_kstride, a.w_ms = w_mstride;
+    a.s_ls = states_lstride, a.s_ds = states_dstride;
+    a.M = n_rows, a.L = n_candidates;
+    a.tiles_per_slice = plan.tiles_per_slice;
+    a.K = n_terms, a.D = n_dims, a.n_slices = plan.n_slices;
+    return launched(gpk::launch_lut_posterior<T>(a, plan.grid.workgroups, ctx->stream), "lut posterior");
   });
 }
 

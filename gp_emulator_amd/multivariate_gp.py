@@ -925,6 +925,51 @@ class MultivariateEmulator(object):
                     tb.close()
         return _first_guess.gather_starts(cand, index, n_best), cost, index
 
+    def posterior_many(self, candidates, obs, weights=None, prior=None, is_gpu=True, precision=np.float64, table=None,
+                       space="band"):
+        """The Bayesian look-up-table posterior in band space, as ``perband.posterior_bands``: every candidate (L, D) --
+        None: the emulators' shared training inputs, or the candidates of ``table=`` -- weighted by
+        ``exp(-(J - Jmin))`` with ``first_guess_many``'s J (``obs``, ``weights`` and the shared ``prior`` as there), on the
+        ``(L, N_full)`` spectra table (``candidate_table``; ``table=`` reuses one).  Returns ``(mean (M, D), cov (M, D,
+        D), info)`` in float64, ``info = dict(index, cost, log_evidence, ess)`` with ``log_evidence = lse - log L``.
+        ``is_gpu=False`` is the explicit numpy branch (``predict_many(is_gpu=False)`` and ``_lib.lut_posterior_numpy``);
+        never a fallback.  ``space="pc"`` is a ``ValueError``: the fold has no PC-space form."""
+        from . import _first_guess
+        if space != "band":
+            raise ValueError("posterior_many folds in band space only (space=%r)" % (space,))
+        D, B = self.emulators[0].inputs.shape[1], self.basis_functions.shape[1]
+        if table is not None and candidates is None:
+            cand = table.candidates
+        else:
+            cand = _first_guess.check_candidates(self.emulators[0].inputs if candidates is None else candidates, D)
+        obs = np.asarray(obs, dtype=np.float64)
+        weights = None if weights is None else np.asarray(weights, dtype=np.float64)
+        for name, a in (("obs", obs), ("weights", weights)):
+            if a is not None and (a.ndim not in (1, 2) or a.shape[-1] != B):
+                raise ValueError("%s must be (%d,) or (n_rows, %d), got %s" % (name, B, B, a.shape))
+        rows = [a.shape[0] for a in (obs, weights) if a is not None and a.ndim == 2]
+        M = rows[0] if rows else 1
+        if any(r != M for r in rows):
+            raise ValueError("obs and weights disagree on the number of rows")
+        offset = _first_guess.prior_offset(cand, _first_guess.shared_prior(prior, D))
+        if not is_gpu:
+            out = _lib.lut_posterior_numpy(self.predict_many(cand, is_gpu=False), cand, obs, weights, offset)
+        else:
+            tb = table if table is not None else self.candidate_table(cand, precision)
+            try:
+                tb.check(self, precision, B, "band")
+                if tb.candidates.shape != cand.shape or (tb.candidates is not cand and not np.array_equal(tb.candidates, cand)):
+                    raise ValueError("table= was built for other candidates")
+
+                def strides(a):
+                    return (1, B) if a.ndim == 2 else (1, 0)
+                out = _first_guess.posterior_table(tb, obs, strides(obs), weights,
+                                                   strides(weights) if weights is not None else (0, 0), offset, M)
+            finally:
+                if table is None:
+                    tb.close()
+        return _first_guess.posterior_result(out, cand.shape[0])
+
     def retrieve_many_multistart(self, candidates, obs, weights=None, n_starts=4, table=None, space="band", **loop_args):
         """``retrieve_many`` from several starts per pixel, as ``perband.retrieve_bands_multistart``: ``first_guess_many``
         with ``n_best = n_starts`` ranked with the loop's shared ``prior``, the starts clipped to ``bounds``, ONE

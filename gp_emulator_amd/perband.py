@@ -670,6 +670,60 @@ def first_guess_bands(gps, candidates, obs, weights=None, prior=None, n_best=1, 
     return _first_guess.gather_starts(cand, index, n_best), cost, index
 
 
+def posterior_bands(gps, candidates, obs, weights=None, prior=None, is_gpu=True, precision=np.float64, device=None,
+                    table=None):
+    """The Bayesian look-up-table posterior of every row: instead of the best candidates (``first_guess_bands``), every
+    candidate (L, D) -- None: the emulators' shared training inputs -- weighted by its likelihood,
+
+        w[m, l] = exp(-(J[m, l] - Jmin[m])),    J = first_guess_bands' J (``obs``, ``weights`` and ``prior`` as there)
+
+    and the weighted moments of the candidate states.  Returns ``(mean (M, D), cov (M, D, D), info)`` in float64;
+    ``info = dict(index (M,) int32, cost (M,), log_evidence (M,), ess (M,))``: the best candidate and its J (the search
+    at ``n_best = 1``), ``log_evidence = log sum_l exp(-J) - log L`` (the Monte-Carlo estimate of the evidence for
+    candidates drawn from the prior; for comparing priors, band sets or emulators on one observation) and the
+    effective sample size ``(sum w)^2 / sum w^2`` (near 1: the table is too sparse for this row, and so is its first
+    guess).  The sums are centred on the row's best candidate: a posterior on one candidate gives that candidate bit for
+    bit, ``cov`` 0 and ``ess`` 1.  A row without a finite J gets index -1 and NaN.  Unlike ``retrieve_bands(return_cov=
+    True)`` the moments see every basin of the data term, a parameter the bands do not constrain and a posterior that
+    leans on the box.  On the GPU the table is ``candidate_table`` (``table=`` reuses one), the states go up once per
+    call and ``gp_lut_posterior_device`` folds; ``is_gpu=False`` is the explicit numpy branch
+    (``_lib.lut_posterior_numpy`` on ``cpu_predict`` means); never a fallback."""
+    inputs = _check_shared_inputs(gps)
+    E, D = len(gps), inputs.shape[1]
+    if table is not None and candidates is None:
+        cand = table.candidates
+    else:
+        cand = _first_guess.check_candidates(inputs if candidates is None else candidates, D)
+    obs = np.asarray(obs, dtype=np.float64)
+    if weights is not None:
+        weights = np.asarray(weights, dtype=np.float64)
+    rows = [a.shape[1] for a in (obs, weights) if a is not None and a.ndim == 2]
+    M = rows[0] if rows else 1
+    obs = _em_broadcast(obs, E, M, "obs")
+    if weights is not None:
+        weights = _em_broadcast(weights, E, M, "weights")
+    offset = _first_guess.prior_offset(cand, _first_guess.shared_prior(prior, D))
+    if not is_gpu:
+        S = np.stack([np.asarray(gp.cpu_predict(cand, do_unc=False)[0]) for gp in gps], axis=1)        # (L, E)
+        out = _lib.lut_posterior_numpy(S, cand, np.broadcast_to(obs, (E, M)).T,
+                                       None if weights is None else np.broadcast_to(weights, (E, M)).T, offset)
+    else:
+        tb = table if table is not None else candidate_table(gps, cand, precision, device)
+        try:
+            tb.check(_owner(tb, gps), precision, E)
+            if tb.candidates.shape != cand.shape or (tb.candidates is not cand and not np.array_equal(tb.candidates, cand)):
+                raise ValueError("table= was built for other candidates")
+
+            def strides(a):
+                return (1, 0) if a.shape[1] == 1 and M != 1 else (M, 1)
+            out = _first_guess.posterior_table(tb, obs, strides(obs), weights,
+                                               strides(weights) if weights is not None else (0, 0), offset, M)
+        finally:
+            if table is None:
+                tb.close()
+    return _first_guess.posterior_result(out, cand.shape[0])
+
+
 def retrieve_bands_multistart(gps, candidates, obs, weights=None, n_starts=4, table=None, **loop_args):
     """``retrieve_bands`` from several starts per pixel: ``first_guess_bands`` with ``n_best = n_starts``, ranked with
     the loop's shared ``prior``; the starts clipped to ``bounds``; ONE ``retrieve_bands`` call on the ``M n_starts``

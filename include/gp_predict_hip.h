@@ -688,6 +688,44 @@ int gp_lut_search_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t ta
 /* The kernel's geometry (no GPU needed): rows of a work item, candidates of a register tile, terms of a staged chunk. */
 int gp_lut_search_geometry(int* rows_per_item, int* candidate_tile, int* term_chunk);
 
+/* ---- look-up-table posterior: mean, covariance, evidence ---------------------------------------------------
+ * Every candidate weighted by its likelihood.  With J[m][l] exactly gp_lut_search_device's quantity (the same operands,
+ * strides, optional weights and offset, masking of a weight of exactly 0, and dtype), candidate states x_l (element
+ * (l, d) at d_states[l * states_lstride + d * states_dstride], n_dims in 1..16), Jmin the row's minimum, l* the lower
+ * index there and c = x_{l*}:
+ *   w_l = exp(-(J[m][l] - Jmin))      (0 for a J that is NaN or +infinity)
+ *   S0 = sum w   Sq = sum w^2   S1 = sum w (x_l - c)   S2 = sum w (x_l - c)(x_l - c)^T
+ *   mean = c + S1 / S0    cov = S2 / S0 - (S1 / S0)(S1 / S0)^T    lse = -Jmin + log S0 (= log sum_l exp(-J))    ess = S0^2 / Sq
+ * The sums are centred on the row's own best candidate, so that nothing of order one cancels: a posterior that sits on
+ * one candidate gives mean = x_{l*} bit for bit, cov = 0 and ess = 1 exactly.  cov is symmetric bit for bit.
+ * Outputs: d_index int32 [n_rows] and d_cost [n_rows] (`dtype`) are the search's result at n_best = 1, bit for bit;
+ * d_mean [n_rows][n_dims], d_cov [n_rows][n_dims][n_dims], d_lse [n_rows] and d_ess [n_rows] are double whatever
+ * `dtype` is.  The weights, their sums and the states are taken in double; J is recomputed by the search's chain in
+ * `dtype`, so that J[m][l*] is bit for bit Jmin.
+ * Three steps on the context's stream: the search at n_best = 1; lut_posterior_kernel (a lane per row, the search's
+ * tiling, the sums in registers); with more than one slice lut_posterior_finish_kernel, which adds the slices' partial
+ * sums in ascending slice order.  n_slices as in the search (0: chosen; gp_launch_plan, GP_OP_LUT_POSTERIOR, reports
+ * it), but the partial sums -- n_rows x (2 + n_dims + n_dims (n_dims + 1) / 2) doubles per slice in the context's
+ * scratch -- are kept within 256 MiB: the slices are capped by that, a requested count too.  UNLIKE THE SEARCH the
+ * result depends on the number of slices through the order of those additions (within rounding); for a fixed number of
+ * slices a row's outputs are bit for bit independent of n_rows, of the row's place in the call and of the grid, and two
+ * calls agree bit for bit.  No atomics.
+ * A row without any finite J (index -1) gets NaN in cost, mean, cov, lse and ess; every other row is bit for bit the
+ * call without it.  A NaN or an infinity in the table takes its candidate out for every row.
+ * GP_ERR_INVALID: a NULL context, table, obs, states or output, a bad dtype, non-positive sizes, n_candidates beyond
+ * int32, a negative n_slices or stride.  GP_ERR_UNSUPPORTED: n_dims above 16.
+ * Device pointers, asynchronous on the context's stream. */
+int gp_lut_posterior_device(gp_ctx* ctx, int dtype, const void* d_table, int64_t table_kstride, int64_t table_lstride,
+                            const void* d_offset, const void* d_obs, int64_t obs_kstride, int64_t obs_mstride,
+                            const void* d_weights, int64_t w_kstride, int64_t w_mstride, const void* d_states,
+                            int64_t states_lstride, int64_t states_dstride, int n_dims, int32_t* d_index, void* d_cost,
+                            double* d_mean, double* d_cov, double* d_lse, double* d_ess, int64_t n_rows,
+                            int64_t n_candidates, int n_terms, int n_slices);
+/* The kernel instance for (dtype, n_dims) (no GPU needed): rows of a work item, candidates of its register tile, terms
+ * of a staged chunk, the padded n_dims it is compiled for (8, 12 or 16) and the workgroups a compute unit takes of it. */
+int gp_lut_posterior_geometry(int dtype, int n_dims, int* rows_per_item, int* candidate_tile, int* term_chunk,
+                              int* padded_dims, int* workgroups_per_cu);
+
 /* ---- look-up-table search of a multivariate emulator in PC space -----------------------------------------
  * The spectra of a multivariate emulator are f = B^T mu (B the [n_pcs][n_bands] basis, mu the n_pcs per-PC means), so
  * for a row with observation o and weights w (W = diag(w)) and ANY centre c0 [n_pcs]
@@ -837,6 +875,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_LUT_SEARCH_PC 8      /* gp_lut_search_pc_device: n_inputs is n_pcs and aux n_candidates; rest_items is n_slices */
 #define GP_OP_SOBOL 9              /* gp_sobol_batch_f64: n_emulators is n_pairs and n_rows n_boxes; an item is 16 training rows */
 #define GP_OP_MOMENTS 10           /* gp_moments_batch_f64: n_emulators is n_pairs; an item is one (row, pair) */
+#define GP_OP_LUT_POSTERIOR 11     /* gp_lut_posterior_device: n_inputs is n_dims and aux n_candidates; rest_items is n_slices */
 #define GP_PLAN_PREDICT_FEW 1     /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
@@ -853,6 +892,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_LUT_SEARCH_PC 14   /* lut_search_pc_kernel: the same items; workgroups per CU by instance (n_pcs, dtype) */
 #define GP_PLAN_SOBOL 15           /* sobol_pair_kernel: items = n_boxes x n_pairs x ceil(n_train / 16); one workgroup per CU */
 #define GP_PLAN_MOMENTS 16         /* moments_pair_kernel: items = n_rows x n_pairs; 2 workgroups per CU for n_inputs <= 12, 1 beyond */
+#define GP_PLAN_LUT_POSTERIOR 17   /* lut_posterior_kernel: an item is 256 rows x one slice of the candidates; one workgroup per CU */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
