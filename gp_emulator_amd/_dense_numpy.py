@@ -113,6 +113,136 @@ def newton_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=No
     return step, trial, status
 
 
+def box_pass_cap(D):
+    """The most passes a row of the box step runs; a row cut off there reports one more."""
+    return 3 * D + 4
+
+
+def box_step_numpy(x, grad, A, lam, damping="diagonal", prior=None, bounds=None):
+    """The bound-constrained damped Newton step of ``gp_box_step_device`` in float64 numpy, vectorised over the rows and
+    written out in the kernel's order (csrc/gp_box_step_kernel.hpp): ``(step (M, D), trial (M, D), status (M,) int32,
+    at_lo (M,) uint32, at_hi (M,) uint32, passes (M,) int32)``.  The explicit CPU branch of ``Context.box_step`` and of
+    the retrievals' ``bounds_mode="active_set"``, and the reference of the CPU tests; never a fallback.
+
+        H = the damped A' and g' of ``newton_step_numpy``;  l = lo - x, u = hi - x;
+        step = argmin 1/2 d^T H d + g'^T d over l <= d <= u by the primal active-set method: start at clip(0, l, u); a
+        pass factors H with the bound components' rows and columns replaced by the identity, solves s_F = -H_FF^-1 r_F,
+        goes to the first bound it meets (lowest index of the smallest ratio) and fixes that component, or takes the
+        whole step and frees the bound component with the largest wrong-signed multiplier (lowest index), or is done;
+        trial = clip(x + step, lo, hi);  status = k + 1 when pivot k of any pass fails, then step = 0 and trial = x.
+
+    At most ``box_pass_cap(D)`` passes: a row that is cut off there returns its iterate with one more in ``passes``.  A
+    row with a non-finite ``x``, ``g'`` or bound is NaN in every element of step and trial, with status, masks and passes
+    0.  ``bounds`` is required; the other arguments are ``newton_step_numpy``'s."""
+    if damping not in DAMPINGS:
+        raise ValueError("damping must be 'diagonal' or 'identity'")
+    if bounds is None:
+        raise ValueError("the box step needs bounds")
+    x = np.array(x, dtype=np.float64, ndmin=2)
+    M, D = x.shape
+    g = np.array(grad, dtype=np.float64).reshape(M, D)
+    H = np.array(A, dtype=np.float64).reshape(M, D, D)
+    lam = np.broadcast_to(np.asarray(lam, dtype=np.float64), (M,))
+    lo, hi = (np.asarray(b, dtype=np.float64).reshape(D) for b in bounds)
+    rows, idx = np.arange(M), np.arange(D)
+    with np.errstate(all="ignore"):
+        if prior is not None:
+            x0, P = prior_rows(prior, M, D)
+            H = H + P
+            for c in range(D):
+                g += P[..., :, c] * (x[:, c] - x0[..., c])[:, None]
+        diag = H[:, idx, idx]
+        H[:, idx, idx] = diag + lam[:, None] * (diag if damping == "diagonal" else 1.0)
+        H = _mirror_lower(H)                                         # (the lower triangle is the matrix)
+        l, u = lo - x, hi - x
+        poisoned = ~(np.isfinite(x).all(axis=1) & np.isfinite(g).all(axis=1) & np.isfinite(lo).all() & np.isfinite(hi).all())
+
+        def residual(d):
+            r = g.copy()
+            for c in range(D):
+                r += H[:, :, c] * d[:, c, None]
+            return r
+        d = np.minimum(np.maximum(0.0, l), u)
+        r = residual(d)
+        cls = np.where((d <= l) & (r > 0.0), -1, np.where((d >= u) & (r < 0.0), 1, 0))
+        done = poisoned.copy()
+        status, passes = np.zeros(M, np.int32), np.zeros(M, np.int32)
+        cap = box_pass_cap(D)
+        eye = np.eye(D)
+        for _ in range(cap):
+            if done.all():
+                break
+            passes[~done] += 1
+            free = cls == 0
+            L = np.where(free[:, :, None] & free[:, None, :], H, eye)
+            st = _cholesky_factor_numpy(L)
+            failed = ~done & (st != 0)
+            status[failed] = st[failed]
+            done = done | failed
+            y = np.where(free, -r, 0.0)                              # y = L^-1 (-r_F)
+            for k in range(D):
+                y[:, k] = y[:, k] / L[:, k, k]
+                y[:, k + 1:] -= L[:, k + 1:, k] * y[:, k][:, None]
+            s = np.zeros((M, D))                                     # s = L^-T y
+            for i in range(D - 1, -1, -1):
+                a = y[:, i].copy()
+                for k in range(i + 1, D):
+                    a -= L[:, k, i] * s[:, k]
+                s[:, i] = a / L[:, i, i]
+            s = np.where(free, s, 0.0)
+            ratio = np.where(free & (s > 0.0), (u - d) / s, np.where(free & (s < 0.0), (l - d) / s, np.inf))
+            ratio[np.isnan(ratio)] = np.inf
+            k = np.argmin(ratio, axis=1)                             # (the lowest index of the minimum)
+            amin = ratio[rows, k]
+            blocked = amin < 1.0
+            dn = np.where(blocked[:, None], np.minimum(np.maximum(d + amin[:, None] * s, l), u), d + s)
+            cn = cls.copy()
+            up_ = s[rows, k] > 0.0
+            dn[blocked, k[blocked]] = np.where(up_, u[rows, k], l[rows, k])[blocked]
+            cn[blocked, k[blocked]] = np.where(up_, 1, -1)[blocked]
+            go = ~done
+            d[go], cls[go] = dn[go], cn[go]
+            r[go] = residual(d)[go]
+            mult = np.where(cls == -1, -r, np.where(cls == 1, r, -np.inf))
+            mult[np.isnan(mult)] = -np.inf
+            q = np.argmax(mult, axis=1)                              # (the lowest index of the maximum)
+            release = go & ~blocked & (mult[rows, q] > 0.0)
+            cls[release, q[release]] = 0
+            done = done | (go & ~blocked & ~release)
+        passes[~done] = cap + 1
+        ok = (status == 0)[:, None]
+        step = np.where(ok, d, 0.0)
+        trial = np.where(ok, _clip(x + step, (lo, hi)), x)
+        step[poisoned], trial[poisoned], passes[poisoned] = np.nan, np.nan, 0
+        clear = poisoned | (status != 0)
+        bits = np.uint64(1) << idx.astype(np.uint64)
+        at_lo = np.where(clear, 0, ((cls == -1) * bits).sum(axis=1)).astype(np.uint32)
+        at_hi = np.where(clear, 0, ((cls == 1) * bits).sum(axis=1)).astype(np.uint32)
+    return step, trial, status, at_lo, at_hi, passes
+
+
+def active_set_numpy(X, grad, A, prior, bounds):
+    """What the retrievals' ``return_active=True`` appends, from the returned ``X`` (M, D) and the loop's final ``grad``
+    (M, D), ``A`` (M, D, D) and prior (``prior_rows``' pair or None), in float64: ``active`` (M, D) int8, -1 where ``X <=
+    lo`` and ``g' > 0``, +1 where ``X >= hi`` and ``g' < 0``, 0 otherwise, with ``g' = grad (+ P (X - x0))``; and ``kkt``
+    (M,), the largest ``|g'_d| / sqrt(A'_dd)`` over the components with ``active == 0``, ``A' = A (+ P)`` -- the scaled
+    projected gradient: near 0 at a constrained minimum, whatever ``state`` says."""
+    X = np.asarray(X, dtype=np.float64)
+    M, D = X.shape
+    g = np.array(grad, dtype=np.float64).reshape(M, D)
+    Ad = np.array(A, dtype=np.float64).reshape(M, D, D)[:, np.arange(D), np.arange(D)]
+    lo, hi = (np.asarray(b, dtype=np.float64).reshape(D) for b in bounds)
+    with np.errstate(all="ignore"):
+        if prior is not None:
+            x0, P = prior_rows(prior, M, D)
+            Ad = Ad + P[..., np.arange(D), np.arange(D)]
+            for c in range(D):
+                g += P[..., :, c] * (X[:, c] - x0[..., c])[:, None]
+        active = np.where((X <= lo) & (g > 0.0), -1, np.where((X >= hi) & (g < 0.0), 1, 0)).astype(np.int8)
+        kkt = np.max(np.where(active == 0, np.abs(g) / np.sqrt(Ad), 0.0), axis=1)
+    return active, kkt
+
+
 def _cholesky_inverse_numpy(L):
     """``(W, status)`` for the matrices ``L`` (M, D, D), factored in place: ``W[:, i, j]``, i >= j, is element (i, j) of
     the inverse by the kernels' chains (ascending index in the factorisation and in both substitutions of every unit

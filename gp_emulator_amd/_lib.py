@@ -12,7 +12,7 @@ import threading
 
 import numpy as np
 
-from ._dense_numpy import (DAMPINGS, newton_step_numpy, posterior_cov_numpy, prec_rows, prior_propagate_numpy,  # noqa: F401
+from ._dense_numpy import (DAMPINGS, active_set_numpy, box_pass_cap, box_step_numpy, newton_step_numpy, posterior_cov_numpy, prec_rows, prior_propagate_numpy,  # noqa: F401
                            prior_rows, row_strides, rts_smooth_numpy, series_cov_numpy, series_objective_numpy,
                            series_step_numpy, series_update_numpy, _cholesky_inverse_numpy, _mirror_lower)
 from ._lut_numpy import MAX_PCS as lut_pc_max_pcs  # noqa: F401
@@ -85,6 +85,8 @@ SIGNATURES = {
     "gp_newton_step_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 7 + [c_i64, c_int]),
     "gp_lm_update_device": (c_int, [c_void_p, c_int] + [c_void_p] * 14 + [ctypes.c_double] * 6 + [c_i64, c_int]),
     "gp_posterior_cov_device": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_i64, c_int]),
+    "gp_box_step_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_i64, c_i64] + [c_void_p] * 8
+                           + [c_i64, c_int]),
     "gp_newton_step_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 7 + [c_i64, c_int, c_i64, c_i64]),
     "gp_lm_update_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 14 + [ctypes.c_double] * 6 + [c_i64, c_int, c_i64, c_i64]),
     "gp_posterior_cov_rows_device": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_i64, c_int, c_i64]),
@@ -561,6 +563,21 @@ class Context:
                                              d_prior_prec, d_lo, d_hi, d_step, d_trial, d_status, int(n_rows),
                                              int(n_inputs)), "gp_newton_step_device")
 
+    def box_step_device(self, dtype, d_x, d_grad, d_A, d_lambda, d_step, d_trial, d_status, n_rows, n_inputs, d_lo, d_hi,
+                        damping="diagonal", d_prior_mean=None, d_prior_prec=None, prior_mean_stride=0, prior_prec_stride=0,
+                        d_at_lo=None, d_at_hi=None, d_passes=None):
+        """Asynchronous bound-constrained damped Newton step of ``n_rows`` systems on the device
+        (``gp_box_step_device``): the system of ``newton_step_rows_device``, then ``step`` = the exact minimiser of the
+        damped model inside ``[lo - x, hi - x]`` by the primal active-set method, ``trial = clamp(x + step)``,
+        ``status`` int32 (0, or the 1-based index of the failed pivot: then step = 0, trial = x), ``at_lo`` / ``at_hi``
+        uint32 bit masks of the components held at a bound, ``passes`` int32.  Device pointers of ``dtype``; the bounds
+        are required; the prior pair, the masks, ``d_passes`` and one of ``d_step`` / ``d_trial`` may be None; a stride
+        of 0 is the shared prior."""
+        check(self.lib.gp_box_step_device(self.h, _dtype_code(dtype), d_x, d_grad, d_A, d_lambda, _DAMPING[damping], d_prior_mean,
+                                          d_prior_prec, int(prior_mean_stride), int(prior_prec_stride), d_lo, d_hi, d_step,
+                                          d_trial, d_status, d_at_lo, d_at_hi, d_passes, int(n_rows), int(n_inputs)),
+              "gp_box_step_device")
+
     def lm_update_device(self, dtype, d_x, d_trial, d_cost, d_cost_trial, d_grad, d_grad_trial, d_A, d_A_trial, d_lambda,
                          d_status, d_state, d_accepted, n_rows, n_inputs, d_prior_mean=None, d_prior_prec=None,
                          down=1.0 / 3.0, up=4.0, lambda_min=1e-12, lambda_max=1e12, ftol=1e-10, xtol=0.0):
@@ -845,6 +862,36 @@ class Context:
                                         d_lo, d_hi)
             return (_download(self, d_step, (M, D), dt), _download(self, d_trial, (M, D), dt),
                     _download(self, d_status, (M,), np.int32))
+
+    def box_step(self, x, grad, A, lam, damping="diagonal", prior=None, bounds=None, precision=None, is_gpu=True):
+        """``(step, trial, status, at_lo, at_hi, passes)`` of the bound-constrained damped Newton step for host arrays
+        as ``newton_step`` takes them: uploads, launches ``gp_box_step_device``, downloads.  ``bounds=(lo, hi)`` is
+        required.  ``is_gpu=False`` is the explicit numpy branch (``box_step_numpy``: the same algorithm in float64);
+        never a fallback."""
+        if bounds is None:
+            raise ValueError("the box step needs bounds")
+        if not is_gpu:
+            return box_step_numpy(x, grad, A, lam, damping, prior, bounds)
+        if damping not in _DAMPING:
+            raise ValueError("damping must be 'diagonal' or 'identity'")
+        x = np.asarray(x)
+        if x.ndim != 2:
+            raise ValueError("x must be (n_rows, n_inputs)")
+        dt = _device_dtype(precision, x)
+        M, D = x.shape
+        host = [x, np.reshape(grad, (M, D)), np.reshape(A, (M, D, D)), np.broadcast_to(np.asarray(lam, dtype=dt), (M,))]
+        host += list(prior_rows(prior, M, D, dt)) if prior is not None else [None, None]
+        strides = row_strides(host[4], host[5])
+        host += [np.reshape(b, D) for b in bounds]
+        with Scratch(self, dt) as scratch:
+            d_x, d_grad, d_A, d_lam, d_x0, d_P, d_lo, d_hi = [scratch.up(a) for a in host]
+            d_step, d_trial = scratch.alloc(M * D * dt.itemsize), scratch.alloc(M * D * dt.itemsize)
+            d_status, d_at_lo, d_at_hi, d_passes = (scratch.alloc(M * 4) for _ in range(4))
+            self.box_step_device(dt, d_x, d_grad, d_A, d_lam, d_step, d_trial, d_status, M, D, d_lo, d_hi, damping, d_x0, d_P,
+                                 strides[0], strides[1], d_at_lo, d_at_hi, d_passes)
+            return (_download(self, d_step, (M, D), dt), _download(self, d_trial, (M, D), dt),
+                    _download(self, d_status, (M,), np.int32), _download(self, d_at_lo, (M,), np.uint32),
+                    _download(self, d_at_hi, (M,), np.uint32), _download(self, d_passes, (M,), np.int32))
 
     def lut_search_device(self, dtype, d_table, table_strides, d_offset, d_obs, obs_strides, d_weights, w_strides, d_index,
                           d_cost, n_rows, n_candidates, n_terms, n_best, n_slices=0):

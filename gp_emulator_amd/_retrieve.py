@@ -52,19 +52,50 @@ def prior_and_bounds(prior, bounds, D, M=1):
     return prior, bounds
 
 
-def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov, next_prior=None, return_A=False):
+BOUNDS_MODES = ("clamp", "active_set")
+
+
+def check_bounds_mode(bounds_mode, bounds, return_active=False):
+    """The retrievals' argument rules of the bounds: ``bounds_mode`` is "clamp" (the unconstrained step, clamped) or
+    "active_set" (the box step: the minimiser of the damped model inside the box); the latter and ``return_active``
+    need ``bounds``."""
+    if bounds_mode not in BOUNDS_MODES:
+        raise ValueError("bounds_mode must be 'clamp' or 'active_set'")
+    if bounds_mode == "active_set" and bounds is None:
+        raise ValueError("bounds_mode='active_set' needs bounds")
+    if return_active and bounds is None:
+        raise ValueError("return_active needs bounds")
+
+
+def clamp_only(bounds_mode):
+    """The joint retrievals' rule: their block-tridiagonal step has the clamp only."""
+    if bounds_mode != "clamp":
+        raise ValueError("the joint retrieval offers bounds_mode='clamp' only")
+
+
+def numpy_step(prior, bounds, bounds_mode):
+    """The host loop's step: ``(x, grad, A, lam) -> (step, trial, status, ...)`` by ``newton_step_numpy`` or, with
+    ``bounds_mode="active_set"``, ``box_step_numpy`` (diagonal damping)."""
+    form = _lib.box_step_numpy if bounds_mode == "active_set" else _lib.newton_step_numpy
+    return lambda x, g, A, lam: form(x, g, A, lam, "diagonal", prior, bounds)
+
+
+def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, return_cov, next_prior=None, return_A=False,
+             active_bounds=None):
     """The loop on the host in float64: ``data_term(X) -> (cost, grad, A)``, ``step(x, grad, A, lam) -> (step, trial,
     status)``.  Returns ``(X, cost, state, n_accepted, lam)``, with ``return_cov`` ``_lib.posterior_cov_numpy``'s
     three of the loop's ``A`` behind them, and with a process noise ``next_prior`` ``_lib.prior_propagate_numpy``'s
-    two behind those; ``return_A`` appends the loop's final data-term matrix ``A (M, D, D)`` as the last element (what
-    the smoother of a series needs of a date)."""
+    two behind those; ``return_A`` appends the loop's final data-term matrix ``A (M, D, D)`` behind those (what
+    the smoother of a series needs of a date); ``active_bounds=(lo, hi)`` (the callers' ``return_active``) appends
+    ``_lib.active_set_numpy``'s two of the returned ``X`` and the loop's final ``grad``, ``A`` and prior as the last
+    elements.  Only the first three of what ``step`` returns are read."""
     M = X0.shape[0]
     X = np.array(X0, dtype=np.float64)
     lam = np.full(M, float(lam0))
     state, n_acc = np.zeros(M, np.int32), np.zeros(M, np.int32)
     cost, grad, A = (np.array(a) for a in data_term(X))
     for it in range(max_iter):
-        _, trial, status = step(X, grad, A, lam)
+        _, trial, status = step(X, grad, A, lam)[:3]
         trial = np.asarray(trial, dtype=np.float64)
         cost_t, grad_t, A_t = data_term(trial)
         n_acc += _lm_update_numpy(X, trial, cost, cost_t, grad, grad_t, A, A_t, lam, np.asarray(status), state, prior,
@@ -78,6 +109,8 @@ def lm_numpy(data_term, step, X0, lam0, max_iter, down, up, ftol, xtol, prior, r
         out += _lib.prior_propagate_numpy(A, prior[1] if prior is not None else None, next_prior)
     if return_A:
         out += (A,)
+    if active_bounds is not None:
+        out += _lib.active_set_numpy(X, grad, A, prior, active_bounds)
     return out
 
 
@@ -85,7 +118,7 @@ Scratch = _lib.Scratch     # the device arrays of one call (the loop's callers o
 
 
 def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov, misfit, next_prior=None,
-              return_A=False):
+              return_A=False, bounds_mode="clamp", return_active=False):
     """The loop on the device from the host rows ``X0``, in the precision and on the context of ``scratch`` (the
     caller's ``Scratch``, which also holds whatever ``misfit`` reads).  ``misfit(d_rows, d_cost, d_grad, d_A)`` enqueues
     the data term at ``d_rows`` on the context's stream.  Every iteration is that, ``lm_update_device`` and
@@ -94,7 +127,12 @@ def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, 
     with the arrays' row strides; with a shared or absent prior the calls are exactly the plain ones.  A process noise
     ``next_prior`` (D, D) or (M, D, D) adds one ``prior_propagate_device`` call after the loop (and after the
     covariance) on the loop's own ``d_A`` and ``d_P``; ``return_A`` adds one download, of ``d_A``, behind everything
-    else.  Returns what ``lm_numpy`` returns, in the scratch's precision."""
+    else.  ``bounds_mode="active_set"`` calls ``box_step_device`` where the Newton step is called (one entry for the
+    shared and the per-row prior: the strides say which); ``"clamp"`` makes exactly the calls it always made.
+    ``return_active`` adds one download, of ``d_grad`` (and of ``d_A`` unless ``return_A`` brought it), and appends
+    ``_lib.active_set_numpy``'s two, in float64 numpy from the downloaded arrays.  Returns what ``lm_numpy`` returns, in
+    the scratch's precision."""
+    check_bounds_mode(bounds_mode, bounds, return_active)
     ctx, dt = scratch.ctx, scratch.dt
     up_, alloc, isz = scratch.up, scratch.alloc, dt.itemsize
     d_x, d_lam = up_(X0), up_(np.full(M, float(lam0)))
@@ -110,7 +148,10 @@ def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, 
     rows = any(strides)
 
     def newton():
-        if rows:
+        if bounds_mode == "active_set":
+            ctx.box_step_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, d_lo, d_hi, "diagonal", d_x0, d_P,
+                                strides[0], strides[1])
+        elif rows:
             ctx.newton_step_rows_device(dt, d_x, d_grad, d_A, d_lam, None, d_trial, d_status, M, D, "diagonal", d_x0,
                                         d_P, d_lo, d_hi, strides[0], strides[1])
         else:
@@ -153,8 +194,11 @@ def lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, 
         ctx.prior_propagate_device(dt, d_A, d_P, strides[1], d_Q, _lib.row_strides(None, Q)[1], d_next, d_pstat, M, D)
         ctx.synchronize()
         out += (np.array(ctx.to_host(d_next, (M, D, D), dt)), np.array(ctx.to_host(d_pstat, (M,), np.int32)))
+    A_host = np.array(ctx.to_host(d_A, (M, D, D), dt)) if return_A or return_active else None
     if return_A:
-        out += (np.array(ctx.to_host(d_A, (M, D, D), dt)),)
+        out += (A_host,)
+    if return_active:
+        out += _lib.active_set_numpy(X, np.array(ctx.to_host(d_grad, (M, D), dt)), A_host, prior, bounds)
     return out
 
 

@@ -126,6 +126,7 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
               ("gp_gram_tu.hip", "gram", []), ("gp_var_grad_operand_tu.hip", "vargrad_operand", []),
               ("gp_band_misfit_tu.hip", "band_misfit", []), ("gp_band_unc_tu.hip", "band_unc", []),
               ("gp_mv_unc_tu.hip", "mv_unc", []), ("gp_newton_tu.hip", "newton", []),
+              ("gp_box_step_tu.hip", "box_step", []),
               ("gp_series_tu.hip", "series", []),
               ("gp_lut_search_tu.hip", "lut_search", []), ("gp_lut_search_pc_tu.hip", "lut_search_pc", []),
               ("gp_lut_posterior_tu.hip", "lut_posterior", []),

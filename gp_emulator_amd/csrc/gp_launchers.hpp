@@ -16,6 +16,7 @@ template <typename T> struct BandMisfitArgs;
 template <typename T> struct BandUncArgs;
 template <typename T> struct NewtonArgs;
 template <typename T> struct LmUpdateArgs;
+template <typename T> struct BoxStepArgs;
 template <typename T> struct PosteriorCovArgs;
 template <typename T> struct PriorPropagateArgs;
 template <typename T> struct RtsSmoothArgs;
@@ -53,6 +54,7 @@ template <typename T> hipError_t launch_band_misfit_add(const T* gn, T* hess, lo
 template <typename T> hipError_t launch_band_unc_fold(const BandUncArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_newton_step(const NewtonArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_lm_update(const LmUpdateArgs<T>&, hipStream_t);
+template <typename T> hipError_t launch_box_step(const BoxStepArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_posterior_cov(const PosteriorCovArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_prior_propagate(const PriorPropagateArgs<T>&, hipStream_t);
 template <typename T> hipError_t launch_rts_smooth(const RtsSmoothArgs<T>&, hipStream_t);

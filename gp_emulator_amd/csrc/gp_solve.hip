@@ -1,9 +1,10 @@
-// The small dense solves on device buffers: damped Newton step, LM update, posterior covariance, prior propagation and
+// The small dense solves on device buffers: damped Newton step, its bound-constrained form, LM update, posterior covariance, prior propagation and
 // the smoother's backward step, the joint step, update and covariance of a whole series; the look-up-table search that starts a retrieval and the look-up-table posterior.  Device arrays in, device arrays
 // out, no model.  The Sobol indices of a batch of emulators and their moments under a Gaussian input, on host arrays
 // (no model either).
 #include "gp_host.hpp"
 
+#include "gp_box_step_kernel.hpp"
 #include "gp_launch_plan.hpp"
 #include "gp_launchers.hpp"
 #include "gp_lut_posterior_kernel.hpp"
@@ -87,6 +88,48 @@ int gp_newton_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d
                           int64_t n_rows, int n_inputs) {
   return gp_newton_step_rows_device(ctx, dtype, d_x, d_grad, d_A, d_lambda, damping, d_prior_mean, d_prior_prec, d_lo, d_hi,
                                     d_step, d_trial, d_status, n_rows, n_inputs, 0, 0);
+}
+
+int gp_box_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A, const void* d_lambda,
+                       int damping, const void* d_prior_mean, const void* d_prior_prec, int64_t prior_mean_stride,
+                       int64_t prior_prec_stride, const void* d_lo, const void* d_hi, void* d_step, void* d_trial,
+                       int32_t* d_status, uint32_t* d_at_lo, uint32_t* d_at_hi, int32_t* d_passes, int64_t n_rows,
+                       int n_inputs) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!d_x || !d_grad || !d_A || !d_lambda || !d_status || (!d_step && !d_trial))
+    return fail(GP_ERR_INVALID, "null device pointer");
+  if (!d_lo || !d_hi) return fail(GP_ERR_INVALID, "the box step needs both bounds");
+  if (int rc = newton_sizes(dtype, n_rows, n_inputs)) return rc;
+  if (damping != GP_DAMP_DIAGONAL && damping != GP_DAMP_IDENTITY) return fail(GP_ERR_INVALID, "bad damping %d", damping);
+  if ((d_prior_mean != nullptr) != (d_prior_prec != nullptr))
+    return fail(GP_ERR_INVALID, "prior mean and prior precision go together");
+  if (int rc = row_stride("prior mean", d_prior_mean, prior_mean_stride, n_inputs)) return rc;
+  if (int rc = row_stride("prior precision", d_prior_prec, prior_prec_stride, (int64_t)n_inputs * n_inputs)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return for_dtype(dtype, [&](auto t) {
+    using T = GP_TAG_TYPE(t);
+    gpk::BoxStepArgs<T> a;
+    a.x = as<T>(d_x);
+    a.grad = as<T>(d_grad);
+    a.A = as<T>(d_A);
+    a.lambda = as<T>(d_lambda);
+    a.prior_mean = as<T>(d_prior_mean);
+    a.prior_prec = as<T>(d_prior_prec);
+    a.prior_mean_stride = prior_mean_stride;
+    a.prior_prec_stride = prior_prec_stride;
+    a.lo = as<T>(d_lo);
+    a.hi = as<T>(d_hi);
+    a.step = as<T>(d_step);
+    a.trial = as<T>(d_trial);
+    a.status = d_status;
+    a.at_lo = d_at_lo;
+    a.at_hi = d_at_hi;
+    a.passes = d_passes;
+    a.rows = n_rows;
+    a.d = n_inputs;
+    a.diagonal = damping == GP_DAMP_DIAGONAL ? 1 : 0;
+    return launched(gpk::launch_box_step<T>(a, ctx->stream), "box step");
+  });
 }
 
 int gp_lm_update_rows_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_trial, void* d_cost,

@@ -619,7 +619,7 @@ class MultivariateEmulator(object):
 
     def retrieve_many(self, Y0, obs, weights=None, prior=None, bounds=None, lam0=1e-2, max_iter=20, down=1.0 / 3.0,
                       up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False, next_prior=None,
-                      return_A=False, emulator_unc=False):
+                      return_A=False, emulator_unc=False, bounds_mode="clamp", return_active=False):
         """Levenberg-Marquardt retrieval of M state vectors at once on this emulator: minimises, row by row,
 
             F(y) = 1/2 sum_b w_b (f_b(y) - obs_b)^2  (+ 1/2 (y - y0)^T P (y - y0) with ``prior=(y0 (D,), P (D, D))``)
@@ -676,8 +676,13 @@ class MultivariateEmulator(object):
         emulators' share of the error.  On the GPU an iteration is then ``predict_mean_grad_device``,
         ``predict_var_grad_device``, ``mv_misfit_device`` (cost and ``basis (w * r)``, no gradient) and
         ``mv_misfit_unc_device`` with the matrix formed once before the loop, then the same update and step; the numpy
-        branch hands the loop the numpy form of that term.  With ``False`` nothing changes."""
+        branch hands the loop the numpy form of that term.  With ``False`` nothing changes.
+
+        ``bounds_mode="active_set"`` (default "clamp": nothing changes) replaces the clamped step by the exact minimiser of
+        the damped model inside the box, and ``return_active=True`` appends ``active (M, D) int8`` and ``kkt (M,)`` behind
+        everything else; both need ``bounds`` and are ``retrieve_bands``' arguments word for word."""
         from . import _first_guess, _retrieve
+        _retrieve.check_bounds_mode(bounds_mode, bounds, return_active)
         Y0 = np.asarray(Y0)
         if Y0.ndim != 2:
             raise ValueError("Y0 must be (n_rows, n_inputs)")
@@ -691,17 +696,17 @@ class MultivariateEmulator(object):
         max_iter = int(max_iter)
 
         if not is_gpu:
-            def step(x, g, A, lam):
-                return _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds)
+            step = _retrieve.numpy_step(prior, bounds, bounds_mode)
             return _retrieve.lm_numpy(self._retrieval_term_numpy(obs, weights, emulator_unc), step, Y0, lam0, max_iter, down,
-                                      up, ftol, xtol, prior, return_cov, next_prior, return_A)
+                                      up, ftol, xtol, prior, return_cov, next_prior, return_A,
+                                      bounds if return_active else None)
 
         dt = np.dtype(precision)
         st = self._fresh_gpu_state(dt)
         with _retrieve.Scratch(st["ctx"], dt) as scratch:
             misfit = self._retrieval_term_device(scratch, st, obs, weights, M, D, emulator_unc)
             return _retrieve.lm_device(scratch, M, D, Y0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                       misfit, next_prior, return_A)
+                                       misfit, next_prior, return_A, bounds_mode, return_active)
 
     def _retrieval_term_numpy(self, obs, weights, emulator_unc):
         """The data term of the retrievals on the host: ``X (R, D) -> (cost, grad, A)`` for ``obs`` and ``weights`` as
@@ -756,7 +761,7 @@ class MultivariateEmulator(object):
 
     def retrieve_joint(self, Y0, obs, weights, prior, noise, bounds=None, lam0=1e-2, max_iter=20, down=1.0 / 3.0, up=4.0,
                        ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64, return_cov=False, emulator_unc=False,
-                       second_order="gauss_newton", work_budget=None):
+                       second_order="gauss_newton", work_budget=None, bounds_mode="clamp"):
         """Joint maximum a posteriori retrieval of M trajectories of T dates on this emulator: what
         ``perband.retrieve_bands_joint`` is to ``retrieve_bands`` (the objective, the loop, the keywords, the returned
         ``(Y (T, M, D), sigma (T, M, D), cost (T, M), F (M,), state, n_accepted, lam, cov_status)`` and ``cov (T, M, D,
@@ -765,8 +770,10 @@ class MultivariateEmulator(object):
         every date and pixel, (T, N_full) or (T, M, N_full); ``Y0`` (T, M, D), or (M, D) taken for every date; ``prior`` is
         date 0's, required.  One data-term call runs on the T M rows of all dates; with anything but one weight vector
         for all of them the per-row Gram matrices are formed for those rows, once.  ``second_order`` is "gauss_newton"
-        only.  ``is_gpu=False`` is the explicit numpy branch; never a fallback."""
+        only.  ``is_gpu=False`` is the explicit numpy branch; never a fallback.  ``bounds_mode`` is "clamp"
+        only (``ValueError`` otherwise): the box step has no block-tridiagonal form yet."""
         from . import _first_guess, _retrieve
+        _retrieve.clamp_only(bounds_mode)
         if second_order != "gauss_newton":
             raise ValueError("the joint retrieval needs second_order='gauss_newton': the Hessian of F must stay positive definite")
         if prior is None:

@@ -403,7 +403,8 @@ def misfit_bands(gps, X, obs, weights=None, second_order=None, return_residual=F
 
 def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prior=None, bounds=None, lam0=1e-2,
                    max_iter=20, down=1.0 / 3.0, up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64,
-                   device=None, step_fn=None, return_cov=False, next_prior=None, return_A=False, emulator_unc=False):
+                   device=None, step_fn=None, return_cov=False, next_prior=None, return_A=False, emulator_unc=False,
+                   bounds_mode="clamp", return_active=False):
     """Levenberg-Marquardt retrieval of M state vectors at once on E per-band emulators: minimises, row by row,
 
         F(x) = 1/2 sum_e w (mu_e(x) - obs[e])^2  (+ 1/2 (x - x0)^T P (x - x0) with ``prior=(x0 (D,), P (D, D))``)
@@ -435,7 +436,8 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     ``cov`` and ``sigma`` are NaN.  ``A`` is the matrix of the row's last accepted step (the one at the returned
     ``X``), WITHOUT the damping: the Gauss-Newton term by default; with ``second_order="full"`` the full
     second-order term, which may be indefinite away from a minimum -- ``cov_status`` then says so.  Active bounds are
-    ignored: a component held at its bound gets the unconstrained variance.  ``C`` is a covariance only when
+    ignored: a component held at its bound gets the unconstrained variance (``return_active=True`` says which
+    components those are).  ``C`` is a covariance only when
     ``weights`` are the inverse variances of the observations (and ``P`` that of the prior).  On the GPU this is one
     ``posterior_cov_device`` call on the loop's own device arrays after the loop, and only the three results come
     back; on the numpy branch ``_lib.posterior_cov_numpy`` on the loop's ``A``.  With ``False`` nothing changes.
@@ -461,11 +463,24 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     predictive variance widens its observation's, ``A`` is the Fisher matrix, and ``cov``, ``sigma``, ``next_prec``, ``A``
     and the smoother of ``retrieve_bands_series`` then carry the emulators' share of the error.  The loop is the same;
     only the misfit it calls differs (``misfit_unc_device`` on a batch built with invQ; ``_misfit_unc_numpy``).
-    ``second_order="full"`` raises ``ValueError``.  With ``False`` nothing changes."""
+    ``second_order="full"`` raises ``ValueError``.  With ``False`` nothing changes.
+
+    ``bounds_mode`` is "clamp" (the default: the step above, bit for bit what it always was) or "active_set": the trial
+    is then ``x + delta`` with ``delta`` the exact minimiser of the damped model ``1/2 d^T (A + P + lambda diag) d + g'^T d``
+    inside the box ``lo - x <= d <= hi - x`` (``gp_box_step_device``, a primal active-set method; ``_lib.box_step_numpy``
+    on the numpy branch; DESIGN.md, "Bound-constrained step").  A row that sits on a bound with correlated parameters then
+    takes a descent step where the clamped one is rejected.  It needs ``bounds``; the rest of the loop is unchanged.
+
+    ``return_active=True`` (either mode; needs ``bounds``) appends, behind everything else, ``active (M, D) int8`` -- -1
+    where ``X <= lo`` and ``g' > 0``, +1 where ``X >= hi`` and ``g' < 0``, 0 otherwise, ``g' = grad + P (X - x0)`` at the
+    returned ``X`` -- and ``kkt (M,)``, the largest ``|g'_d| / sqrt((A + P)_dd)`` over the components with ``active == 0``:
+    the scaled projected gradient, which tells whether a row flagged unconverged is in fact at a constrained minimum.
+    Numpy arithmetic in both branches; on the GPU one more download, of the loop's gradient."""
     if second_order not in ("gauss_newton", "full"):
         raise ValueError("second_order must be 'gauss_newton' or 'full'")
     if emulator_unc:
         _check_unc_order(second_order)
+    _retrieve.check_bounds_mode(bounds_mode, bounds, return_active)
     X0, inputs = _rows_and_inputs(gps, X0, "X0")
     E, (M, D) = len(gps), X0.shape
     obs = _em_broadcast(obs, E, M, "obs")
@@ -476,17 +491,17 @@ def retrieve_bands(gps, X0, obs, weights=None, second_order="gauss_newton", prio
     max_iter = int(max_iter)
 
     if step_fn is not None or not is_gpu:
-        step = step_fn if step_fn is not None else (
-            lambda x, g, A, lam: _lib.newton_step_numpy(x, g, A, lam, "diagonal", prior, bounds))
+        step = step_fn if step_fn is not None else _retrieve.numpy_step(prior, bounds, bounds_mode)
         return _retrieve.lm_numpy(_data_term_numpy(gps, obs, weights, second_order, emulator_unc), step, X0, lam0,
-                                  max_iter, down, up, ftol, xtol, prior, return_cov, next_prior, return_A)
+                                  max_iter, down, up, ftol, xtol, prior, return_cov, next_prior, return_A,
+                                  bounds if return_active else None)
 
     ctx = _lib.default_context(device)
     with _batch_model(ctx, gps, inputs, precision, bool(emulator_unc)) as batch, \
             _retrieve.Scratch(ctx, np.dtype(precision)) as scratch:
         misfit = _data_term_device(batch, scratch, obs, weights, M, second_order, emulator_unc)
         return _retrieve.lm_device(scratch, M, D, X0, lam0, prior, bounds, max_iter, down, up, ftol, xtol, return_cov,
-                                   misfit, next_prior, return_A)
+                                   misfit, next_prior, return_A, bounds_mode, return_active)
 
 
 def _data_term_numpy(gps, obs, weights, second_order, emulator_unc):
@@ -526,7 +541,7 @@ def _joint_em_rows(a, T, E, M, name):
 
 def retrieve_bands_joint(gps, X0, obs, weights, prior, noise, second_order="gauss_newton", bounds=None, lam0=1e-2,
                          max_iter=20, down=1.0 / 3.0, up=4.0, ftol=1e-10, xtol=0.0, is_gpu=True, precision=np.float64,
-                         device=None, return_cov=False, emulator_unc=False, work_budget=None):
+                         device=None, return_cov=False, emulator_unc=False, work_budget=None, bounds_mode="clamp"):
     """Joint maximum a posteriori retrieval of M trajectories of T dates on E per-band emulators: minimises, pixel by
     pixel and over all dates at once, the objective the series is built around,
 
@@ -556,7 +571,10 @@ def retrieve_bands_joint(gps, X0, obs, weights, prior, noise, second_order="gaus
 
     On the GPU the pixels are cut into runs whose work memory (the factors between the two sweeps, 8 (D (D + 1) / 2 +
     D (D | 1) + D) bytes per pixel and date) stays under ``work_budget`` bytes (default 1 GiB); the cut changes no
-    bit.  ``is_gpu=False`` is the explicit numpy branch (``_retrieve.lm_series_numpy``); never a fallback."""
+    bit.  ``is_gpu=False`` is the explicit numpy branch (``_retrieve.lm_series_numpy``); never a fallback.
+    ``bounds_mode`` is "clamp" only: the box step of ``retrieve_bands`` has no block-tridiagonal form yet, and anything
+    else raises ``ValueError``."""
+    _retrieve.clamp_only(bounds_mode)
     if second_order != "gauss_newton":
         raise ValueError("the joint retrieval needs second_order='gauss_newton': the Hessian of F must stay positive definite")
     if prior is None:

@@ -504,6 +504,31 @@ int gp_lm_update_rows_device(gp_ctx* ctx, int dtype, void* d_x, const void* d_tr
                              double up, double lambda_min, double lambda_max, double ftol, double xtol,
                              int64_t n_rows, int n_inputs, int64_t prior_mean_stride, int64_t prior_prec_stride);
 
+/* ---- bound-constrained damped Newton step ------------------------------------------------------------
+ * gp_newton_step_rows_device's A', g' and damping (the same chains, bit for bit; H = the damped A'), then, in place of
+ * the clamp of the unconstrained step, the exact minimiser of the damped model inside the box:
+ *   delta = argmin 1/2 d^T H d + g'^T d   subject to   lo - x_m <= d <= hi - x_m
+ * by a primal active-set method whose order csrc/gp_box_step_kernel.hpp states: deterministic, every iterate feasible,
+ * at most 3 D + 4 passes of one Cholesky factorisation (of H with the rows and columns of the bound components replaced
+ * by the identity) and two substitutions each.
+ *   step[m]   = delta                     d_step  [n_rows][D]
+ *   trial[m]  = clamp((T)(x_m + delta), lo, hi)   d_trial [n_rows][D]: the sum in double, rounded once, clamped in `dtype`
+ *   status[m] = 0, or k + 1 when pivot k of any pass is not > 0 or not finite; then step[m] = 0, trial[m] = x_m
+ *   at_lo[m], at_hi[m]                    uint32 bit masks (bit d = component d) of the components the minimiser holds
+ *                                         at its lower / upper bound with a multiplier of the right sign; may be NULL
+ *   passes[m]                             int32, the passes the row ran; 3 D + 5 for a row that was cut off at the cap
+ *                                         (it returns its iterate: feasible, no worse than the start); may be NULL
+ * A row with a non-finite x, g', lo or hi: step and trial NaN in every element, status 0, masks 0, passes 0; every
+ * other row is bit for bit the call without it.  When no bound is touched along the way (pass 1 takes the full step and
+ * no multiplier asks for a release) step, trial and status are bit for bit gp_newton_step_rows_device's.
+ * d_lo and d_hi are required; stride 0 is the shared prior; every other argument rule and error code is
+ * gp_newton_step_rows_device's.  Asynchronous on the context's stream. */
+int gp_box_step_device(gp_ctx* ctx, int dtype, const void* d_x, const void* d_grad, const void* d_A, const void* d_lambda,
+                       int damping, const void* d_prior_mean, const void* d_prior_prec, int64_t prior_mean_stride,
+                       int64_t prior_prec_stride, const void* d_lo, const void* d_hi, void* d_step, void* d_trial,
+                       int32_t* d_status, uint32_t* d_at_lo, uint32_t* d_at_hi, int32_t* d_passes, int64_t n_rows,
+                       int n_inputs);
+
 /* ---- posterior covariance ----------------------------------------------------------------------------
  * The inverse of the matrix the Newton step factors, without the damping: what a retrieval reports beside its
  * state as x +- sigma, from the d_A (and prior precision) that the loop above leaves on the device.  For each of

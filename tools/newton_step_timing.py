@@ -7,6 +7,7 @@ retrieve_bands iteration against its misfit_device alone.  Prints one JSON line 
     python tools/newton_step_timing.py --legs posterior [--out FILE] [--reps 50] [--warmup 5]
     python tools/newton_step_timing.py --legs rows,propagate [--shared-only] [--out FILE]
     python tools/newton_step_timing.py --legs smooth,smooth_series [--out FILE] [--reps 30]
+    python tools/newton_step_timing.py --legs box,box_loop [--out FILE] [--reps 30]
     python tools/newton_step_timing.py --legs registers        # no GPU: compiles csrc/gp_newton_tu.hip once
 
 device     gp_newton_step_device at M = 1e5 rows, D in {11, 16}, both dtypes, trial and status out: the median of
@@ -38,6 +39,17 @@ smooth     gp_rts_smooth_device (x_smooth, cov_smooth, sigma_smooth, status out)
            D in {11, 16, 32}, both dtypes, P and Q shared and per row; the numpy branch on --numpy-rows rows, scaled to M.
 smooth_series  one retrieve_bands_series at E = 12, N = 250, D = 11, 1e5 rows, T = 8: wall clock of the forward pass, of
            the smoothed series and of the backward pass alone (profiles/r13_rts_smooth.txt quotes both legs).
+box        gp_box_step_device (trial, status, masks and passes out) against gp_newton_step_device (trial and status out)
+           on the same resident rows and bounds, alternating inside one loop, each call between its own pair of events:
+           M = 1e5, D = 11, both dtypes, three inputs -- "free" (bounds at -+1e30: no bound can be active), "one" (about
+           30 % of the rows have one component on a bound that the Newton direction pushes against) and "hard" (column
+           scales log-uniform over four decades, 30 % of the components start on the lower and 20 % on the upper bound,
+           lambda log-uniform in [1e-12, 1e-2]).  Per input the two medians, their ratio, the share of rows with an
+           active bound and the histogram of ``passes`` (profiles/r23_box_step.txt quotes such a run's lines).
+box_loop   the toy of the box step's issue through retrieve_bands in both bounds modes, on the device (float64) and on
+           the numpy branch: E = 12 trained-like emulators on D = 6 inputs with two pairs of correlated columns, 400 rows,
+           box [0, 1]^D, truths from [-0.3, 1.3], weight 1e4, max_iter 10, 20, 60: the share of converged rows, the median
+           data cost and the share of rows whose scaled projected gradient is above 1e-3 sqrt(cost + 1).
 
 Every leg that touches the GPU runs under the caller's time limit, e.g.
     timeout -k 10 300 python tools/newton_step_timing.py --legs device,host,iteration --out profiles/r09_newton_step.txt
@@ -464,6 +476,96 @@ def leg_iteration(a):
         batch.close()
 
 
+def box_inputs(kind, D, dt):
+    """(x, grad, A, lam, lo, hi) of the box leg's three inputs."""
+    rs = np.random.RandomState(500 + D)
+    if kind == "hard":
+        scale = 10.0 ** rs.uniform(-2.0, 2.0, D)
+        J = rs.standard_normal((M, D + 8, D)) * scale
+        A = np.einsum("med,mef->mdf", J, J)
+        g = np.einsum("me,med->md", rs.standard_normal((M, D + 8)), J)
+        u = rs.uniform(size=(M, D))
+        x = np.where(u < 0.3, 0.0, np.where(u < 0.5, 1.0, rs.uniform(0.05, 0.95, (M, D))))
+        lam = 10.0 ** rs.uniform(-12.0, -2.0, M)
+        return x.astype(dt), g.astype(dt), A.astype(dt), lam.astype(dt), np.zeros(D, dt), np.ones(D, dt)
+    x, g, A, lam = systems(D, dt)
+    if kind == "free":
+        return x, g, A, lam, np.full(D, -1e30, dt), np.full(D, 1e30, dt)
+    # "one": steps of a hundredth of the box from rows well inside it, then 30 % of the rows get the component of their
+    # largest step put on the bound that step points at
+    g = (0.05 * g).astype(dt)
+    A64 = A.astype(np.float64)
+    idx = np.arange(D)
+    A64[:, idx, idx] *= 1.0 + 1e-2
+    step = -np.linalg.solve(A64, g.astype(np.float64)[:, :, None])[:, :, 0]
+    x = rs.uniform(0.3, 0.7, (M, D))
+    rows = np.flatnonzero(rs.uniform(size=M) < 0.3)
+    c = np.argmax(np.abs(step[rows]), axis=1)
+    x[rows, c] = np.where(step[rows, c] < 0.0, 0.0, 1.0)
+    return x.astype(dt), g, A, lam, np.zeros(D, dt), np.ones(D, dt)
+
+
+def leg_box(a):
+    ctx = _lib.default_context(0)
+    D = 11
+    for prec in (np.float64, np.float32):
+        dt = np.dtype(prec)
+        for kind in ("free", "one", "hard"):
+            host = box_inputs(kind, D, dt)
+            d_x, d_g, d_A, d_lam, d_lo, d_hi = dev = [ctx.to_device(v) for v in host]
+            outs = [ctx.malloc(M * D * dt.itemsize), ctx.malloc(M * D * dt.itemsize)] + [ctx.malloc(M * 4) for _ in range(5)]
+            d_t_n, d_t_b, d_s_n, d_s_b, d_lo_m, d_hi_m, d_pass = outs
+            calls = {
+                "newton": lambda: ctx.newton_step_device(dt, d_x, d_g, d_A, d_lam, None, d_t_n, d_s_n, M, D, "diagonal", None, None,
+                                                         d_lo, d_hi),
+                "box": lambda: ctx.box_step_device(dt, d_x, d_g, d_A, d_lam, None, d_t_b, d_s_b, M, D, d_lo, d_hi, "diagonal",
+                                                   None, None, 0, 0, d_lo_m, d_hi_m, d_pass),
+            }
+            t = timed_alternating(ctx, calls, a)
+            passes = np.array(ctx.to_host(d_pass, (M,), np.int32))
+            masks = np.array(ctx.to_host(d_lo_m, (M,), np.uint32)) | np.array(ctx.to_host(d_hi_m, (M,), np.uint32))
+            failed = int(np.count_nonzero(np.array(ctx.to_host(d_s_b, (M,), np.int32))))
+            same_trial = bool(np.array_equal(np.array(ctx.to_host(d_t_n, (M, D), dt)), np.array(ctx.to_host(d_t_b, (M, D), dt))))
+            emit(a, leg="box", input=kind, dtype=dt.name, M=M, D=D, newton=stats(t["newton"]), box=stats(t["box"]),
+                 ratio=round(float(np.median(t["box"]) / np.median(t["newton"])), 3),
+                 rows_with_an_active_bound=round(float(np.mean(masks != 0)), 4), failed_rows=failed,
+                 trial_equals_newton=same_trial, passes_mean=round(float(passes.mean()), 3), passes_max=int(passes.max()),
+                 cap=3 * D + 4, passes_histogram={str(k): int(n) for k, n in enumerate(np.bincount(passes)) if n})
+            for p in dev + outs:
+                ctx.free(p)
+
+
+def leg_box_loop(a):
+    from gp_emulator_amd import GaussianProcess, perband
+    E, D, N, rows = 12, 6, 60, 400
+    rs = np.random.RandomState(2024)
+    X = rs.uniform(-0.4, 1.4, (N, D))
+    ee, bb = np.full(D, 0.3), 4.0
+    diff = X[:, None, :] - X[None, :, :]
+    Q = bb * np.exp(-0.5 * ((diff * diff) @ ee)) + 1e-5 * np.eye(N)
+    pair = np.zeros((2, D))
+    pair[0, :2], pair[1, 2:4] = 1.0, 1.0
+    gps = []
+    for e in range(E):
+        w = 0.3 * rs.standard_normal(D) + rs.standard_normal(2) @ pair
+        gp = GaussianProcess(X, [])
+        gp.theta, gp.invQt = np.log(np.concatenate([ee, [bb, 1e-5]])), np.linalg.solve(Q, X @ w + 0.2 * np.sin(X @ rs.standard_normal(D)))
+        gps.append(gp)
+    truth = rs.uniform(-0.3, 1.3, (rows, D))
+    obs = np.stack([gp.cpu_predict(truth, do_unc=False)[0] for gp in gps])
+    X0, bounds, w = rs.uniform(0.3, 0.7, (rows, D)), (np.zeros(D), np.ones(D)), np.full(E, 1e4)
+    for is_gpu in (False, True):
+        for mode in ("clamp", "active_set"):
+            for it in (10, 20, 60):
+                out = perband.retrieve_bands(gps, X0, obs, w, bounds=bounds, is_gpu=is_gpu, bounds_mode=mode, return_active=True,
+                                             max_iter=it)
+                cost, kkt = out[1].astype(np.float64), out[-1]
+                emit(a, leg="box_loop", branch="device f64" if is_gpu else "numpy", bounds_mode=mode, max_iter=it, rows=rows, D=D, E=E,
+                     converged=round(float(np.mean(out[2] == 1)), 4), median_cost=round(float(np.median(cost)), 3),
+                     not_at_a_kkt_point=round(float(np.mean(kkt > 1e-3 * np.sqrt(cost + 1.0))), 4),
+                     components_on_a_bound=round(float(np.mean(out[-2] != 0)), 4))
+
+
 def leg_registers(a):
     """What the compiler reports for every instance in csrc/gp_newton_tu.hip, with build.py's flags."""
     src = os.path.join(gp_build.CSRC, "gp_newton_tu.hip")
@@ -536,3 +638,7 @@ if __name__ == "__main__":
         leg_smooth(a)
     if "smooth_series" in legs:
         leg_smooth_series(a)
+    if "box" in legs:
+        leg_box(a)
+    if "box_loop" in legs:
+        leg_box_loop(a)
