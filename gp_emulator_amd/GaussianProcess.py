@@ -408,6 +408,29 @@ class GaussianProcess:
         boxed = np.ndim(bounds[0]) == 2
         return r._replace(**{k: (v[:, 0] if boxed else v[0]) for k, v in r._asdict().items()})
 
+    def sobol_interactions(self, bounds, is_gpu=False):
+        """Second-order Sobol indices on ``bounds`` as ``sobol_indices`` takes them: ``SobolInteractions(second (D, D),
+        higher, first (D,), total (D,), variance, mean)`` -- ``second[i, k] = (Var(E[mu | t_i, t_k]) - Vm^i - Vm^k) / V``
+        off the diagonal (symmetric) and ``first`` on it, ``higher = 1 - sum_{i <= k} second``, the share of the
+        interactions of order three and more; the last four fields are ``sobol_indices``'s.  Closed form
+        (``_sobol_numpy``); ``is_gpu=True`` runs the HIP kernels (``gp_sobol_interactions_f64``, float64 only) and never
+        falls back.  See ``perband.sobol_interactions_bands``.  Not in the reference."""
+        from . import perband
+        r = perband.sobol_interactions_bands([self], bounds, is_gpu=is_gpu)
+        boxed = np.ndim(bounds[0]) == 2
+        return r._replace(**{k: (v[:, 0] if boxed else v[0]) for k, v in r._asdict().items()})
+
+    def main_effects(self, bounds, grid=None, n_grid=33, is_gpu=False):
+        """Main-effect curves on ``bounds`` as ``sobol_indices`` takes them: ``MainEffects(grid (D, G), effect (D, G),
+        mean)`` with ``effect[d, g] = E[mu | t_d = grid[d, g]] - E[mu]``.  ``grid`` (D, G) -- or (n_boxes, D, G) -- holds
+        the points of input d; ``None`` means ``n_grid`` equally spaced points from ``lo`` to ``hi`` inclusive.
+        ``is_gpu=True`` runs the HIP kernel (``gp_sobol_main_effects_f64``, float64 only) and never falls back.  See
+        ``perband.main_effects_bands``.  Not in the reference."""
+        from . import perband
+        r = perband.main_effects_bands([self], bounds, grid=grid, n_grid=n_grid, is_gpu=is_gpu)
+        boxed = np.ndim(bounds[0]) == 2
+        return r._replace(effect=r.effect[:, 0] if boxed else r.effect[0], mean=r.mean[:, 0] if boxed else r.mean[0])
+
     # ------------------------------------------------------------------ Gaussian input uncertainty
     def predict_uncertain(self, X, cov, is_gpu=False):
         """Predict at uncertain inputs ``x_m ~ N(X[m], cov[m])`` -- ``X`` (M, D), ``cov`` (D, D) or (M, D, D), positive

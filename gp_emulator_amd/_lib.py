@@ -18,7 +18,7 @@ from ._dense_numpy import (DAMPINGS, active_set_numpy, box_pass_cap, box_step_nu
 from ._lut_numpy import MAX_PCS as lut_pc_max_pcs  # noqa: F401
 from ._lut_numpy import lut_pc_prepare_numpy, lut_posterior_numpy, lut_search_numpy, lut_search_pc_numpy  # noqa: F401
 from ._moments_numpy import rows_arrays as _moments_rows
-from ._sobol_numpy import bounds_arrays as _sobol_bounds
+from ._sobol_numpy import bounds_arrays as _sobol_bounds, grid_array as _sobol_grid
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GP_PREDICT_LIB lets tools/ab_bench.py time differently-built variants of the library on
@@ -134,6 +134,10 @@ SIGNATURES = {
                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gp_sobol_batch_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p, c_void_p]),
+    "gp_sobol_interactions_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_void_p]),
+    "gp_sobol_main_effects_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_void_p]),
     "gp_moments_batch_f64": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_i64, c_void_p,
                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gp_pack_sizes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
@@ -1075,6 +1079,53 @@ class Context:
               "gp_sobol_batch_f64")
         return (mean, cov) if boxed else (mean[0], cov[0])
 
+    @staticmethod
+    def _sobol_arrays(expX, inputs, invQt, lo, hi):
+        """The emulators and boxes of the Sobol entries as contiguous float64, checked: (expX, inputs, invQt, lo, hi, boxed)."""
+        expX = np.ascontiguousarray(np.atleast_2d(expX), dtype=np.float64)
+        inputs = np.ascontiguousarray(inputs, dtype=np.float64)
+        invQt = np.ascontiguousarray(np.atleast_2d(invQt), dtype=np.float64)
+        if inputs.ndim != 2:
+            raise ValueError("inputs must be (n_train, n_inputs)")
+        (N, D), E = inputs.shape, expX.shape[0]
+        if expX.shape != (E, D + 2):
+            raise ValueError("expX must be (n_emulators, n_inputs + 2), got %s" % (expX.shape,))
+        if invQt.shape != (E, N):
+            raise ValueError("invQt must be (n_emulators, n_train), got %s" % (invQt.shape,))
+        return (expX, inputs, invQt) + _sobol_bounds(lo, hi, D)
+
+    def sobol_interactions(self, expX, inputs, invQt, lo, hi, pairs=None):
+        """``inter`` of ``gp_sobol_interactions_f64``: the emulators, boxes and ``pairs`` of ``sobol_batch``; for every pair
+        of emulators the interaction covariances ``V2^{ik}`` of the input pairs ``_sobol_numpy.input_pairs(D)``,
+        (P, D (D - 1) / 2), with a leading ``n_boxes`` axis for 2-D bounds; (P, 0) for ``D = 1``.  float64 only.
+        ``_sobol_numpy.interactions_numpy`` is the numpy branch and ``_sobol_numpy.second_order`` turns it into indices."""
+        expX, inputs, invQt, lo, hi, boxed = self._sobol_arrays(expX, inputs, invQt, lo, hi)
+        (N, D), E = inputs.shape, expX.shape[0]
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+            if pairs.ndim != 2 or pairs.shape[1] != 2:
+                raise ValueError("pairs must be (n_pairs, 2)")
+        B, P = lo.shape[0], E if pairs is None else pairs.shape[0]
+        inter = np.empty((B, P, D * (D - 1) // 2))
+        check(self.lib.gp_sobol_interactions_f64(self.h, E, _ptr(expX), _ptr(inputs), _ptr(invQt), N, D, B, _ptr(lo),
+                                                 _ptr(hi), P, None if pairs is None else _ptr(pairs), _ptr(inter)),
+              "gp_sobol_interactions_f64")
+        return inter if boxed else inter[0]
+
+    def sobol_main_effects(self, expX, inputs, invQt, lo, hi, grid):
+        """``effect`` of ``gp_sobol_main_effects_f64``: the emulators and boxes of ``sobol_batch`` and ``grid`` (D, G) --
+        or (n_boxes, D, G) -- of points of input d (inside the box or not); the main-effect curves
+        ``E[mu_e | t_d = grid[d, g]] - E[mu_e]``, (E, D, G), with a leading ``n_boxes`` axis for 2-D bounds.  float64
+        only.  ``_sobol_numpy.main_effects_numpy`` is the numpy branch."""
+        expX, inputs, invQt, lo, hi, boxed = self._sobol_arrays(expX, inputs, invQt, lo, hi)
+        (N, D), E = inputs.shape, expX.shape[0]
+        grid = _sobol_grid(grid, lo, hi)
+        B, G = lo.shape[0], grid.shape[2]
+        effect = np.empty((B, E, D, G))
+        check(self.lib.gp_sobol_main_effects_f64(self.h, E, _ptr(expX), _ptr(inputs), _ptr(invQt), N, D, B, _ptr(lo),
+                                                 _ptr(hi), G, _ptr(grid), _ptr(effect)), "gp_sobol_main_effects_f64")
+        return effect if boxed else effect[0]
+
     def moments_batch(self, expX, inputs, invQt, invQ, mean_in, cov_in, pairs=None):
         """``(mean (M, E), egrad (M, E, D), cov (M, P), evar (M, E) or None, info (M,) int32)`` of
         ``gp_moments_batch_f64``: for E emulators on shared ``inputs`` (N, D) with ``expX`` (E, D + 2), ``invQt`` (E, N)
@@ -1521,14 +1572,15 @@ GP_OP_LUT_SEARCH_PC = 8
 GP_OP_SOBOL = 9
 GP_OP_MOMENTS = 10
 GP_OP_LUT_POSTERIOR = 11
+GP_OP_SOBOL_INTER = 12
 PLAN_KERNELS = {1: "predict_few", 2: "predict", 3: "generic", 4: "hessian_valu", 5: "hessian_win_kl3",
                 6: "hessian_win_kl4", 7: "hessian_win_direct", 8: "reconstruct_narrow", 9: "reconstruct_wide",
                 10: "misfit", 11: "mv_gram", 12: "var_grad", 13: "lut_search", 14: "lut_search_pc", 15: "sobol",
-                16: "moments", 17: "lut_posterior"}
+                16: "moments", 17: "lut_posterior", 18: "sobol_inter"}
 _PLAN_OPS = {"predict": GP_OP_PREDICT, "mean_grad": GP_OP_MEAN_GRAD, "hessian": GP_OP_HESSIAN,
              "reconstruct": GP_OP_RECONSTRUCT, "misfit": GP_OP_MISFIT, "mv_gram": GP_OP_MV_GRAM, "var_grad": GP_OP_VAR_GRAD,
              "lut_search": GP_OP_LUT_SEARCH, "lut_search_pc": GP_OP_LUT_SEARCH_PC, "sobol": GP_OP_SOBOL,
-             "moments": GP_OP_MOMENTS, "lut_posterior": GP_OP_LUT_POSTERIOR}
+             "moments": GP_OP_MOMENTS, "lut_posterior": GP_OP_LUT_POSTERIOR, "sobol_inter": GP_OP_SOBOL_INTER}
 
 
 def lut_search_geometry():
@@ -1576,7 +1628,8 @@ def launch_plan(op, precision, n_rows, n_train=0, n_inputs=0, n_emulators=1, n_p
     and ``term_chunk`` (``lut_search_geometry``).  "lut_search_pc" takes ``n_pcs`` and ``n_candidates``: the same
     items and slices, with ``candidate_tile``, ``padded_pcs`` and ``workgroups_per_cu`` (``lut_search_pc_geometry``).
     "sobol" takes ``n_rows`` boxes, ``n_emulators`` pairs, ``n_train`` and ``n_inputs``: an item is ``rows_per_item``
-    training rows of one (box, pair).  "moments" takes ``n_rows``, ``n_emulators`` pairs, ``n_train`` and ``n_inputs``:
+    training rows of one (box, pair); "sobol_inter" (``gp_sobol_interactions_f64``) takes the same and plans no items
+    for ``n_inputs = 1``.  "moments" takes ``n_rows``, ``n_emulators`` pairs, ``n_train`` and ``n_inputs``:
     an item is one (row, pair).  "lut_posterior" takes ``n_inputs`` (the states' n_dims) and ``n_candidates``: the
     search's items, with ``slices`` (capped by the scratch budget of the partial sums), ``candidate_tile``,
     ``term_chunk``, ``padded_dims`` and ``workgroups_per_cu`` (``lut_posterior_geometry``)."""

@@ -130,7 +130,7 @@ def _build(force, jobs, verbose, defines, OBJ, LIB, only_units):
               ("gp_series_tu.hip", "series", []),
               ("gp_lut_search_tu.hip", "lut_search", []), ("gp_lut_search_pc_tu.hip", "lut_search_pc", []),
               ("gp_lut_posterior_tu.hip", "lut_posterior", []),
-              ("gp_train_tu.hip", "train", []), ("gp_sobol_tu.hip", "sobol", []),
+              ("gp_train_tu.hip", "train", []), ("gp_sobol_tu.hip", "sobol", []), ("gp_sobol2_tu.hip", "sobol2", []),
               ("gp_moments_tu.hip", "moments", [])]
     # the host units (gp_host.hpp lists them)
     units += [("gp_%s.hip" % u, "gp_" + u, []) for u in ("ctx", "model", "device", "solve", "host_path", "folds", "mv")]

@@ -356,6 +356,14 @@ int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators
     k = GP_PLAN_SOBOL;
     rpi = gpk::skRows;
     g = gpk::plan_sobol(n_rows, n_emulators, n_train, gpk::sobol_cap(compute_units, n_inputs));
+  } else if (op == GP_OP_SOBOL_INTER) {
+    // (n_emulators = n_pairs here; n_rows = n_boxes; n_inputs = 1: nothing to launch)
+    if (n_train <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+    if (n_inputs > gpk::skMaxD || n_train > gpk::skMaxN)
+      return fail(GP_ERR_UNSUPPORTED, "the Sobol kernels serve n_train <= %d, n_inputs <= %d", gpk::skMaxN, gpk::skMaxD);
+    k = GP_PLAN_SOBOL_INTER;
+    rpi = gpk::skRows;
+    g = gpk::plan_sobol_inter(n_rows, n_emulators, n_train, n_inputs, gpk::sobol_inter_cap(compute_units));
   } else if (op == GP_OP_MOMENTS) {
     // (n_emulators = n_pairs here)
     if (n_train <= 0 || n_inputs <= 0) return fail(GP_ERR_INVALID, "bad sizes");

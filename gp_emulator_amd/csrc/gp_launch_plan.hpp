@@ -183,6 +183,22 @@ inline GridPlan plan_sobol(long long n_boxes, long long n_pairs, int n_train, lo
   return plan_grid(n_train, skRows, n_boxes * n_pairs, cap);
 }
 
+// sobol_inter_kernel: sobol_pair_kernel's items, limits and padded instances (plan_sobol).  The instances of 12 and 16
+// inputs take more than 256 registers (DM (DM - 1) / 2 accumulators), so a CU holds one 4-wave workgroup of them; the
+// instance of 8 takes 240 and is planned the same way (two a CU have not been measured).  A single input has no pair
+// of inputs: nothing is launched.
+constexpr int skInterWgsPerCu = 1;
+inline long long sobol_inter_cap(int compute_units) { return (long long)compute_units * skInterWgsPerCu; }
+inline GridPlan plan_sobol_inter(long long n_boxes, long long n_pairs, int n_train, int n_inputs, long long cap) {
+  if (n_inputs < 2) return GridPlan{0, 0};
+  return plan_sobol(n_boxes, n_pairs, n_train, cap);
+}
+// sobol_main_kernel: an item is one (box, emulator) over all inputs and grid points; 72 KB of LDS, two workgroups a CU
+constexpr int smThreads = 256;
+inline GridPlan plan_sobol_main(long long n_boxes, long long n_emulators, int compute_units) {
+  return plan_grid(1, 1, n_boxes * n_emulators, 2LL * compute_units);
+}
+
 // moments_pair_kernel: an item is one (row, pair) over all n_train x n_train; plan_grid with one row per item.  The
 // instance is the padded n_inputs (8, 12 or 16: the width of the g table in LDS, 512 x padded doubles, which with the
 // other tables is 52, 69 and 85 KB of a CU's 160; two workgroups a CU where the registers allow it without spills).  The rows of a call run in slabs whose

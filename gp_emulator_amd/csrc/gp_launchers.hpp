@@ -33,6 +33,8 @@ template <typename T> struct LutPostArgs;
 template <typename T> struct LutPcSolveArgs;
 struct TrainArgs;
 struct SobolArgs;
+struct SobolInterArgs;
+struct SobolMainArgs;
 struct MomentsArgs;
 
 #pragma GCC visibility push(hidden)      // (the launchers are the library's own)
@@ -80,6 +82,10 @@ template <typename T> hipError_t launch_lut_posterior(const LutPostArgs<T>&, int
 hipError_t launch_likelihood(const TrainArgs&, int n_sets, hipStream_t);      // fp64 only
 // sobol_pair_kernel on `grid` workgroups (the instance by n_inputs), then sobol_fold_kernel; fp64 only
 hipError_t launch_sobol(const SobolArgs&, int grid, hipStream_t);
+// sobol_inter_kernel on `grid` workgroups (the instance by n_inputs), then sobol_inter_fold_kernel; sobol_main_kernel
+// on `grid` workgroups; fp64 only
+hipError_t launch_sobol_inter(const SobolInterArgs&, int grid, hipStream_t);
+hipError_t launch_sobol_main(const SobolMainArgs&, int grid, hipStream_t);
 // moments_flag_kernel, once per call; then per slab of rows moments_prepare_kernel, moments_mean_kernel and
 // moments_pair_kernel on `grid` workgroups (the instance by n_inputs); fp64 only
 hipError_t launch_moments_flags(const MomentsArgs&, hipStream_t);

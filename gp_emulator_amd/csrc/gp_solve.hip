@@ -17,6 +17,7 @@
 #include "gp_series_kernel.hpp"
 #include "gp_moments_args.hpp"
 #include "gp_sobol_args.hpp"
+#include "gp_sobol2_args.hpp"
 
 // what a launcher returned, as the entry's status
 static int launched(hipError_t e, const char* kernel) {
@@ -39,6 +40,25 @@ static int row_stride(const char* what, const void* ptr, int64_t stride, int64_t
   if (stride != 0 && stride < row_elems)
     return fail(GP_ERR_INVALID, "%s stride %lld is neither 0 nor >= %lld", what, (long long)stride, (long long)row_elems);
   if (stride != 0 && !ptr) return fail(GP_ERR_INVALID, "%s stride without a pointer", what);
+  return GP_OK;
+}
+
+// the argument checks the interaction and main-effect entries share with gp_sobol_batch_f64 (pairs: n_pairs < 0 = none);
+// that entry keeps its own copy of them, word for word: one function for the three is a later merge
+static int sobol2_checks(int n_emulators, int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi,
+                         int n_pairs, const int32_t* pairs) {
+  if (n_emulators <= 0 || n_train <= 0 || n_inputs <= 0 || n_boxes <= 0 || n_pairs == 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (n_inputs > gpk::skMaxD || n_train > gpk::skMaxN)
+    return fail(GP_ERR_UNSUPPORTED, "the Sobol kernels serve n_train <= %d, n_inputs <= %d", gpk::skMaxN, gpk::skMaxD);
+  if (n_pairs > 0 && !pairs && n_pairs != n_emulators) return fail(GP_ERR_INVALID, "without a pair list n_pairs is n_emulators");
+  if (n_pairs > 0 && pairs)
+    for (size_t k = 0; k < 2 * (size_t)n_pairs; ++k)
+      if (pairs[k] < 0 || pairs[k] >= n_emulators)
+        return fail(GP_ERR_INVALID, "pair %lld names emulator %d of %d", (long long)(k / 2), pairs[k], n_emulators);
+  for (size_t k = 0; k < (size_t)n_boxes * n_inputs; ++k)
+    if (!(hi[k] > lo[k]) || !(hi[k] - lo[k] <= 1.79769313486231570815e308) || !(lo[k] >= -1.79769313486231570815e308))
+      return fail(GP_ERR_INVALID, "box %lld, input %lld: the bounds must be finite with hi > lo", (long long)(k / n_inputs),
+                  (long long)(k % n_inputs));
   return GP_OK;
 }
 
@@ -662,6 +682,84 @@ int gp_sobol_batch_f64(gp_ctx* ctx, int n_emulators, const double* expX, const d
   if (int rc = launched(gpk::launch_sobol(a, plan.workgroups, st), "sobol")) return rc;
   HIP_TRY(hipMemcpyAsync(mean, d_mean, sizeof(double) * n_mean, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(cov, d_cov, sizeof(double) * n_cov, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GP_OK;
+}
+
+int gp_sobol_interactions_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs, const double* invQt,
+                              int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi, int n_pairs,
+                              const int32_t* pairs, double* inter) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!expX || !inputs || !invQt || !lo || !hi || !inter) return fail(GP_ERR_INVALID, "null pointer");
+  if (n_pairs < 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (int rc = sobol2_checks(n_emulators, n_train, n_inputs, n_boxes, lo, hi, n_pairs, pairs)) return rc;
+  if (n_inputs < 2) return GP_OK;      // (no pair of inputs: inter is empty)
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t E = (size_t)n_emulators, N = (size_t)n_train, D = (size_t)n_inputs, B = (size_t)n_boxes, P = (size_t)n_pairs;
+  const size_t K = D * (D - 1) / 2, JB = (N + gpk::skRows - 1) / gpk::skRows;
+  const gpk::GridPlan plan =
+      gpk::plan_sobol_inter(n_boxes, n_pairs, n_train, n_inputs, gpk::sobol_inter_cap(ctx->compute_units));
+  const size_t n_theta = E * (D + 2), n_in = N * D, n_al = E * N, n_box = B * D, n_part = B * P * JB * K, n_out = B * P * K,
+               n_pair = pairs ? P : 0;      // (the pairs last: two int32 per double)
+  if (int rc = ensure_scratch(ctx, sizeof(double) * (n_theta + n_in + n_al + 2 * n_box + n_part + n_out + n_pair))) return rc;
+  double* d_theta = (double*)ctx->scratch;
+  double* d_in = d_theta + n_theta;
+  double* d_al = d_in + n_in;
+  double* d_lo = d_al + n_al;
+  double* d_hi = d_lo + n_box;
+  double* d_part = d_hi + n_box;
+  double* d_out = d_part + n_part;
+  int* d_pairs = pairs ? (int*)(d_out + n_out) : nullptr;
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(d_theta, expX, sizeof(double) * n_theta, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_in, inputs, sizeof(double) * n_in, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_al, invQt, sizeof(double) * n_al, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_lo, lo, sizeof(double) * n_box, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_hi, hi, sizeof(double) * n_box, hipMemcpyHostToDevice, st));
+  if (pairs) HIP_TRY(hipMemcpyAsync(d_pairs, pairs, sizeof(int32_t) * 2 * P, hipMemcpyHostToDevice, st));
+  gpk::SobolInterArgs a;
+  a.expX = d_theta, a.inputs = d_in, a.alpha = d_al, a.lo = d_lo, a.hi = d_hi, a.pairs = d_pairs;
+  a.part = d_part, a.inter = d_out;
+  a.N = n_train, a.D = n_inputs, a.E = n_emulators, a.B = n_boxes, a.P = n_pairs, a.JB = (int)JB;
+  a.items = plan.items;
+  if (int rc = launched(gpk::launch_sobol_inter(a, plan.workgroups, st), "sobol interactions")) return rc;
+  HIP_TRY(hipMemcpyAsync(inter, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return GP_OK;
+}
+
+int gp_sobol_main_effects_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs, const double* invQt,
+                              int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi, int n_grid,
+                              const double* grid, double* effects) {
+  if (!ctx) return fail(GP_ERR_INVALID, "null context");
+  if (!expX || !inputs || !invQt || !lo || !hi || !grid || !effects) return fail(GP_ERR_INVALID, "null pointer");
+  if (n_grid <= 0) return fail(GP_ERR_INVALID, "bad sizes");
+  if (int rc = sobol2_checks(n_emulators, n_train, n_inputs, n_boxes, lo, hi, -1, nullptr)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t E = (size_t)n_emulators, N = (size_t)n_train, D = (size_t)n_inputs, B = (size_t)n_boxes, G = (size_t)n_grid;
+  const gpk::GridPlan plan = gpk::plan_sobol_main(n_boxes, n_emulators, ctx->compute_units);
+  const size_t n_theta = E * (D + 2), n_in = N * D, n_al = E * N, n_box = B * D, n_grd = B * D * G, n_out = B * E * D * G;
+  if (int rc = ensure_scratch(ctx, sizeof(double) * (n_theta + n_in + n_al + 2 * n_box + n_grd + n_out))) return rc;
+  double* d_theta = (double*)ctx->scratch;
+  double* d_in = d_theta + n_theta;
+  double* d_al = d_in + n_in;
+  double* d_lo = d_al + n_al;
+  double* d_hi = d_lo + n_box;
+  double* d_grid = d_hi + n_box;
+  double* d_out = d_grid + n_grd;
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(d_theta, expX, sizeof(double) * n_theta, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_in, inputs, sizeof(double) * n_in, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_al, invQt, sizeof(double) * n_al, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_lo, lo, sizeof(double) * n_box, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_hi, hi, sizeof(double) * n_box, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_grid, grid, sizeof(double) * n_grd, hipMemcpyHostToDevice, st));
+  gpk::SobolMainArgs a;
+  a.expX = d_theta, a.inputs = d_in, a.alpha = d_al, a.lo = d_lo, a.hi = d_hi, a.grid = d_grid, a.effects = d_out;
+  a.N = n_train, a.D = n_inputs, a.E = n_emulators, a.B = n_boxes, a.G = n_grid;
+  a.items = plan.items;
+  if (int rc = launched(gpk::launch_sobol_main(a, plan.workgroups, st), "sobol main effects")) return rc;
+  HIP_TRY(hipMemcpyAsync(effects, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return GP_OK;
 }

@@ -1035,6 +1035,37 @@ class MultivariateEmulator(object):
                                         pairs=_sobol_numpy.upper_pairs(P), is_gpu=is_gpu)
         return _sobol_numpy.spectral(np.asarray(self.basis_functions)[:P], mean, _sobol_numpy.mirror(cov, P))
 
+    def sobol_interactions(self, bounds, is_gpu=True):
+        """Second-order Sobol indices of every band of the reconstructed output on ``bounds`` as ``sobol`` takes them:
+        ``SobolInteractions(second (D, D, N_full), higher (N_full,), first (D, N_full), total (D, N_full), variance
+        (N_full,), mean (N_full,))``; ``second[i, k, n] = beta_n' V2^{ik} beta_n / beta_n' V beta_n`` off the diagonal
+        (symmetric in i, k) and ``first`` on it, ``higher`` the share of the interactions of order three and more.  The
+        interaction covariances of all ``P (P + 1) / 2`` pairs of PCs come from one ``gp_sobol_interactions_f64`` call
+        and the last four fields from the ``gp_sobol_batch_f64`` call of ``sobol`` (``is_gpu=False``: the numpy
+        branch).  Not in the reference."""
+        from . import _sobol_numpy, perband
+        P = self.n_pcs
+        consts, pairs = perband._sobol_constants(self.emulators), _sobol_numpy.upper_pairs(P)
+        mean, cov = perband.sobol_pairs(*consts, bounds, pairs=pairs, is_gpu=is_gpu)
+        inter = perband.sobol_interaction_pairs(*consts, bounds, pairs=pairs, is_gpu=is_gpu)
+        basis = np.asarray(self.basis_functions)[:P]
+        covm = _sobol_numpy.mirror(cov, P)
+        r = _sobol_numpy.spectral(basis, mean, covm)
+        second, higher = _sobol_numpy.spectral_second(basis, covm, _sobol_numpy.mirror(inter, P))
+        return _sobol_numpy.SobolInteractions(second, higher, r.first, r.total, r.variance, r.mean)
+
+    def main_effects(self, bounds, grid=None, n_grid=33, is_gpu=True):
+        """Main-effect curves of every band of the reconstructed output: ``MainEffects(grid (D, G), effect
+        (D, G, N_full), mean (N_full,))`` with ``effect[d, g, n] = E[f_n | t_d = grid[d, g]] - E[f_n]``.  The curve is
+        linear in the emulator: the PCs' curves from one ``gp_sobol_main_effects_f64`` call (``is_gpu=False``: the numpy
+        branch) times the basis, on the host like the band means.  ``grid`` and ``n_grid`` as
+        ``GaussianProcess.main_effects``; a leading ``n_boxes`` axis for 2-D bounds.  Not in the reference."""
+        from . import perband
+        P = self.n_pcs
+        r = perband.main_effects_bands(self.emulators[:P], bounds, grid=grid, n_grid=n_grid, is_gpu=is_gpu)
+        basis = np.asarray(self.basis_functions, dtype=np.float64)[:P]
+        return r._replace(effect=np.einsum("...pdg,pn->...dgn", r.effect, basis), mean=r.mean @ basis)
+
     # ---- Gaussian input uncertainty ----------------------------------------------------------------
     def predict_uncertain(self, Y, cov, is_gpu=True, return_pc=False):
         """The reconstructed spectrum ``f_k = sum_p basis[p, k] mu_p`` under Gaussian inputs ``y_m ~ N(Y[m], cov[m])``

@@ -151,6 +151,52 @@ def sobol_bands(gps, bounds, is_gpu=True, device=None):
     return _sobol_numpy.SobolIndices(first, total, variance, mean)
 
 
+def sobol_interaction_pairs(expX, inputs, invQt, bounds, pairs=None, is_gpu=True, device=None):
+    """``inter`` of ``Context.sobol_interactions`` on the default context of ``device``, or with ``is_gpu=False`` of its
+    numpy branch ``_sobol_numpy.interactions_numpy``."""
+    if is_gpu:
+        return _lib.default_context(device).sobol_interactions(expX, inputs, invQt, bounds[0], bounds[1], pairs)
+    return _sobol_numpy.interactions_numpy(expX, inputs, invQt, bounds[0], bounds[1], pairs)
+
+
+def sobol_interactions_bands(gps, bounds, is_gpu=True, device=None):
+    """Second-order Sobol indices of the E emulators in ``gps`` (shared training inputs) on ``bounds = (lo, hi)``, each
+    (D,) or (n_boxes, D): ``SobolInteractions(second (E, D, D), higher (E,), first, total, variance, mean)``.
+    ``second`` is symmetric with ``S_ik = V2^{ik} / V`` off the diagonal -- which input ``i`` interacts with when
+    ``total[i] - first[i]`` is large -- and ``first`` on it; ``higher = 1 - sum_{i <= k} second`` is the share of the
+    interactions of order three and more; NaN where ``V <= 0``.  The last four fields are ``sobol_bands``'s, from one
+    ``gp_sobol_batch_f64`` call; the interaction covariances from one ``gp_sobol_interactions_f64`` call (float64 only).
+    ``is_gpu=False`` is the numpy branch.  A leading ``n_boxes`` axis for 2-D bounds."""
+    consts = _sobol_constants(gps)
+    mean, cov = sobol_pairs(*consts, bounds, is_gpu=is_gpu, device=device)
+    inter = sobol_interaction_pairs(*consts, bounds, is_gpu=is_gpu, device=device)
+    first, total, variance = _sobol_numpy.indices(cov)
+    second, higher = _sobol_numpy.second_order(cov, inter)
+    return _sobol_numpy.SobolInteractions(second, higher, first, total, variance, mean)
+
+
+def main_effects_bands(gps, bounds, grid=None, n_grid=33, is_gpu=True, device=None):
+    """Main-effect curves of the E emulators in ``gps`` on ``bounds = (lo, hi)``, each (D,) or (n_boxes, D):
+    ``MainEffects(grid (D, G), effect (E, D, G), mean (E,))`` with ``effect[e, d, g] = E[mu_e | t_d = grid[d, g]] - mean[e]``
+    -- the picture next to the indices; its mean over ``t_d`` is 0 and its mean square ``first[d] * variance``.
+    ``grid`` is (D, G) or (n_boxes, D, G) of points of input d (outside the box is allowed); ``None`` means ``n_grid``
+    equally spaced points from ``lo`` to ``hi`` inclusive.  One ``gp_sobol_main_effects_f64`` call (float64 only; the
+    means from ``gp_sobol_batch_f64``); ``is_gpu=False`` is the numpy branch.  A leading ``n_boxes`` axis for 2-D bounds."""
+    expX, inputs, invQt = _sobol_constants(gps)
+    lo, hi, boxed = _sobol_numpy.bounds_arrays(bounds[0], bounds[1], inputs.shape[1])
+    grid = _sobol_numpy.grid_array(grid, lo, hi, n_grid)
+    if is_gpu:
+        ctx = _lib.default_context(device)
+        effect = ctx.sobol_main_effects(expX, inputs, invQt, lo, hi, grid)
+        mean, _ = ctx.sobol_batch(expX, inputs, invQt, lo, hi)
+    else:
+        effect = _sobol_numpy.main_effects_numpy(expX, inputs, invQt, lo, hi, grid)
+        mean = _sobol_numpy.means_numpy(expX, inputs, invQt, lo, hi)
+    if not boxed:
+        grid, effect, mean = grid[0], effect[0], mean[0]
+    return _sobol_numpy.MainEffects(grid, effect, mean)
+
+
 def _moments_constants(gps):
     """``_sobol_constants`` and invQ (E, N, N) -- None when an emulator has none."""
     expX, inputs, invQt = _sobol_constants(gps)

@@ -840,6 +840,28 @@ int gp_sobol_batch_f64(gp_ctx* ctx, int n_emulators, const double* expX, const d
                        int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi, int n_pairs,
                        const int32_t* pairs, double* mean, double* cov);
 
+/* ---- Sobol interaction covariances and main-effect curves, closed form ---------------------------------
+ * The emulators, boxes and pairs as in gp_sobol_batch_f64.  gp_sobol_interactions_f64: for every box, every pair (p, q)
+ * and the input pairs i < k in the order (0,1), (0,2), .., (n_inputs-2, n_inputs-1),
+ *     inter [n_boxes][n_pairs][n_inputs (n_inputs - 1) / 2]
+ *           V2^{ik} = Cov(E[mu_p | t_i, t_k], E[mu_q | t_i, t_k]) - Vm^i - Vm^k = sum_jl a_jl cov_i cov_k prod_{d != i,k} cc_d,
+ * the lower orders subtracted term by term; for p = q the second-order index is V2^{ik} / V.  n_inputs = 1 is valid and
+ * writes nothing.  gp_sobol_main_effects_f64: for every box, emulator and input d, at the n_grid points
+ * grid [n_boxes][n_inputs][n_grid] of that input (inside the box or not),
+ *     effects [n_boxes][n_emulators][n_inputs][n_grid]      E[mu_e | t_d = t] - E[mu_e],
+ * whose mean over t_d ~ U[lo_d, hi_d] is 0 and whose mean square is Vm^d of the pair (e, e).  No atomics: a (box, pair)
+ * row of inter is bit for bit the same alone or in any batch, in any pair order, on any grid (gp_launch_plan,
+ * GP_OP_SOBOL_INTER); an (emulator, input, point) of effects is summed serially over the training points and is the
+ * same bits in any batch and for any n_grid.  A non-finite expX or invQt entry gives NaN in every output the emulator
+ * takes part in and changes no other.  Errors as gp_sobol_batch_f64 (n_grid <= 0 and a NULL grid: GP_ERR_INVALID).
+ * Nothing is written on an error.  Host pointers, fp64 only, synchronous. */
+int gp_sobol_interactions_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs, const double* invQt,
+                              int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi, int n_pairs,
+                              const int32_t* pairs, double* inter);
+int gp_sobol_main_effects_f64(gp_ctx* ctx, int n_emulators, const double* expX, const double* inputs, const double* invQt,
+                              int n_train, int n_inputs, int n_boxes, const double* lo, const double* hi, int n_grid,
+                              const double* grid, double* effects);
+
 /* ---- Moments of the emulators under a Gaussian input, closed form -------------------------------------
  * The emulators as in gp_sobol_batch_f64, with invQ [n_emulators][n_train][n_train] or NULL; n_rows inputs
  * x ~ N(mean_in[m], cov_in[m]), mean_in [n_rows][n_inputs], cov_in [n_rows][n_inputs][n_inputs] (only the lower
@@ -901,6 +923,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_OP_SOBOL 9              /* gp_sobol_batch_f64: n_emulators is n_pairs and n_rows n_boxes; an item is 16 training rows */
 #define GP_OP_MOMENTS 10           /* gp_moments_batch_f64: n_emulators is n_pairs; an item is one (row, pair) */
 #define GP_OP_LUT_POSTERIOR 11     /* gp_lut_posterior_device: n_inputs is n_dims and aux n_candidates; rest_items is n_slices */
+#define GP_OP_SOBOL_INTER 12       /* gp_sobol_interactions_f64: as GP_OP_SOBOL; n_inputs = 1 launches nothing (0 items) */
 #define GP_PLAN_PREDICT_FEW 1     /* predict_few_kernel: a workgroup per 16-row tile */
 #define GP_PLAN_PREDICT 2          /* predict_kernel (throughput form), with or without the variance */
 #define GP_PLAN_GENERIC 3          /* predict_generic_kernel */
@@ -918,6 +941,7 @@ int gp_pack_sizes(int dtype, int n_train, int n_inputs, int* kernel_d, int* kern
 #define GP_PLAN_SOBOL 15           /* sobol_pair_kernel: items = n_boxes x n_pairs x ceil(n_train / 16); one workgroup per CU */
 #define GP_PLAN_MOMENTS 16         /* moments_pair_kernel: items = n_rows x n_pairs; 2 workgroups per CU for n_inputs <= 12, 1 beyond */
 #define GP_PLAN_LUT_POSTERIOR 17   /* lut_posterior_kernel: an item is 256 rows x one slice of the candidates; one workgroup per CU */
+#define GP_PLAN_SOBOL_INTER 18     /* sobol_inter_kernel: sobol_pair_kernel's items; one workgroup per CU */
 int gp_launch_plan(int op, int dtype, int n_train, int n_inputs, int n_emulators, int64_t n_rows, int aux,
                    int compute_units, int aligned16, int* kernel, int64_t* items, int* workgroups,
                    int64_t* rest_items, int* rest_workgroups, int* rows_per_item);
